@@ -2,7 +2,14 @@
 """Benchmark of the moment-matched GP rollout (BASELINE.json metric) on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5] [--scaling weak|strong]
-                  [--recipe pilco|baseline|worst]
+                  [--recipe pilco|baseline|worst] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`); nothing else runs.
+--full adds everything else this file measures or checks: the other data regimes of c3, the staged pass behind `segments_ms`
+and the roofline blocks, the off-diagonal item statistics, parity against the CPU oracles, the CPU baselines and the next-row
+timings (c3_grad, c1 and c5: their own extra passes, parity and CPU baselines).
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64 as
+computed; at most 64 MB in all, else a fixed seeded sample of each array); the inputs are seeded, identical from run to run.
 
 One "step" = one pass of the hot path over the local batch: q stage + fused Q reduce (+ Euler moment update
 where the state is closed, d == L).  Per-step expected costs are evaluated and all-gathered once per H-step
@@ -27,7 +34,7 @@ Recipes (the reduce kernels choose range tiers per tile, so their time depends o
   pilco     lengthscales log-uniform [0.7, 3], contracting targets: the state stays inside the data's support for
             the whole closed rollout (DESIGN.md section 5) -- default for c1_closed, c2;
   worst     the pilco data with MM_FORCE_WORST_TIER: every tile takes its most expensive tier.
-The default N = 1 run of c3 times all three in one process (each with the same --steps / --warmup) and reports them
+The default N = 1 run of c3 with --full times all three in one process (each with the same --steps / --warmup) and reports them
 under `regimes`; `value`, `ms_per_step`, `segments_ms`, `roofline`, `parity`, `cpu_baseline` describe the baseline one.
 
 Output: rank 0 prints ONE compact strict-JSON line (< 6000 bytes: the contract keys, `config`, `roofline` with numbers only,
@@ -273,7 +280,39 @@ def parse():
   ap.add_argument("--pmc-run", action="store_true", help="set by tools/collect_pmc.sh: exact --steps, no rounding to rollouts")
   ap.add_argument("--rehearse-gloo", action="store_true",
                   help="multi-process rehearsal on ONE GPU: gloo backend, every rank on cuda:0, costs gathered via host")
+  ap.add_argument("--full", action="store_true",
+                  help="also run everything beyond the timed steps: other regimes, staged pass + roofline, parity, CPU baselines, next rows")
+  ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                  help="write the arrays the timed path returned in its last timed step to DIR/<name>.npy (rank 0)")
   return ap.parse_args()
+
+
+DUMP_LIMIT = 64 << 20                                      # bytes, all .npy files of one --dump-outputs together
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT):
+  """--dump-outputs: every array as <path>/<name>.npy, float32 or float64 as computed (other dtypes as float64).  Where they
+  exceed `limit` bytes together, each is replaced by a fixed, seeded sample of its flattened entries (the same indices on
+  every run), its share of the budget in proportion to its size."""
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  arrs = {}
+  for name, a in arrays.items():
+    a = np.asarray(a)
+    arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+  total = sum(a.nbytes for a in arrs.values())
+  budget = limit - 4096 * len(arrs)                        # room for the .npy headers
+  for name, a in arrs.items():
+    if total > limit:
+      keep = min(a.size, max(1, a.size * budget // total))
+      idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+      a = a.reshape(-1)[idx]
+    np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+def host_arrays(**tensors):
+  """Device tensors -> numpy copies (taken right after the timed region, before anything else runs on the device)."""
+  return {k: v.detach().cpu().numpy() for k, v in tensors.items() if v is not None}
 
 
 def spawn_ranks(args):
@@ -518,10 +557,10 @@ def main():
   steps = args.steps                                       # EXACTLY --steps timed steps (see one_step / finish_rollout)
   primary = args.recipe or cfg["recipe"]
   # the regimes of one run: the primary recipe gives `value`; the others are timed in the same process after it and
-  # reported under `regimes` (N = 1 only unless --regimes says otherwise)
+  # reported under `regimes` (N = 1 and --full only unless --regimes says otherwise)
   if args.regimes:
     names = [primary] + [r for r in args.regimes.split(",") if r and r != primary]
-  elif args.recipe is None and not args.pmc_run and world == 1:
+  elif args.recipe is None and not args.pmc_run and world == 1 and args.full:
     names = [primary] + [r for r in cfg.get("also", ()) if r != primary]
   else:
     names = [primary]
@@ -630,6 +669,7 @@ def main():
         Sff = ops.Q_reduce_forward(pm, B, base | F.MM_STAGE_FINALIZE)
       else:
         f1, Sff, cross = ops.moment_match(pm, state["mu"], state["S"], True, True, 0.0, args.force_generic, extra)
+      state["out"] = (f1, Sff, cross)
       if cfg["closed"]:
         state["mu"], state["S"] = ops.euler_update(state["mu"], state["S"], f1, Sff, cross, 1.0)
         traj_mu[h].copy_(state["mu"]); traj_S[h].copy_(state["S"])
@@ -669,8 +709,15 @@ def main():
       elapsed = float(tmax.item())
     pm.check_status(B)
     rollouts_timed, collectives_timed = state["rollouts"], state["collectives"]
+    # what the caller of the timed path holds after the last timed step: its moments, the updated state (closed rollouts)
+    # and the gathered cost matrix of the last (possibly partial) rollout
+    dumped = None
+    if args.dump_outputs and is_primary and rank == 0:
+      f1_l, Sff_l, cross_l = state["out"]
+      dumped = host_arrays(f1=f1_l, Sff=Sff_l, cross=cross_l, mu=state["mu"] if cfg["closed"] else None,
+                           Sigma=state["S"] if cfg["closed"] else None, cost=state["cost"])
     # per-stage times: a separate, untimed pass of staged steps (<= one rollout of them)
-    if not args.pmc_run:
+    if args.full and not args.pmc_run:
       ev.clear()
       state["h"] = 0
       for _ in range(min(steps, H)):
@@ -680,7 +727,7 @@ def main():
     collapsed = [0, 0, 0]
     groups = [0, 0, 0]
     routed = 0
-    if f32_mode and not args.pmc_run:
+    if f32_mode and args.full and not args.pmc_run:
       state["h"] = 0
       for _ in range(H):
         one_step(False)
@@ -695,6 +742,14 @@ def main():
                          f"expected {(B_total, H)}")
       if not torch.isfinite(state["cost"]).all():
         raise SystemExit("non-finite per-step costs")
+    step_ms = 1e3 * elapsed / steps
+    res = {"recipe": recipe_name, "recipe_text": rec["text"],
+           "value": round(B_total * steps / elapsed, 2), "ms_per_step": round(step_ms, 4), "steps": steps,
+           "rollouts_timed": rollouts_timed, "collectives_timed": collectives_timed if world > 1 else 0}
+    if dumped is not None:
+      res["_dump"] = dumped
+    if not args.full:
+      return res
 
     # ---- per-segment device time (HIP events on the launch stream; the staged pass above / the counter passes' steps) -------------
     seg = {k: float(np.mean([e[i].elapsed_time(e[i + 1]) for e in ev])) for i, k in enumerate(("q_stage", "diag", "offdiag", "tail"))}
@@ -721,7 +776,6 @@ def main():
     roofs = {"offdiag": reduce_roofline("offdiag") if Po else None, "diag": reduce_roofline("diag")}
     dominant = "offdiag" if (Po and seg["offdiag"] >= seg["diag"]) else "diag"
     # step-level cross-check of the same model: all pairs' 8d flops over the whole step, against the f32/f64 peak
-    step_ms = 1e3 * elapsed / steps
     step_flops = (e_off + e_diag) * (2 * d + 12) + e_diag * 2
     step_tf = step_flops / (step_ms * 1e-3) / 1e12
     step_peak = PEAK_TFLOPS["f32" if f32_mode else "f64"]
@@ -739,17 +793,14 @@ def main():
         if got and "hbm_bytes" in got[1]["counters"]:
           qroof["per_kernel"][got[0]] = {"hbm_bytes": got[1]["counters"]["hbm_bytes"] * pscale}
 
-    res = {
-        "recipe": recipe_name, "recipe_text": rec["text"],
-        "value": round(B_total * steps / elapsed, 2), "ms_per_step": round(step_ms, 4), "steps": steps,
-        "rollouts_timed": rollouts_timed, "collectives_timed": collectives_timed if world > 1 else 0,
+    res.update({
         "segments_ms": {k: round(v, 4) for k, v in seg.items()},
         "offdiag_items_one_rollout": {"collapsed": collapsed[0], "wholly_inside": collapsed[2], "total": collapsed[1],
                                       "routed_to_f64": routed, "partly_collapsed": groups[0],
                                       "collapsed_row_groups": groups[1], "row_groups": groups[2]},
         "roofline": roofs[dominant], "roofline_other": roofs["diag" if dominant == "offdiag" else "offdiag"],
         "roofline_step": roof_step, "roofline_q_stage": qroof,
-    }
+    })
 
     # ---- parity of THIS regime (rank 0, N == 1): GPU step vs the CPU restatements on the same element ------------
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pmc_run:
@@ -822,22 +873,21 @@ def main():
                  "value_is": f"the `{primary}` regime; every other entry of `regimes` was timed in the same process with the same --steps/--warmup",
                  "rollouts_timed": pr["rollouts_timed"], "collectives_timed": pr["collectives_timed"],
                  "steps_requested": args.steps,
-                 "diag_pairs": "f64", "offdiag_pairs": cfg["dtype"],
-                 "offdiag_items_one_rollout": dict(pr["offdiag_items_one_rollout"],
-                                                   meaning="(b, off-diagonal pair, step) items of one rollout; collapsed: the degree-3..6 polynomial "
-                                                           "p6 of the remainder from weight moments for EVERY row (Cauchy-Schwarz bound <= 1/2), tiles with max|b| <= 1/4 skipped after a "
-                                                           "screening MFMA; partly_collapsed: the same for some 64-row groups of the item (collapsed_row_groups of row_groups over "
-                                                           "all items), the other groups reduced densely; wholly_inside: the Cauchy-Schwarz bound alone puts every |b| <= 1/4, "
-                                                           "no tile work (csrc/mm_moments.hip, mm_moments6.hip, mm_mfma.hip); routed_to_f64: items whose f32 "
-                                                           "rounding-error estimate exceeded MM_ROUTE_TOL = 3e-4 of the covariance block's scale and "
-                                                           "were re-reduced in f64 inside the timed off-diagonal segment (csrc/mm_route.hip)")},
-      "segments_ms": pr["segments_ms"],
-      "roofline": pr["roofline"],
-      "roofline_other": pr["roofline_other"],
-      "roofline_step": pr["roofline_step"],
-      "roofline_q_stage": pr["roofline_q_stage"],
+                 "diag_pairs": "f64", "offdiag_pairs": cfg["dtype"]},
   }
+  if args.full:
+    out["config"]["offdiag_items_one_rollout"] = dict(
+        pr["offdiag_items_one_rollout"],
+        meaning="(b, off-diagonal pair, step) items of one rollout; collapsed: the degree-3..6 polynomial "
+                "p6 of the remainder from weight moments for EVERY row (Cauchy-Schwarz bound <= 1/2), tiles with max|b| <= 1/4 skipped after a "
+                "screening MFMA; partly_collapsed: the same for some 64-row groups of the item (collapsed_row_groups of row_groups over "
+                "all items), the other groups reduced densely; wholly_inside: the Cauchy-Schwarz bound alone puts every |b| <= 1/4, "
+                "no tile work (csrc/mm_moments.hip, mm_moments6.hip, mm_mfma.hip); routed_to_f64: items whose f32 "
+                "rounding-error estimate exceeded MM_ROUTE_TOL = 3e-4 of the covariance block's scale and "
+                "were re-reduced in f64 inside the timed off-diagonal segment (csrc/mm_route.hip)")
+    out.update({k: pr[k] for k in ("segments_ms", "roofline", "roofline_other", "roofline_step", "roofline_q_stage")})
   ctx = pr.pop("_ctx", None)
+  dump = pr.pop("_dump", None)
 
   # ---- CPU baseline + parity vs the literal oracle (rank 0, N == 1 only, primary regime) --------------------------
   if ctx is not None:
@@ -928,6 +978,8 @@ def main():
     r.pop("_fused", None); r.pop("_ctx", None)
   if len(results) > 1 or args.regimes:
     out["regimes"] = {n: {k: v for k, v in r.items() if k not in ("roofline_q_stage",)} for n, r in results.items()}
+  if dump is not None:
+    write_outputs(args.dump_outputs, dump)
   if rank == 0:
     emit(out)
   if world > 1:
@@ -993,13 +1045,17 @@ def composed_bench(args, rank, world, dev, dist):
   if not (torch.isfinite(cost).all() and torch.isfinite(S_H).all()):
     raise SystemExit("non-finite composed rollout")
   dev_ms = e0.elapsed_time(e1) / steps
-  # the same rollouts enqueued eagerly (one mm_rollout_composed call each), for the record
-  torch.cuda.synchronize()
-  te = time.perf_counter()
-  for _ in range(steps // H):
-    eager_roll(mx, Sxx, H)
-  torch.cuda.synchronize()
-  eager_ms = 1e3 * (time.perf_counter() - te) / steps
+  # the graph's static outputs of the last timed rollout (valid until its next replay)
+  dump = host_arrays(mu_H=m_H, Sigma_H=S_H, cost=cost) if args.dump_outputs and rank == 0 else None
+  eager_ms = None
+  if args.full:
+    # the same rollouts enqueued eagerly (one mm_rollout_composed call each), for the record
+    torch.cuda.synchronize()
+    te = time.perf_counter()
+    for _ in range(steps // H):
+      eager_roll(mx, Sxx, H)
+    torch.cuda.synchronize()
+    eager_ms = round(1e3 * (time.perf_counter() - te) / steps, 4)
   model_bytes = float(drift.packed(dtype, True, dev).nbytes + pol.packed(dtype, False, dev).nbytes)
   out = {"metric": "moment_matched_rollout_step_elements_per_sec", "value": round(B * world * steps / elapsed, 2),
          "unit": "rollout step-elements/s (B*H per rollout second)", "n_gpus": world, "steps": steps, "warmup": args.warmup,
@@ -1008,7 +1064,7 @@ def composed_bench(args, rank, world, dev, dist):
          "config": {"workload": c["label"], "N": c["M"], "N_policy": c["Mpol"], "d": 6, "D": 4, "H": H, "B_per_gpu": B, "B_total": B * world,
                     "parallelism": f"dp{world} over B (weak)", "rollouts_timed": steps // H,
                     "collectives_timed": steps // H if world > 1 else 0, "steps_requested": args.steps,
-                    "launch": "HIP graph replay of one mm_rollout_composed call per rollout", "eager_ms_per_step": round(eager_ms, 4)},
+                    "launch": "HIP graph replay of one mm_rollout_composed call per rollout", "eager_ms_per_step": eager_ms},
          "roofline": {"bound": "hbm", "kernel": "mm_rollout_composed: chain of ~16 dependent launches per step (2 GP moment matches + 4 composition kernels + cost)",
                       "achieved": round(model_bytes / (dev_ms * 1e-3) / 1e9, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                       "frac": round(model_bytes / (dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 6), "traffic": None, "kernel_ms": round(dev_ms, 4),
@@ -1016,7 +1072,7 @@ def composed_bench(args, rank, world, dev, dist):
                       "note": "B = 1: every kernel runs for a few microseconds on a fraction of one XCD; the step is bound by the "
                               "dependency chain of its launches (MI355X_MICROARCH.md 'boundary': ~1.5-1.9 us each), not by a "
                               "bandwidth or issue ceiling.  `achieved` = packed model bytes touched once per step / step time"}}
-  if rank == 0 and world == 1:
+  if args.full and rank == 0 and world == 1:
     # what the only real caller of this rollout does with it (examples/cartpole_swingup/train_utils.py:91-105): the
     # gradient of the loss w.r.t. the policy's parameters -- taped native rollout + reverse sweep
     # (mm_rollout_composed_backward), forward + backward replayed from one HIP graph; untimed by the metric, reported beside it
@@ -1047,7 +1103,7 @@ def composed_bench(args, rank, world, dev, dist):
         "grad_norm": float(torch.sqrt(sum((g_ * g_).sum() for g_ in gl._grads)))}
     for p_ in prm:
       p_.requires_grad_(False)
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     from oracle import mm_compose_oracle as co
     from oracle import mm_oracle as mo
     po_d = mo.SVGPParams(Z=np.broadcast_to(drift_s.Z, (4, c["M"], 6)).copy(), lengthscales=drift_s.lengthscales, variance=drift_s.variance,
@@ -1072,6 +1128,8 @@ def composed_bench(args, rank, world, dev, dist):
                                      "loss": float(np.abs(cost[:1].sum(1).cpu().numpy() - loss_o).max())},
                      "max_abs": {"mu_H": float(np.abs(traj_o[-1][0]).max()), "Sigma_H": float(np.abs(traj_o[-1][1]).max()),
                                  "loss": float(np.abs(loss_o).max())}}
+  if dump is not None:
+    write_outputs(args.dump_outputs, dump)
   if rank == 0:
     emit(out)
   if world > 1:
@@ -1162,35 +1220,38 @@ def grad_bench(args, rank, world, dev, dist):
   f1, Sff, gmu, gS = last["out"]
   if not all(bool(torch.isfinite(t).all()) for t in (f1, Sff, gmu, gS)):
     raise SystemExit("non-finite outputs")
-  # one-call backward == staged backward (same kernels, same order)
-  mu, S = draws_mu[(steps - 1) % ndraw], draws_S[(steps - 1) % ndraw]
-  gmu1, gS1 = ops.moment_match_backward(pm, mu, S, g1, g2, g3, True, True)
-  same = float((gmu1 - gmu).abs().amax()) <= 1e-12 * float(gmu1.abs().amax()) and float((gS1 - gS).abs().amax()) <= 1e-12 * float(gS1.abs().amax())
-  # the product's default for a differentiating caller: value AND sums from one pair of sweeps, then the chain rule alone
-  def one_sweep_step(k, ev=None):
-    mu_k, S_k = draws_mu[k % ndraw], draws_S[k % ndraw]
-    if ev: ev[0].record()
-    f1_, Sff_, cr_, sums_, g_ = ops.moment_match_with_sums(pm, mu_k, S_k)
-    if ev: ev[1].record()
-    gm_, gS_ = ops.moment_match_backward(pm, mu_k, S_k, g1, g2, g3, True, True, forward_generation=g_, sums=sums_)
-    if ev: ev[2].record()
-    return Sff_, gm_, gS_
-  one_sweep_step(0)
-  evs1 = []
-  for k in range(steps):
-    ev = [Ev() for _ in range(3)]
-    Sff1, gm1, gS1s = one_sweep_step(k, ev)
-    evs1.append(ev)
-  torch.cuda.synchronize()
-  os_fwd = sum(e[0].elapsed_time(e[1]) for e in evs1) / steps
-  os_bwd = sum(e[1].elapsed_time(e[2]) for e in evs1) / steps
-  one_sweep = {"value_and_sums_ms": round(os_fwd, 4), "chain_rule_ms": round(os_bwd, 4), "total_ms": round(os_fwd + os_bwd, 4),
-               "over_forward": round((os_fwd + os_bwd) / seg["forward"], 2),
-               "Sff_max_diff_over_scale_vs_forward": float((Sff1 - Sff).abs().amax() / Sff.abs().amax()),
-               "gradient_equals_two_pass": bool(torch.equal(gm1, gmu) and torch.equal(gS1s, gS)),
-               "what": "mm_moment_match_with_sums + mm_moment_match_backward(MM_SUMS_CURRENT): the backward's sweeps do not depend on the "
-                       "incoming gradient and contain the forward's sums, so value + gradient need ONE diagonal and ONE off-diagonal "
-                       "sweep (autodiff.MomentMatchFunction's default); the timed region above is the two-pass form, stage by stage"}
+  dump = host_arrays(f1=f1, Sff=Sff, grad_mu=gmu, grad_Sigma=gS) if args.dump_outputs and rank == 0 else None
+  same, one_sweep = None, None
+  if args.full:
+    # one-call backward == staged backward (same kernels, same order)
+    mu, S = draws_mu[(steps - 1) % ndraw], draws_S[(steps - 1) % ndraw]
+    gmu1, gS1 = ops.moment_match_backward(pm, mu, S, g1, g2, g3, True, True)
+    same = float((gmu1 - gmu).abs().amax()) <= 1e-12 * float(gmu1.abs().amax()) and float((gS1 - gS).abs().amax()) <= 1e-12 * float(gS1.abs().amax())
+    # the product's default for a differentiating caller: value AND sums from one pair of sweeps, then the chain rule alone
+    def one_sweep_step(k, ev=None):
+      mu_k, S_k = draws_mu[k % ndraw], draws_S[k % ndraw]
+      if ev: ev[0].record()
+      f1_, Sff_, cr_, sums_, g_ = ops.moment_match_with_sums(pm, mu_k, S_k)
+      if ev: ev[1].record()
+      gm_, gS_ = ops.moment_match_backward(pm, mu_k, S_k, g1, g2, g3, True, True, forward_generation=g_, sums=sums_)
+      if ev: ev[2].record()
+      return Sff_, gm_, gS_
+    one_sweep_step(0)
+    evs1 = []
+    for k in range(steps):
+      ev = [Ev() for _ in range(3)]
+      Sff1, gm1, gS1s = one_sweep_step(k, ev)
+      evs1.append(ev)
+    torch.cuda.synchronize()
+    os_fwd = sum(e[0].elapsed_time(e[1]) for e in evs1) / steps
+    os_bwd = sum(e[1].elapsed_time(e[2]) for e in evs1) / steps
+    one_sweep = {"value_and_sums_ms": round(os_fwd, 4), "chain_rule_ms": round(os_bwd, 4), "total_ms": round(os_fwd + os_bwd, 4),
+                 "over_forward": round((os_fwd + os_bwd) / seg["forward"], 2),
+                 "Sff_max_diff_over_scale_vs_forward": float((Sff1 - Sff).abs().amax() / Sff.abs().amax()),
+                 "gradient_equals_two_pass": bool(torch.equal(gm1, gmu) and torch.equal(gS1s, gS)),
+                 "what": "mm_moment_match_with_sums + mm_moment_match_backward(MM_SUMS_CURRENT): the backward's sweeps do not depend on the "
+                         "incoming gradient and contain the forward's sums, so value + gradient need ONE diagonal and ONE off-diagonal "
+                         "sweep (autodiff.MomentMatchFunction's default); the timed region above is the two-pass form, stage by stage"}
   Po, Mp = L * (L - 1) // 2, -(-M // 128) * 128
   nmono = 1 + d + d * (d + 1) // 2
   e_off = float(B) * Po * M * M
@@ -1227,9 +1288,9 @@ def grad_bench(args, rank, world, dev, dist):
                     "one_sweep_value_and_gradient": one_sweep},
          "segments_ms": {k: round(v, 4) for k, v in seg.items()},
          "roofline": r_off, "roofline_other": r_diag}
-  if not same:
+  if same is False:
     raise SystemExit("staged backward differs from the one-call backward")
-  if rank == 0 and not args.no_cpu_baseline and world == 1:
+  if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
     # the reference's way: autograd through the materialised [P, M, M] evaluation (autodiff.moment_match_torch, the torch
     # transliteration of models.py:200-299) on the host cores, float64, ONE batch element of the same workload
     from gpflowpilco_amd import autodiff
@@ -1259,6 +1320,8 @@ def grad_bench(args, rank, world, dev, dist):
                      "max_err_over_scale_vs_f64_pack": {"g_mu": rel(ga[0], gb[0]), "g_Sigma": rel(ga[1], gb[1])},
                      "f64_pack_vs_cpu_autograd": {"g_mu": rel(gb[0], gc[0]), "g_Sigma": rel(gb[1], gc[1])},
                      "items_routed_to_f64_in_this_backward": pm.routed()[1]}
+  if dump is not None:
+    write_outputs(args.dump_outputs, dump)
   if rank == 0:
     emit(out)
   if world > 1:
@@ -1333,6 +1396,7 @@ def pathwise_bench(args, rank, world, dev, dist):
     elapsed = float(tmax.item())
   if not torch.isfinite(cost).all():
     raise SystemExit("non-finite sample costs")
+  dump = host_arrays(cost=cost) if args.dump_outputs and rank == 0 else None
   k_ms = e0.elapsed_time(e1) / steps
   bytes_per_launch = float(S) * L * (K + M) * 4
   achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9
@@ -1352,8 +1416,10 @@ def pathwise_bench(args, rank, world, dev, dist):
                       "kernel_ms": round(k_ms, 4), "bytes_per_launch": bytes_per_launch,
                       "note": "achieved = algorithmic bytes S*L*(K+M)*4 per step / step time (the step time includes the small cost kernels "
                               "between launches)"}}
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     out.update(pathwise_extras(args, dev, c, paths, x0, dtype))
+  if dump is not None:
+    write_outputs(args.dump_outputs, dump)
   if rank == 0:
     emit(out)
   if world > 1:

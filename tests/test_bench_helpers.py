@@ -190,3 +190,39 @@ def test_every_committed_bench_result_renders_to_a_short_line():
     assert len(line) < 6000 and "\n" not in line and got["metric"] == res["metric"] and "roofline" in got, p
     seen += 1
   assert seen >= 5
+
+
+def test_dump_outputs_keep_their_dtype_and_a_fixed_sample_under_the_limit(tmp_path):
+  """bench.write_outputs (--dump-outputs): float32 / float64 arrays are written as computed; past the byte limit every array
+  becomes a seeded sample of its entries, the same on every run, and the files stay within the limit."""
+  import numpy as np
+  bench = _load("bench_dump_t", os.path.join(ROOT, "bench.py"))
+  rng = np.random.default_rng(1)
+  small = {"f1": rng.standard_normal((4, 3)).astype(np.float32), "Sff": rng.standard_normal((2, 3, 3)), "n": np.arange(5)}
+  bench.write_outputs(str(tmp_path / "small"), small)
+  for k, v in small.items():
+    got = np.load(tmp_path / "small" / f"{k}.npy")
+    assert got.dtype == (v.dtype if k != "n" else np.float64) and got.shape == v.shape and np.array_equal(got, v)
+  big = {"a": rng.standard_normal(40000), "b": rng.standard_normal((100, 200)).astype(np.float32)}
+  limit = 1 << 16
+  for run in ("one", "two"):
+    bench.write_outputs(str(tmp_path / run), big, limit=limit)
+  sizes = [os.path.getsize(tmp_path / "one" / f"{k}.npy") for k in big]
+  assert sum(sizes) <= limit
+  for k, v in big.items():
+    one, two = np.load(tmp_path / "one" / f"{k}.npy"), np.load(tmp_path / "two" / f"{k}.npy")
+    assert one.dtype == v.dtype and 0 < one.size < v.size and np.array_equal(one, two)
+    assert np.isin(one, v.reshape(-1)).all()
+
+
+def test_a_plain_run_line_carries_the_contract_keys(capsys, tmp_path):
+  """Without --full the result has no roofline / parity / cpu_baseline blocks; its line still carries the contract keys."""
+  bench = _load("bench_plain_t", os.path.join(ROOT, "bench.py"))
+  res = {k: v for k, v in _canned_result().items()
+         if k not in ("segments_ms", "roofline", "roofline_other", "roofline_step", "roofline_q_stage", "cpu_baseline",
+                      "cpu_baseline_matched", "parity", "next_rows", "regimes")}
+  bench.emit(res, detail_path=str(tmp_path / "detail.json"))
+  got = json.loads(capsys.readouterr().out)
+  for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+    assert got[k] == res[k], k
+  assert got["roofline"] is None and "parity" not in got and "cpu_baseline" not in got

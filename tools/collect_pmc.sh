@@ -29,7 +29,7 @@ for g in "${groups[@]}"; do
   # shellcheck disable=SC2086
   # only this library's kernels are counted (the model set-up launches thousands of rocBLAS / rocSOLVER kernels:
   # counting those makes a pass take many minutes)
-  rocprofv3 --pmc ${g} --kernel-include-regex "^(void )?(k_|mm_)" -d "${out}/pass${i}" -o pmc --output-format csv -- python3 "${root}/bench.py" "$@" --steps "${PMC_STEPS:-4}" --warmup 1 --no-cpu-baseline --pmc-run \
+  rocprofv3 --pmc ${g} --kernel-include-regex "^(void )?(k_|mm_)" -d "${out}/pass${i}" -o pmc --output-format csv -- python3 "${root}/bench.py" "$@" --full --steps "${PMC_STEPS:-4}" --warmup 1 --no-cpu-baseline --pmc-run \
     > "${out}/pass${i}.log" 2>&1 || { echo "pass ${i} failed (see ${out}/pass${i}.log)"; tail -5 "${out}/pass${i}.log"; exit 1; }
   echo "pass ${i} done: ${g}"
 done

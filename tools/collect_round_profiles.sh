@@ -3,7 +3,7 @@
 #
 #   ROUND=r05 bash tools/collect_round_profiles.sh          # writes gpurun_out/<round>/final/ and gpurun_out/<round>/<round>_pmc_*.json
 #
-#   1. the driver's bench command verbatim (line + bench_detail.json);
+#   1. the headline bench command with --full (line + bench_detail.json);
 #   2. rocprofv3 --kernel-trace --stats of the same workload, one recipe at a time (per-kernel durations);
 #   3. hardware counters (tools/collect_pmc.sh: --pmc only, one pass per group) for every config, copied into profiles/ ON THE BOX so
 #      that step 4's bench lines carry roofline.traffic / issue_frac from counters of this very tree (src_hash);
@@ -14,10 +14,10 @@ set -u
 round="${ROUND:-r05}"
 R="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"; O="$R/gpurun_out/$round/final"; mkdir -p "$O"
 cd "$R"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_c3_driver_line.json" 2> "$O/bench_c3_driver.err" && cp bench_detail.json "$O/bench_c3_driver.json"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_c3_driver_line.json" 2> "$O/bench_c3_driver.err" && cp bench_detail.json "$O/bench_c3_driver.json"
 export TMPDIR=/tmp
 for rec in baseline pilco worst; do
-  (cd /tmp && rocprofv3 --kernel-trace --stats -d "$O/kt_$rec" -o t --output-format csv -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --recipe $rec --no-cpu-baseline > "$O/bench_c3_${rec}_under_rocprof_line.json" 2> "$O/kt_$rec.err")
+  (cd /tmp && rocprofv3 --kernel-trace --stats -d "$O/kt_$rec" -o t --output-format csv -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --full --recipe $rec --no-cpu-baseline > "$O/bench_c3_${rec}_under_rocprof_line.json" 2> "$O/kt_$rec.err")
   cp "$R/bench_detail.json" "$O/bench_c3_${rec}_under_rocprof.json"; cp "$O/kt_$rec/t_kernel_stats.csv" "$O/bench_c3_${rec}_kernel_stats.csv"; rm -rf "$O/kt_$rec"
 done
 for t in "c3_baseline --config c3 --recipe baseline" "c3_pilco --config c3 --recipe pilco" "c3_worst --config c3 --recipe worst" "c2_pilco --config c2" \
@@ -26,8 +26,8 @@ for t in "c3_baseline --config c3 --recipe baseline" "c3_pilco --config c3 --rec
   ROUND=$round bash tools/collect_pmc.sh "$tag" "$@" > "$O/pmc_$tag.log" 2>&1; tail -1 "$O/pmc_$tag.log"
 done
 cp "$R/gpurun_out/$round/${round}"_pmc_*.json "$R/profiles/"
-run() { name=$1; shift; python3 bench.py "$@" > "$O/bench_${name}_line.json" 2> "$O/bench_${name}.err"; cp bench_detail.json "$O/bench_${name}.json"; }
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_c3_driver_line.json" 2> "$O/bench_c3_driver.err" && cp bench_detail.json "$O/bench_c3_driver.json"
+run() { name=$1; shift; python3 bench.py --full "$@" > "$O/bench_${name}_line.json" 2> "$O/bench_${name}.err"; cp bench_detail.json "$O/bench_${name}.json"; }
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_c3_driver_line.json" 2> "$O/bench_c3_driver.err" && cp bench_detail.json "$O/bench_c3_driver.json"
 run c1 --config c1; run c1_closed --config c1_closed; run c2 --config c2; run c3_grad --config c3_grad; run c5 --config c5
 run c5_shard --config c5 --batch 8192; run c4_shard --config c4 --batch 32 --steps 10 --warmup 2
 run c3_rehearse_gloo2 --gpus 2 --rehearse-gloo --steps 10 --warmup 2
