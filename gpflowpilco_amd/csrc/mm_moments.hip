@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_wmom_perm(const unsigned int* __restrict__ amaxc, const double* __restrict__ zmax2, int L, int B,
                                                     int Po, int* __restrict__ gperm) {
-  // classes by the item's bound X^2 (mm_common.h): 0: collapsed, X > 1/16 (degrees 3..6); 1: 1/32 < X <= 1/16 (3..5); 2: X <= 1/32
+  // classes by the item's bound X^2 (mm_common.h): 0: collapsed, X > 1/16 (degrees 3..6); 1: 1/40 < X <= 1/16 (3..5); 2: X <= 1/40
   // (3, 4); 3: not collapsed.  Classes 0..2 from the front in this order (stable inside a class), class 3 from the back.
   const int a = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int R = (L - 1) * B;
@@ -475,7 +475,11 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
     // (mm_common.h: no forward reduce follows on this workspace) -- poison instead of compute: all-ones doubles are NaN
     if (mm_moment56_cols(d) <= 0 || wl.Po <= 0) return 0;
     const hipError_t em = hipMemsetAsync(ws + wl.s56, 0xFF, (size_t)B * wl.Po * sizeof(double), stream);
-    return em == hipSuccess ? 0 : (int)em;
+    if (em != hipSuccess) return (int)em;
+    // ... and no collapsed item leaves tiles out: estS is zero, so that mm_route_estimates reports the estimate the backward's
+    // route decision read (which adds no estS), not what an earlier forward on this workspace left there
+    const hipError_t es = hipMemsetAsync(ws + wl.estS, 0, (size_t)B * wl.Po * sizeof(float), stream);
+    return es == hipSuccess ? 0 : (int)es;
   }
   // orders 5 and 6 of the collapsed items (f32 moments on the bf16 matrix pipe: mm_moments6.hip) -> s56, estS
   return mm_launch_moments56(packed, ml, ws, wl, B, L, d, some ? 1 : 0, stream);
