@@ -20,8 +20,9 @@
 //   expm1     : wave-uniform Taylor tiers by the tile's range (degree 6/7/8/9/10/15 for an f32 model,
 //               7/8/9/10/12/15 for an f64 model), Horner steps vertical over 8 entries; beyond the last
 //               tier k ln2 + r reduction + v_ldexp_f64 (relative error ~2e-16 for every argument);
-//   pipeline  : operands of batch element b + 1 prefetched into a second register set; per-thread
-//               partials of 16 batch elements staged in LDS and reduced together;
+//   pipeline  : diagonal pairs: the tile's operands of batch element b + 1 land in a two-slot LDS ring
+//               (global_load_lds_dwordx4) while b is reduced; off-diagonal pairs: prefetched into a second
+//               register set; per-thread partials of 16 batch elements staged in LDS and reduced together;
 //   grid      : 1-D, remapped so that an XCD owns a contiguous (pair, chunk, tile) range;
 //   output    : per (b, pair, tile) partial sums -> slab (deterministic, no atomics).
 #include <hip/hip_runtime.h>
@@ -40,6 +41,8 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 #define MM_F64_TARGET_WGS 8192
 #endif
 #define MM_F64_NB 16      // batch elements whose partial sums are staged in LDS between workgroup reductions
+// rows of 64 doubles in one slot of the diagonal pairs' operand ring: 4 KS4 MFMA B-operand rows, row weights, column weights
+#define MM_F64_RING_ROWS(KS4_) (4 * (KS4_) + 2)
 // diagonal pairs with the rank-one terms factored into the weights need ~100 fewer VGPRs: three waves per SIMD
 // up to this many K = 4 steps (d <= 4 MM_F64_3WAVE_KS4)
 #ifndef MM_F64_3WAVE_KS4
@@ -125,7 +128,8 @@ __device__ __forceinline__ void mmq_f64_body(const double* __restrict__ Zc, int 
                                              const double* __restrict__ rowA,
                                              const double* __restrict__ colB,
                                              double* __restrict__ partB,
-                                             double* __restrict__ partC, int orig, double (*stage)[256], double (*part16)[16]) {
+                                             double* __restrict__ partC, int orig, double (*stage)[256], double (*part16)[16],
+                                             double* __restrict__ ring) {
   // 1-D grid, XCD-aware: workgroups b and b + 8 share an XCD (round-robin dispatch), so the remap
   // hands every XCD one contiguous range of work items ordered (pair, batch chunk, tile): the
   // per-batch-element operands of one latent stay in ONE XCD's L2.  Bijective for any nwork.
@@ -358,6 +362,69 @@ __device__ __forceinline__ void mmq_f64_body(const double* __restrict__ Zc, int 
     if ((b - b0) % MM_F64_NB == MM_F64_NB - 1 || b == b1 - 1) flush(b - (b - b0) % MM_F64_NB, (b - b0) % MM_F64_NB + 1);
   };
 
+  if constexpr (DIAG) {
+    // Diagonal pairs: the per-b operands of the whole 64 x 64 tile go through a two-slot LDS ring, MM_F64_RING_ROWS(KS4)
+    // rows of 64 doubles per slot: the 4 KS4 MFMA B-operand rows (row k holds colB row min(k, d)), the row weights, the
+    // column weights.  global_load_lds_dwordx4 fills two rows per instruction (lanes 0-31 / 32-63), the instructions of
+    // a slot dealt round-robin to the 4 waves; batch element b + 1 lands while b is reduced (one barrier per b), and each
+    // wave reads its 28 operand doubles back as ds_read2_b64 -- no second register set, no per-lane scattered loads.
+    constexpr int NR = MM_F64_RING_ROWS(KS4), NI = NR / 2, NIW = (NI + 3) / 4;
+    const double* src[NIW];
+    size_t sstr[NIW];
+#pragma unroll
+    for (int n = 0; n < NIW; ++n) {
+      const int i = wv + 4 * n;
+      const int row = 2 * i + (lane >> 5), col = (lane & 31) * 2;
+      if (row < 4 * KS4) {
+        src[n] = colB + (((size_t)b0 * np + lp) * (d + 1) + (row < d ? row : d)) * Mp + jt * MM_F64_TILE + col;
+        sstr[n] = st_cb;
+      } else if (row == 4 * KS4) {
+        src[n] = w + ((size_t)b0 * L + a) * Mp + it * MM_F64_TILE + col;
+        sstr[n] = st_w;
+      } else {
+        src[n] = q + ((size_t)b0 * L + a2) * Mp + jt * MM_F64_TILE + col;
+        sstr[n] = st_w;
+      }
+    }
+    auto fill = [&](int slot) {
+#pragma unroll
+      for (int n = 0; n < NIW; ++n)
+        if (wv + 4 * n < NI)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[n],
+                                           (__attribute__((address_space(3))) void*)(ring + (slot * NR + 2 * (wv + 4 * n)) * 64), 16, 0, 0);
+    };
+    const int rl = (wv >> 1) * 32 + kq, cl = (wv & 1) * 32 + l15;
+    auto read_ops = [&](MMF64Operands<KS4, DIAG>& o, int slot) {
+      const double* sl = ring + slot * NR * 64;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+        for (int s = 0; s < KS4; ++s) o.breg[ct][s] = sl[(4 * s + kq) * 64 + cl + ct * 16];
+        o.cw[ct] = sl[(4 * KS4 + 1) * 64 + cl + ct * 16];
+      }
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o.rw[rt][r] = sl[4 * KS4 * 64 + rl + rt * 16 + 4 * r];
+    };
+    MMF64Operands<KS4, DIAG> o;
+    fill(0);
+    for (int b = b0; b < b1; ++b) {
+      const int j = b - b0;
+      // slot j & 1 has landed: this wave's LDS DMA (the compiler's fence waits for lgkmcnt only), then every wave's
+      // (barrier); slot (j + 1) & 1 was read at b - 1
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      read_ops(o, j & 1);
+      if (b + 1 < b1) {
+#pragma unroll
+        for (int n = 0; n < NIW; ++n) src[n] += sstr[n];
+        fill((j + 1) & 1);
+      }
+      reduce_b(b, o);
+    }
+    return;
+  }
   // two operand sets in registers: batch element b + 1 is in flight while b is reduced
   // (the prefetch is unconditional -- past the end it re-reads the last element -- so that the
   // compiler's s_waitcnt for the current set does not have to cover a maybe-not-issued prefetch)
@@ -392,8 +459,9 @@ __global__ __launch_bounds__(256, (KS4 >= 6 ? 1 : (DIAG && KS4 <= MM_F64_3WAVE_K
                                                           double* __restrict__ partC) {
   __shared__ double stage[MM_F64_NB][256];
   __shared__ double part16[MM_F64_NB][16];
+  __shared__ double ring[DIAG ? 2 * MM_F64_RING_ROWS(KS4) * 64 : 1];
   mmq_f64_body<KS4, DIAG, WITHC, LOWP>(Zc, Kz, Cm, beta, M, L, Mp, d, P, NS, p0, B, bchunk, np, nslots, nchunk, nwork, force_worst,
-                                       w, q, rowA, colB, partB, partC, (int)blockIdx.x, stage, part16);
+                                       w, q, rowA, colB, partB, partC, (int)blockIdx.x, stage, part16, ring);
 }
 
 // Both reduces of a SMALL f64 model in one launch (cartpole sizes: every kernel of the step costs ~ 4-5 us whatever it does, so
@@ -411,14 +479,15 @@ __global__ __launch_bounds__(256, (KS4 >= 6 ? 1 : 2)) void k_qred_f64_both(const
                                                                            double* __restrict__ partC) {
   __shared__ double stage[MM_F64_NB][256];
   __shared__ double part16[MM_F64_NB][16];
+  __shared__ double ring[2 * MM_F64_RING_ROWS(KS4) * 64];
   const int orig = (int)blockIdx.x;
   if (orig < sd.nwork)
     mmq_f64_body<KS4, true, WITHC, false>(Zc, Kz, Cm, beta, M, L, Mp, d, P, NS, sd.p0, B, sd.bchunk, sd.np, sd.nslots, sd.nchunk, sd.nwork,
-                                          force_worst, sd.w, sd.q, sd.rowA, sd.colB, partB, partC, orig, stage, part16);
+                                          force_worst, sd.w, sd.q, sd.rowA, sd.colB, partB, partC, orig, stage, part16, ring);
   else
     mmq_f64_body<KS4, false, false, false>(Zc, Kz, nullptr, beta, M, L, Mp, d, P, NS, so.p0, B, so.bchunk, so.np, so.nslots, so.nchunk,
                                            so.nwork, force_worst, so.w, so.q, so.rowA, so.colB, partB, partC, orig - sd.nwork, stage,
-                                           part16);
+                                           part16, ring);
 }
 
 int mm_f64_num_slots(int Mp, int diag) {
