@@ -18,6 +18,9 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // value-and-gradient call: their sums come from the backward's sweeps): the degree-5/6 moment chain (1.4 ms at C3) is skipped and
 // s56 is poisoned with NaN, so that a forward reduce run on such a workspace by mistake fails loudly instead of reading stale sums
 #define MM_ISTAGE_NO_M56 (1 << 22)
+// forward off-diagonal f32 sweep: take k_qred_f32_mfma (one grid slot per (b, pair)) even where the persistent work-list sweep
+// k_qred_f32_mfma_persist applies (mm_mfma.hip) -- A/B tests and measurements of the two on one build; the slabs are bit-identical
+#define MM_ISTAGE_OLD_OFFDIAG (1 << 23)
 
 static inline int mm_num_pairs(int L, int flags) {
   return (flags & MM_FULL_OUTPUT_COV) ? L * (L + 1) / 2 : L;
@@ -262,6 +265,11 @@ static inline int mm_route_ncc(int NS, int npanel) { int n = NS / npanel; return
 #define MM_GEN_COLS 256
 // f32 MFMA kernel: row panel per workgroup (4 waves x 64 rows).
 #define MM_PANEL_ROWS 256
+// 64-row wave groups of the f32 sweep's row panels (the last panel's groups beyond Mp included: their slots hold zeros)
+__host__ __device__ inline int mm_mfma_groups(int Mp) { return (Mp + MM_PANEL_ROWS - 1) / MM_PANEL_ROWS * (MM_PANEL_ROWS / 64); }
+// MMWorkspaceLayout::plist: the i32 header [0] queue counter, [1..3] unused, [4 + 2 a'] / [5 + 2 a'] the front / back counts of
+// column latent a''s bucket; the list itself from this offset
+__host__ __device__ inline int mm_f32p_list_off(int L) { return 4 + 2 * L; }
 // f64 MFMA kernel: 64 x 64 tiles
 #define MM_F64_TILE 64
 
@@ -321,6 +329,9 @@ struct MMWorkspaceLayout {
   size_t ilist;    // i32 [4] counts {items collapsed to degree 6, to degree 5, to degree 4, 0} + [B Po] item indices: the degree-6 and
                    //              degree-5 items from the front (in that order), the degree-4 items from the back (k_item_classes:
                    //              the work lists of k_spoly56 / k_spoly4, mm_moments6.hip)
+  size_t plist;    // i32 [mm_f32p_list_off(L)] header + [B Po] items (f32 mode, d <= 8): the work list of the persistent off-diagonal
+                   //              sweep, items with a tile to visit by column latent (k_offdiag_worklist, mm_mfma.hip); the header is
+                   //              zeroed before every pass
   size_t s56;      // [B][Po] f64: C1 <N_4, G^4 Q_4> + C2 <N_5, G^5 Q_5> + C3 <N_6, G^6 Q_6> of a collapsed item (0 otherwise): the degree-4..6
                    //              part of p6 from the f32 moments.  Kept apart from s12: an item the accuracy contract re-reduces in f64 (mm_route.hip) takes
                    //              those two orders from the re-reduce instead (k_finalize skips s56 where rflag is set)
@@ -384,6 +395,7 @@ static inline MMWorkspaceLayout mm_workspace_layout(int B, int L, int M, int d, 
   o.estS = off;    off = mm_align_up(off + n56 * 4, A);
   o.s56 = off;     off = mm_align_up(off + n56 * 8, A);
   o.ilist = off;   off = mm_align_up(off + n56 * 4 + 16, A);
+  o.plist = off;   off = mm_align_up(off + (n56 ? (n56 + mm_f32p_list_off(L)) * 4 : 0), A);
   o.f1s = off;     off = mm_align_up(off + (size_t)B * L * es, A);
   o.Sffs = off;    off = mm_align_up(off + (size_t)B * L * L * es, A);
   o.crs = off;     off = mm_align_up(off + (size_t)B * d * L * es, A);

@@ -22,8 +22,11 @@
 // are flushed to f64 once per column tile and written to a slab (no atomics: bitwise
 // reproducible).  The 1-D grid is remapped so that the row panels of one (b, pair) land on the
 // same XCD and share its L2.
+// Where the whole column latent fits in LDS (d <= 8, Mp <= 2048) k_qred_f32_mfma_persist (below) takes over: a work list of the
+// items with a tile to visit and one workgroup per CU with every column operand in LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <atomic>
 #include "mm_common.h"
 #include "mm_mono.h"
 #include "mm_f32_tile.h"
@@ -515,6 +518,461 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
   }
 }
 
+// The persistent sweep's per-wave code: ONE wave's 64 rows row0 .. row0 + 63 of one (b, pair) against every column, with every column
+// operand from LDS -- zlds: the column latent's [Mp/32][3 (h, m, l)][32][16] bf16 block, an exact copy of the packed model's; wlds: the
+// item's what'_j [Mp] f32.  Returns the per-lane sum (f64) and error estimate of the wave, before the cross-lane reduction.
+// It is k_qred_f32_mfma's panel body (its <1, true> instantiation) with the loads of the (m | h), (l | h) parts and what'_j pointed at
+// LDS and nothing else changed: the same tiles, tiers, per-lane accumulation and estimate, so the two sweeps' slabs agree to the bit
+// (tests/test_gpu_offdiag_persist.py).  (k_qred_f32_mfma keeps its own copy of the body: compiled through this function its register
+// allocation changed and its forced-worst-tier regime lost 1.3 %.)
+// icoll: the item has collapsed row groups (k_qred_f32_mfma's icoll_wg); grp0: the item's first entry of gflag / gmax2.
+template <int ND8>
+__device__ __forceinline__ void mm_f32_wave_rows(const char* zlds, const float* wlds,
+                                                 int row0, int b, int lp, int a2, int Mp, int d, int Po, int force_worst,
+                                                 bool icoll, size_t grp0, const unsigned int* __restrict__ amaxc,
+                                                 const unsigned char* __restrict__ gflag, const float* __restrict__ gmax2,
+                                                 const double* __restrict__ zmax2, const float* __restrict__ zt2,
+                                                 const float* __restrict__ rowO,
+                                                 double& sum_out, float& estl_out) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
+  double sum = 0.0;
+  // running estimate of the sweep's own rounding error (mm_common.h: MM_ROUTE_TOL; mm_route.hip): per lane -- one column,
+  // the lane's 32 rows -- sum over the reduced tiles of (max|b|^3 what'_j)^2, two tiles per packed instruction; the rows' sum
+  // of squares and the (1 + X + X^2) factor of rho (X = the lane's largest |b|: one v_max3 per tile pair) once per sweep
+  f32x2 est2 = {0.0f, 0.0f};
+  float rowsq = 0.0f, xall = 0.0f;
+  // icoll: the item has collapsed groups -- then the CUBIC term of every row is in the f64 moments (k_spoly), and a group that
+  // is not collapsed reduces r(b) - C0 b^3 on every tile.  coll: this wave's 64 rows are a COLLAPSED row group (mm_mono.h:
+  // k_pairvec_reg decided, with the Cauchy-Schwarz bound of the group's rows, |b_ij| <= |A_i| |zc_j|); g2: its rows' max |A_i|^2
+  const bool coll = icoll && row0 < Mp && gflag[grp0 + (row0 >> 6)] != 0;
+  const float g2 = coll ? gmax2[grp0 + (row0 >> 6)] : 0.0f;
+  // (a collapsed group with every tile inside the collapsed range: nothing to load, nothing to add)
+  const bool wave_inside = coll && mm_collapse_bound2(__float_as_uint(g2), zmax2[a2]) <= MM_INSIDE_BOUND2;
+  if (row0 < Mp && !wave_inside) {   // Mp % 128 == 0, so a wave's 64 rows are all inside or all outside
+    const float* ra = rowO + ((size_t)b * Po + lp) * (size_t)(d + 1) * Mp;   // [d+1][Mp]: A_i, what_i
+    // bound2: the bound over all collapsed groups of the item (the screening margin)
+    const float bound2 = zmax2 ? mm_collapse_bound2(amaxc[(size_t)b * Po + lp], zmax2[a2]) : 3.0e38f;
+    // a tile is skipped on the screening product alone: its error is <= 2^-9 sum_k |A_k||Z_k| <= 2^-9 sqrt(bound2)
+    const float thr_skip = MM_C6_MAX - 0.00390625f * __builtin_sqrtf(bound2) - 1e-6f;
+
+    // ---- stationary operands --------------------------------------------------------------
+    bf16x8 a1[2][ND8], a2v[2][ND8], a3[2][ND8];
+    f32x2 wrow[2][8], wc0[2][8], wc1[2][8];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      const int row = row0 + rt * 32 + l31;
+#pragma unroll
+      for (int nb = 0; nb < ND8; ++nb) {
+        unsigned int hh[8], mm[8], ll[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = nb * 8 + j;
+          const float v = ra[(size_t)(k < d ? k : d) * Mp + row];
+          mm_split3(k < d ? v : 0.0f, hh[j], mm[j], ll[j]);
+        }
+        u32x4 ph, pm, pl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          ph[j] = hh[2 * j] | (hh[2 * j + 1] << 16);
+          pm[j] = mm[2 * j] | (mm[2 * j + 1] << 16);
+          pl[j] = ll[2 * j] | (ll[2 * j + 1] << 16);
+        }
+        // MFMA1: (m,m) | (m,h)   MFMA3: (h,m) | (h,h)   MFMA2: (h,l) | (l,h)     [lane half 0 | 1]
+        // MFMA1 + MFMA3 alone are the 2-way (16-bit) product; MFMA2 adds the 2^-16 terms
+        a1[rt][nb] = __builtin_bit_cast(bf16x8, pm);
+        a2v[rt][nb] = __builtin_bit_cast(bf16x8, h ? pl : ph);
+        a3[rt][nb] = __builtin_bit_cast(bf16x8, ph);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int rr = row0 + rt * 32 + 8 * g + 4 * h;
+        const float4 v = *reinterpret_cast<const float4*>(ra + (size_t)d * Mp + rr);   // factored row weights
+        wrow[rt][2 * g + 0] = (f32x2){v.x, v.y};
+        wrow[rt][2 * g + 1] = (f32x2){v.z, v.w};
+        if constexpr (ND8 == 1) {
+#pragma unroll
+          for (int q2 = 0; q2 < 2; ++q2) {
+            wc0[rt][2 * g + q2] = wrow[rt][2 * g + q2] * MM_PK(MMRem<1>::c[0]);
+            wc1[rt][2 * g + q2] = wrow[rt][2 * g + q2] * MM_PK(MMRem<1>::c[1]);
+          }
+        }
+      }
+    }
+    {
+      f32x2 rs = {0.0f, 0.0f};
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) rs = mm_pkfma(wrow[rt][r], wrow[rt][r], rs);
+      rowsq = rs[0] + rs[1];
+    }
+
+    // ---- streaming operands: lane half 0 reads parts (m, l), half 1 reads (h, h) ------------
+    // lane byte offsets inside the latent's [Mp/32][3][32][8 ND8] bf16 block; the tile offset is wave-uniform and each
+    // half-wave reads one contiguous 512 ND8-byte part of the tile (from LDS: conflict-free ds_read_b128)
+    const unsigned int tile_bytes = 32u * 48u * ND8, part_bytes = 32u * 16u * ND8;
+    const unsigned int offA = (h ? 0u : 1u) * part_bytes + (unsigned int)l31 * (16u * ND8);
+    const unsigned int offB = (h ? 0u : 2u) * part_bytes + (unsigned int)l31 * (16u * ND8);
+    const int nct = Mp >> 5;                     // Mp % 128 == 0: nct is a multiple of 4
+
+    // zA: the (m | h) parts; zB: the (l | h) parts -- prefetched with the tile for a (b, pair) that is not collapsed, fetched on
+    // demand for a collapsed one (where few tiles get that far)
+    auto load_zA = [&](int ct, u32x4 (&zA)[ND8]) {
+#pragma unroll
+      for (int nb = 0; nb < ND8; ++nb) zA[nb] = *reinterpret_cast<const u32x4*>(zlds + (size_t)ct * tile_bytes + offA + nb * 16);
+    };
+    auto load_zB = [&](int ct, u32x4 (&zB)[ND8]) {
+#pragma unroll
+      for (int nb = 0; nb < ND8; ++nb) zB[nb] = *reinterpret_cast<const u32x4*>(zlds + (size_t)ct * tile_bytes + offB + nb * 16);
+    };
+    auto load_wc = [&](int j) { return wlds[j]; };
+
+    // b_ij in two stages.  Stage 1: the 2-way split product (h + m parts, 2^-17 relative): enough when the
+    // whole tile has |b| <= MM_TWO_WAY_MAX (1/32) -- the kernel only reduces r(b) = O(b^3), whose sensitivity to an error
+    // in b is b^2/2.  Stage 2 (wave-uniform, only for larger tiles): the (h,l) and (l,h) terms.
+    // screening product = MFMA3 alone: (h, m) | (h, h) = A_h . (Z_h + Z_m), |error| <= 2^-9 sum_k |A_k||Z_k|
+    auto mfma_tile_screen = [&](const u32x4 (&zA)[ND8], f32x16 (&acc)[2]) {
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nb = 0; nb < ND8; ++nb)
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[rt][nb], __builtin_bit_cast(bf16x8, zA[nb]), c, 0, 0, 0);
+        acc[rt] = c;
+      }
+    };
+    // + MFMA1: (m, m) | (m, h): together with the screening product the 2-way (h + m) product
+    auto mfma_tile_m = [&](const u32x4 (&zA)[ND8], f32x16 (&acc)[2]) {
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        f32x16 c = acc[rt];
+#pragma unroll
+        for (int nb = 0; nb < ND8; ++nb)
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[rt][nb], __builtin_bit_cast(bf16x8, zA[nb]), c, 0, 0, 0);
+        acc[rt] = c;
+      }
+    };
+    auto mfma_tile_l = [&](const u32x4 (&zB)[ND8], f32x16 (&acc)[2]) {
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        f32x16 c = acc[rt];
+#pragma unroll
+        for (int nb = 0; nb < ND8; ++nb)
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2v[rt][nb], __builtin_bit_cast(bf16x8, zB[nb]), c, 0, 0, 0);
+        acc[rt] = c;
+      }
+    };
+    // max |b| of a finished tile: one v_max3_f32 |a|, |b|, m per entry pair (needs -fno-honor-nans)
+    auto tile_max = [&](const f32x16 (&acc)[2]) {
+      // four independent v_max3 chains (a single chain of 16 dependent ops is the critical path of a skipped tile)
+      float m4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        m4[r & 3] = fmaxf(fmaxf(m4[r & 3], fabsf(acc[r >> 3][2 * (r & 7)])), fabsf(acc[r >> 3][2 * (r & 7) + 1]));
+      return fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+    };
+    // b_ij = acc: a pure bilinear form (rho'_i, gamma_j live in the weights); tile range -> tier.
+    // (sub0, sub1) = (c0, c1) of the first tier for a collapsed (b, pair) -- already in the moments -- else (0, 0).
+    // collm (compile time): the (b, pair) is collapsed -- the moments already carry c0 x^3 + c1 x^4 of the first tier
+    auto reduce_tile = [&](auto collm, const f32x16 (&acc)[2], float mx, float wc) {
+      constexpr int CC = decltype(collm)::value;            // 0 / 1 / 2: MMRemC
+      f32x2 xx[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) xx[r] = (f32x2){acc[r >> 3][2 * (r & 7)], acc[r >> 3][2 * (r & 7) + 1]};
+      f32x2 part2;
+      // wave-uniform tier choice (ballots, no cross-lane reduction)
+      if (CC == 0 && !__any(mx > MM_TIER1_MAX)) {
+        // (the folded coefficients cost 64 more VGPRs: only where the operand registers leave room, d <= 8)
+        if constexpr (ND8 == 1) part2 = mm_weighted_rem1(xx, wc0, wc1);
+        else part2 = mm_weighted_rem<1, 0>(xx, wrow);
+      } else if (!__any(mx > MM_C6_MAX)) {
+        // a collapsed row group has nothing left to add below 1/4: its moments carry this tier's own polynomial
+        if constexpr (CC == 1) part2 = (f32x2){0.0f, 0.0f};
+        else part2 = mm_weighted_rem<3, CC>(xx, wrow);
+      } else if (!__any(mx > 0.5f)) {
+        part2 = mm_weighted_rem<4, CC>(xx, wrow);
+      } else if (!__any(mx > 1.0f)) {
+        part2 = mm_weighted_rem<5, CC>(xx, wrow);
+      } else {
+        part2 = (f32x2){0.0f, 0.0f};
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+          for (int e2 = 0; e2 < 2; ++e2) {
+            // |b| > 1: exp2 on the transcendental unit, then the three leading terms subtracted
+            const float x = fminf(xx[r][e2], MM_EXP_CAP_F32);     // (mm_common.h: exponent caps)
+            const float xs = fminf(fmaxf(x, -1.0f), 1.0f);
+            const float big = (__builtin_amdgcn_exp2f(x * 1.44269504f) - 1.0f) - fmaf(0.5f * x, x, x);
+            float e = (fabsf(x) <= 1.0f) ? mm_rem_p5(xs) : big;
+            if constexpr (CC == 1) e -= (x * x) * x * fmaf(fmaf(fmaf(MM_C6_C3, x, MM_C6_C2), x, MM_C6_C1), x, MM_C6_C0);
+            if constexpr (CC == 2) e -= (x * x) * (x * MM_C6_C0);
+            part2[e2] = fmaf(wrow[r >> 3][r & 7][e2], e, part2[e2]);
+          }
+      }
+      sum += (double)wc * (double)(part2[0] + part2[1]);
+    };
+    // one wave tile: screening product; a collapsed (b, pair) stops here when the whole tile is inside the collapsed
+    // range; else the rest of the split product, the range tier and the weighted reduction
+    // collc (compile time): SCREENED sweep -- the screening check, and neither the column weight nor the (l | h) parts
+    // prefetched (few tiles of such an item need them, and a prefetched global load would put its latency on every tile
+    // of a sweep that is otherwise 2 MFMAs long); collm: collapsed coefficients (reduce_tile)
+    // (emx, ewc): what the error estimate takes from this tile -- its max|b| of the lane and the column weight; zeros for a
+    // tile that contributes exact moments only
+    auto process_tile = [&](auto collc, auto collm, int ct, const u32x4 (&zA)[ND8], u32x4 (&zB)[ND8], float wc, float& emx, float& ewc) __attribute__((always_inline)) {
+      constexpr bool CM = decltype(collc)::value;
+      f32x16 acc[2];
+      emx = 0.0f; ewc = 0.0f;
+      mfma_tile_screen(zA, acc);
+      if constexpr (CM) {
+        const float ms = tile_max(acc);
+        if (!__any(ms > thr_skip)) return;
+      }
+      mfma_tile_m(zA, acc);
+      const float mx = force_worst ? 2.0f : tile_max(acc);       // MM_FORCE_WORST_TIER: wave-uniform override
+      if constexpr (CM) {
+        if (!__any(mx > MM_C6_MAX)) return;                           // inside the collapsed range: all in the moments
+      }
+      if constexpr (CM) wc = load_wc(ct * 32 + l31);
+      emx = mx; ewc = wc;
+      if (__any(mx > MM_TWO_WAY_MAX)) {
+        if constexpr (CM) load_zB(ct, zB);
+        mfma_tile_l(zB, acc);
+      }
+      reduce_tile(collm, acc, mx, wc);
+    };
+
+    // two-stage register ping-pong: tile ct + 1 is in flight while tile ct is reduced.  (Issuing the MFMAs
+    // of tile ct + 1 interleaved with the v_max3 range check of tile ct -- a second accumulator set,
+    // 182 VGPRs -- was measured: 4.27 ms against 4.25 ms; three waves per SIMD already overlap the two.)
+    // A collapsed row group skips, without touching them, the column tiles whose Cauchy-Schwarz bound with ITS rows is inside the
+    // collapsed range: max_i |A_i|^2 (this wave's rows) x max_j |zc'_j|^2 (the tile's 32 points, MMModelLayout::zt2) <=
+    // MM_INSIDE_BOUND2.  The pack's norm order makes those tiles a PREFIX: the sweep starts at the first tile that is not
+    // (BASELINE recipe: two thirds of the screened wave tiles; the screening product + range check was half the sweep's time).
+    int ct_first = 0;
+    if (coll) {
+      const float a2w = g2 * 1.000001f;                     // (gmax2 is rounded up from f64; the f32-rounded operands add < 2e-7)
+      const float* zt = zt2 + (size_t)a2 * nct;
+      int cf = nct;
+      for (int c0 = 0; c0 < nct; c0 += 64) {
+        const int c = c0 + lane;
+        const bool outside = c < nct && a2w * zt[c < nct ? c : 0] > MM_INSIDE_BOUND2;
+        const unsigned long long bal = __ballot(outside);
+        if (bal) { cf = c0 + (int)__builtin_ctzll(bal); break; }
+      }
+      ct_first = cf & ~1;
+    }
+    auto sweep = [&](auto collc, auto collm) __attribute__((always_inline)) {
+      constexpr bool CM = decltype(collc)::value;
+      u32x4 zA0[ND8], zB0[ND8], zA1[ND8], zB1[ND8];
+      float w0, w1;
+      w0 = w1 = 0.0f;
+      const int ct0 = CM ? ct_first : 0;
+      if (ct0 >= nct) return;
+      load_zA(ct0, zA0);
+      if constexpr (!CM) { load_zB(0, zB0); w0 = load_wc(l31); }
+      for (int ct = ct0; ct < nct; ct += 2) {
+        load_zA(ct + 1, zA1);
+        if constexpr (!CM) { load_zB(ct + 1, zB1); w1 = load_wc((ct + 1) * 32 + l31); }
+        float emx0, ewc0, emx1, ewc1;
+        process_tile(collc, collm, ct, zA0, zB0, w0, emx0, ewc0);
+        const int cn = ct + 2 < nct ? ct + 2 : ct;               // clamped: the last pass re-reads its own tile
+        load_zA(cn, zA0);
+        if constexpr (!CM) { load_zB(cn, zB0); w0 = load_wc(cn * 32 + l31); }
+        process_tile(collc, collm, ct + 1, zA1, zB1, w1, emx1, ewc1);
+#if MM_ROUTE_EST
+        {
+          const f32x2 emx = {emx0, emx1}, ewc = {ewc0, ewc1};
+          const f32x2 u = (emx * emx) * (emx * ewc);             // both tiles at once: 4 packed instructions per tile pair
+          est2 = mm_pkfma(u, u, est2);
+          xall = fmaxf(fmaxf(xall, emx0), emx1);
+        }
+#endif
+      }
+    };
+    // A (b, pair) is collapsed only where its bound lets the screening skip most tiles (MM_COLLAPSE_BOUND2 = (1/2)^2: on the
+    // BASELINE recipe items with a bound in (1/4, 1/2] have 98 % of their wave tiles under 1/4, items beyond 1/2 a third,
+    // tools/tile_hist_baseline.py).
+    // (Two instantiations, not a run-time flag: a non-collapsed item must not pay for the collapsed coefficients -- as a flag
+    // they cost the exp2 branch 4 more ops per entry: forced-worst C3 12.5 -> 16.8 ms)
+    // (the third: the dense row groups of an item that has collapsed ones, cubic term in the moments)
+    if (coll) sweep(mm_true{}, mm_int<1>{});
+    else if (icoll) sweep(mm_false{}, mm_int<2>{});
+    else sweep(mm_false{}, mm_int<0>{});
+  }
+  {
+    const float xf = fminf(xall, 8.0f);                     // (beyond |b| = 8 the estimate is astronomically large anyway)
+    const float pf = fmaxf(fmaf(xf, xf, xf) + 1.0f, __expf(xf));   // e^X <= 1 + X + X^2 only up to X = 1.79: the larger of the two (X <= 8)
+    estl_out = ((est2[0] + est2[1]) * rowsq) * (pf * pf);
+  }
+  sum_out = sum;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The persistent sweep (d <= 8, Mp <= MM_F32P_MAX_MP): a work list of the (b, pair) items that have a tile to visit, and one
+// workgroup per CU that takes items from it.
+//
+// k_qred_f32_mfma above pays, per (b, pair), a grid slot even where every wave leaves at once (53 % of the BASELINE recipe's items),
+// a 64 KB LDS fill of an image that depends on the column latent alone (7 distinct images per step at C3, ~6.7 k fills), and, in
+// the dense row groups, per-tile (l | h) operand and column-weight loads from L2 that two waves per SIMD cannot hide (half of their
+// ~1 870 SIMD-cycles per wave tile).  Here:
+//   k_offdiag_worklist (one wave per item) applies the same "does any wave have a tile to visit" predicate, writes the zero slabs of
+//   the items without work, and lists the others by column latent a' -- bucket a' holds the B a' items of the pairs (a < a', a'),
+//   those with dense (not collapsed) row groups from its front, the others from its back;
+//   k_qred_f32_mfma_persist (MM_F32P_WAVES waves, one workgroup per CU) takes items through an atomic counter in list order, so that
+//   it refills the 96 KB latent image only when the column latent changes, copies the item's what'_j (8 KB) beside it, and hands the
+//   item's 64-row groups to its waves through an LDS counter, last group (largest |A_i|: the dense ones) first.  Each wave runs
+//   mm_f32_wave_rows with every operand from LDS and leaves its reduced (sum, estimate) in the group's LDS slot; after one barrier
+//   the panel sums are red[4 p] + .. + red[4 p + 3] left to right, as in k_qred_f32_mfma: the slabs are bit-identical.
+// Workspace: MMWorkspaceLayout::plist ([0] the queue counter, [4 + 2 a'] / [5 + 2 a'] the front / back counts of bucket a', zeroed
+// before every pass; the list behind them).
+// ---------------------------------------------------------------------------------------------------------------------------
+#ifndef MM_F32P_WAVES
+#define MM_F32P_WAVES 8
+#endif
+// largest Mp whose latent image (Mp * 48 bytes), column weights (Mp * 4) and group slots fit the 160 KB of LDS
+#define MM_F32P_MAX_MP 2048
+static inline size_t mm_f32p_lds_bytes(int Mp) {
+  return (size_t)Mp * 48 + (size_t)Mp * 4 + (size_t)mm_mfma_groups(Mp) * 12;
+}
+
+__global__ __launch_bounds__(256) void k_offdiag_worklist(int L, int Mp, int P, int Po, int NS, int npanel, int B, int force_worst,
+                                                          const unsigned int* __restrict__ amax, const unsigned int* __restrict__ amaxc,
+                                                          const unsigned char* __restrict__ gflag, const float* __restrict__ gmax2,
+                                                          const double* __restrict__ zmax2, double* __restrict__ partB,
+                                                          float* __restrict__ estO, int* __restrict__ plist, int* __restrict__ rcount) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { rcount[0] = 0; rcount[1] = 0; }   // this pass's route list (k_route_decide follows)
+  const int item = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (item >= B * Po) return;                                 // (wave-uniform)
+  const int b = item / Po, lp = item - b * Po, p = L + lp;
+  int a, a2;
+  mm_decode_pair_o(p, L, a, a2);
+  bool work = true, dense = true;
+  if (!force_worst) {
+    if (mm_collapse_bound2(amax[item], zmax2[a2]) <= MM_INSIDE_BOUND2) {
+      work = false;                                           // every |b_ij| inside the collapsed range
+    } else if (mm_item_collapsed(amaxc[item])) {
+      // row groups (k_qred_f32_mfma's need / wave_inside): a collapsed group inside by its own bound has no tile to visit
+      const int ng = Mp / MM_GROUP_ROWS;
+      const size_t grp0 = (size_t)item * ng;
+      bool need = false, dn = false;
+      for (int g = lane; g < ng; g += 64) {
+        const bool coll = gflag[grp0 + g] != 0;
+        need = need || !(coll && mm_collapse_bound2(__float_as_uint(gmax2[grp0 + g]), zmax2[a2]) <= MM_INSIDE_BOUND2);
+        dn = dn || !coll;
+      }
+      work = __any(need);
+      dense = __any(dn);
+    }
+  }
+  if (!work) {
+    for (int panel = lane; panel < npanel; panel += 64) {
+      partB[((size_t)b * P + p) * NS + panel] = 0.0;
+      estO[(size_t)item * npanel + panel] = 0.0f;             // exact (f64 moments): nothing to estimate
+    }
+    return;
+  }
+  if (lane == 0) {
+    int* list = plist + mm_f32p_list_off(L);
+    const int off = B * (a2 * (a2 - 1) / 2), cap = B * a2;    // bucket a2: the B a2 items of the pairs (a < a2, a2)
+    if (dense) list[off + atomicAdd(plist + 4 + 2 * a2, 1)] = item;
+    else list[off + cap - 1 - atomicAdd(plist + 5 + 2 * a2, 1)] = item;
+  }
+}
+
+__global__ __launch_bounds__(64 * MM_F32P_WAVES, 1) void k_qred_f32_mfma_persist(const unsigned short* __restrict__ Zs3, int L, int Mp,
+                                                                               int d, int P, int Po, int NS, int npanel, int B,
+                                                                               int force_worst, const unsigned int* __restrict__ amaxc,
+                                                                               const unsigned char* __restrict__ gflag,
+                                                                               const float* __restrict__ gmax2,
+                                                                               const double* __restrict__ zmax2,
+                                                                               const float* __restrict__ zt2,
+                                                                               const float* __restrict__ rowO,
+                                                                               const float* __restrict__ colO,
+                                                                               double* __restrict__ partB, float* __restrict__ estO,
+                                                                               int* __restrict__ plist) {
+  constexpr int NT = 64 * MM_F32P_WAVES;
+  // LDS: the column latent's [Mp/32][3 (h, m, l)][32][16] image | the item's what'_j [Mp] f32 | per 64-row group: sum f64, estimate f32
+  extern __shared__ __align__(16) char zlds[];
+  __shared__ int s_next, s_gcur;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ngrp = mm_mfma_groups(Mp);
+  float* wlds = reinterpret_cast<float*>(zlds + (size_t)Mp * 48);
+  double* red = reinterpret_cast<double*>(wlds + Mp);
+  float* redf = reinterpret_cast<float*>(red + ngrp);
+  const int* cnt = plist + 4;                                 // [L][front, back]
+  const int* list = plist + mm_f32p_list_off(L);
+  int total = 0;
+  for (int c = 1; c < L; ++c) total += cnt[2 * c] + cnt[2 * c + 1];
+  if (tid == 0) s_next = atomicAdd(plist, 1);
+  __syncthreads();
+  int cur = -1;                                               // the column latent of the LDS image
+  for (;;) {
+    int r = __builtin_amdgcn_readfirstlane(s_next);
+    if (r >= total) break;
+    // list position -> item: bucket c (column latent), dense items from its front, the others from its back
+    int c = 1;
+    while (r >= cnt[2 * c] + cnt[2 * c + 1]) { r -= cnt[2 * c] + cnt[2 * c + 1]; ++c; }
+    const int boff = B * (c * (c - 1) / 2);
+    const int item = __builtin_amdgcn_readfirstlane(list[boff + (r < cnt[2 * c] ? r : B * c - 1 - (r - cnt[2 * c]))]);
+    const int b = item / Po, lp = item - b * Po, p = L + lp;
+    int a, a2;
+    mm_decode_pair_o(p, L, a, a2);
+    // (the fills' per-thread offsets are recomputed per item: hoisted out of the item loop they took registers of the tile loop)
+    int ft = tid;
+    asm volatile("" : "+v"(ft));
+    if (a2 != cur) {
+      // the latent's three parts are one contiguous block of the packed model: 16-byte chunks, 8 in flight per thread
+      const char* src = reinterpret_cast<const char*>(Zs3 + (size_t)a2 * Mp * 24);
+      const int nchunk = Mp * 3;
+      for (int c0 = 0; c0 < nchunk; c0 += 8 * NT) {
+        u32x4 tmp[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int ch = c0 + u * NT + ft;
+          tmp[u] = *reinterpret_cast<const u32x4*>(src + (size_t)(ch < nchunk ? ch : nchunk - 1) * 16);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int ch = c0 + u * NT + ft;
+          if (ch < nchunk) *reinterpret_cast<u32x4*>(zlds + (size_t)ch * 16) = tmp[u];
+        }
+      }
+      cur = a2;
+    }
+    {
+      const float* src = colO + (size_t)item * Mp;
+      for (int ch = ft; ch < Mp / 4; ch += NT)
+        reinterpret_cast<u32x4*>(wlds)[ch] = *reinterpret_cast<const u32x4*>(src + (size_t)ch * 4);
+    }
+    if (tid == 0) s_gcur = 0;
+    __syncthreads();                                          // image, what'_j, s_gcur ready; everyone has read s_next
+    if (tid == 0) s_next = atomicAdd(plist, 1);               // (the next item, read after the barrier below)
+    const bool icoll = !force_worst && mm_item_collapsed(amaxc[item]);
+    const size_t grp0 = (size_t)item * (size_t)(Mp / MM_GROUP_ROWS);
+    // (every lane takes part in the LDS atomic -- lane 0 adds 1, the others 0 -- and lane 0's old value is the wave's: no
+    // lane-divergent branch around it, so the loop stays wave-uniform for the compiler as it is at run time)
+    for (int gi = __builtin_amdgcn_readfirstlane(atomicAdd(&s_gcur, lane == 0 ? 1 : 0)); gi < ngrp;
+         gi = __builtin_amdgcn_readfirstlane(atomicAdd(&s_gcur, lane == 0 ? 1 : 0))) {
+      const int g = ngrp - 1 - gi;
+      double sum;
+      float estl;
+      mm_f32_wave_rows<1>(zlds, wlds, g * 64, b, lp, a2, Mp, d, Po, force_worst, icoll, grp0, amaxc, gflag, gmax2, zmax2, zt2, rowO,
+                          sum, estl);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) { sum += __shfl_down(sum, off, 64); estl += __shfl_down(estl, off, 64); }
+      if (lane == 0) { red[g] = sum; redf[g] = estl; }
+    }
+    __syncthreads();                                          // every group's slot written
+    for (int panel = tid; panel < npanel; panel += NT) {
+      const double* rp = red + 4 * panel;
+      const float* rf = redf + 4 * panel;
+      partB[((size_t)b * P + p) * NS + panel] = rp[0] + rp[1] + rp[2] + rp[3];
+      estO[(size_t)item * npanel + panel] = (rf[0] + rf[1]) + (rf[2] + rf[3]);
+    }
+    // (the next item's writes of red[] follow its first barrier; its image / what'_j writes touch nothing read here)
+  }
+}
+
 extern "C" int mm_mfma_supported(int d) { return d >= 1 && d <= 32; }
 
 int mm_mfma_num_slots(int Mp) { return (Mp + MM_PANEL_ROWS - 1) / MM_PANEL_ROWS; }
@@ -540,6 +998,44 @@ int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, c
   const float* colO = (const float*)(ws + wl.colO);
   double* partB = (double*)(ws + wl.partB);
   float* estO = (float*)(ws + wl.estO);
+  // (not with the forced worst tier: every group is dense there and the per-item fill and barriers cost more than the staged
+  // operands save -- measured at C3, worst regime 18.64 -> 19.07 ms per step)
+  if (ml.nd8 == 1 && zmax2 && wl.Mp <= MM_F32P_MAX_MP && !force_worst && !(flags & MM_ISTAGE_OLD_OFFDIAG)) {
+    // the work list (zeroed header first), then the persistent sweep over it: one workgroup per CU
+    int* plist = (int*)(ws + wl.plist);
+    const int nitem = wl.Po * B;                       // (<= nwork above)
+    const hipError_t em = hipMemsetAsync(plist, 0, (size_t)mm_f32p_list_off(L) * 4, stream);
+    if (em != hipSuccess) return (int)em;
+    hipLaunchKernelGGL(k_offdiag_worklist, dim3((nitem + 3) / 4), dim3(256), 0, stream, L, wl.Mp, wl.P, wl.Po, wl.NS, npanel, B,
+                       force_worst, amax, (const unsigned int*)(ws + wl.amaxc), (const unsigned char*)(ws + wl.gflag),
+                       (const float*)(ws + wl.gmax2), zmax2, partB, estO, plist, (int*)(ws + wl.rcount));
+    const hipError_t el = hipGetLastError();
+    if (el != hipSuccess) return (int)el;
+    // (raise the dynamic-LDS limit and read the CU count once per device: the calls are slow)
+    const size_t shm = mm_f32p_lds_bytes(wl.Mp);
+    static std::atomic<unsigned long long> attr_done{0ull};
+    static std::atomic<int> ncu_cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 64;
+    const unsigned long long bit = (dev >= 0 && dev < 64) ? (1ull << dev) : 0ull;
+    int ncu = bit ? ncu_cached[dev].load() : 0;
+    if (!bit || !(attr_done.load() & bit)) {
+      const hipError_t ea = hipFuncSetAttribute((const void*)k_qred_f32_mfma_persist, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)mm_f32p_lds_bytes(MM_F32P_MAX_MP));
+      if (ea != hipSuccess) return (int)ea;
+      int v = 0;
+      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev < 64 ? dev : 0) != hipSuccess || v <= 0) v = 256;
+      ncu = v;
+      if (bit) { ncu_cached[dev].store(v); attr_done.fetch_or(bit); }
+    }
+    if (ncu <= 0) ncu = 256;
+    hipLaunchKernelGGL(k_qred_f32_mfma_persist, dim3(nitem < ncu ? nitem : ncu), dim3(64 * MM_F32P_WAVES), shm, stream, Zs3, L, wl.Mp,
+                       d, wl.P, wl.Po, wl.NS, npanel, B, force_worst, (const unsigned int*)(ws + wl.amaxc),
+                       (const unsigned char*)(ws + wl.gflag), (const float*)(ws + wl.gmax2), zmax2, (const float*)(packed + ml.zt2),
+                       rowO, colO, partB, estO, plist);
+    const hipError_t ep = hipGetLastError();
+    return ep == hipSuccess ? 0 : (int)ep;
+  }
 #define MM_LAUNCH_ND(ND_, LZ_, SH_)                                                                          \
   hipLaunchKernelGGL((k_qred_f32_mfma<ND_, LZ_>), dim3(nwork), dim3(256), SH_, stream, Zs3, L, wl.Mp, d,    \
                      wl.P, wl.Po, wl.NS, npanel, ppw, nwork, force_worst, amax, (const unsigned int*)(ws + wl.amaxc), \
