@@ -61,6 +61,43 @@ static inline int mm_compose_dims(int nx, int na, const int32_t* active_dims, MM
   return 0;
 }
 
+// ---- several actions (mm_compose_nd.hip): nu policy latents, nd = ne + nu ------------------------------------------
+#define MMC_NU 4           // largest number of actions
+
+// host copy of the head's per-action constants, passed to the kernels by value
+struct MMHeadND { double scale[MMC_NU], shift[MMC_NU]; };
+
+// the same blocks as MMComposeLayout with nu policy outputs: pf1 [B][nu], pSff [B][nu][nu], pcross [B][ne][nu],
+// md [B][nd], Sdd [B][nd][nd], dcross [B][nd][nx], cpol [B][ne][nu] f64
+static inline MMComposeLayout mm_compose_layout_nd(int B, int nx, int na, int nu, int dtype) {
+  MMComposeLayout o;
+  const size_t es = mm_elem_size(dtype), A = 256;
+  const int nb = nx - na, ne = 2 * na + nb, nd = ne + nu;
+  size_t off = 0;
+  o.me = off;     off = mm_align_up(off + (size_t)B * ne * es, A);
+  o.See = off;    off = mm_align_up(off + (size_t)B * ne * ne * es, A);
+  o.pf1 = off;    off = mm_align_up(off + (size_t)B * nu * es, A);
+  o.pSff = off;   off = mm_align_up(off + (size_t)B * nu * nu * es, A);
+  o.pcross = off; off = mm_align_up(off + (size_t)B * ne * nu * es, A);
+  o.md = off;     off = mm_align_up(off + (size_t)B * nd * es, A);
+  o.Sdd = off;    off = mm_align_up(off + (size_t)B * nd * nd * es, A);
+  o.df1 = off;    off = mm_align_up(off + (size_t)B * nx * es, A);
+  o.dSff = off;   off = mm_align_up(off + (size_t)B * nx * nx * es, A);
+  o.dcross = off; off = mm_align_up(off + (size_t)B * nd * nx * es, A);
+  o.Sxe = off;    off = mm_align_up(off + (size_t)B * nx * ne * 8, A);
+  o.cpol = off;   off = mm_align_up(off + (size_t)B * ne * nu * 8, A);
+  o.total = off;
+  return o;
+}
+
+static inline int mm_compose_dims_nd(int nx, int na, int nu, const int32_t* active_dims, MMComposeDims& D) {
+  if (nu < 1 || nu > MMC_NU) return MM_E_DIM;
+  const int rc = mm_compose_dims(nx, na, active_dims, D);
+  if (rc) return rc;
+  D.nd = D.ne + nu;
+  return D.nd > MMC_ND ? MM_E_DIM : 0;
+}
+
 
 // ---- tape of a rollout that will be differentiated (mm_rollout_composed_taped -> mm_rollout_composed_backward) ----
 // H + 1 slots with the compose-workspace layout: slot h holds everything step h produced from x_h (me, See, Sxe of

@@ -24,8 +24,10 @@ def get_state_initializer(mean: torch.Tensor, covariance: torch.Tensor) -> Calla
 
 def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[list], moment_solver: bool):
   """The pieces the native rollouts are written for -- TrigonometricEncoder, policy = InverseLinkWrapper(KernelRegressor(SVGP with
-  one latent), Chain[Scale, Shift, NormalCDF]) with scalar scale and shift, SVGP drift, no diffusion, GaussianObjective (the
-  cartpole wiring of ``examples/cartpole_swingup/swingup_loops.py:41-91``) -- or None, with the reason appended to ``why``."""
+  one latent per action, up to 4), Chain[Scale, Shift, NormalCDF]) with scale and shift a scalar or one value per action, SVGP
+  drift, no diffusion, GaussianObjective (the cartpole wiring of ``examples/cartpole_swingup/swingup_loops.py:41-91``; two
+  actions: the double pendulum) -- or None, with the reason appended to ``why``.  ``head_constants()`` returns two floats for
+  one action and two tuples of nu floats for nu > 1."""
   from . import bijectors as tfb
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
@@ -47,8 +49,11 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   if not isinstance(pol, InverseLinkWrapper) or not isinstance(pol.model, KernelRegressor):
     return no("the policy is not InverseLinkWrapper(KernelRegressor(SVGP))")
   pm_, head = pol.model.model, pol.invlink
-  if not isinstance(pm_, SVGP) or not isinstance(drift, SVGP) or pm_.num_latent_gps != 1:
-    return no("the policy is not a one-latent SVGP or the drift is not an SVGP")
+  if not isinstance(pm_, SVGP) or not isinstance(drift, SVGP):
+    return no("the policy or the drift is not an SVGP")
+  nu = int(pm_.num_latent_gps)
+  if nu < 1 or nu > 4:
+    return no(f"a policy with {nu} latents (the native rollout takes 1 to 4 actions)")
   if isinstance(pm_.kernel, LinearCoregionalization) or isinstance(drift.kernel, LinearCoregionalization):
     return no("a LinearCoregionalization kernel (its mixing stays on the host)")
   if any(k.active_dims is not None for k in pm_.latent_kernels + drift.latent_kernels):
@@ -57,14 +62,23 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   if not (bj and len(bj) == 3 and isinstance(bj[0], tfb.Scale) and isinstance(bj[1], tfb.Shift) and isinstance(bj[2], tfb.NormalCDF)):
     return no("the policy head is not Chain[Scale, Shift, NormalCDF]")
 
+  def _constant(v):
+    if isinstance(v, torch.Tensor):
+      v = v.detach()
+      v = float(v) if v.numel() == 1 else [float(t) for t in v.reshape(-1).tolist()]
+    if nu == 1:
+      return float(v)
+    vals = tuple(float(t) for t in v) if isinstance(v, (list, tuple)) else (float(v),) * nu
+    if len(vals) != nu:
+      raise ValueError("not one value per action")
+    return vals
+
   def head_constants():
-    sc, sh = bj[0].scale, bj[1].shift
-    return (float(sc.detach()) if isinstance(sc, torch.Tensor) else float(sc),
-            float(sh.detach()) if isinstance(sh, torch.Tensor) else float(sh))
+    return _constant(bj[0].scale), _constant(bj[1].shift)
   try:
     head_constants()
   except (TypeError, ValueError, RuntimeError):
-    return no("the policy head's scale / shift are not scalars (n-D action: Genz BVN, out of scope)")
+    return no("the policy head's scale / shift are neither scalars nor one value per action")
   return enc, pm_, drift, bj, head_constants
 
 
@@ -72,10 +86,11 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
                        why: Optional[list] = None):
   """``f(mx, Sxx) -> loss [B]`` running the whole rollout in ``mm_rollout_composed`` (csrc/mm_compose.hip), or None
   when the system is not the shape that entry point implements: TrigonometricEncoder, policy =
-  InverseLinkWrapper(KernelRegressor(SVGP with one latent), Chain[Scale, Shift, NormalCDF]) with scalar scale and
-  shift, SVGP drift, no diffusion, MomentMatchingEuler, GaussianObjective -- the cartpole wiring of
-  ``examples/cartpole_swingup/swingup_loops.py:41-91``.  ``f.with_grad(mx, Sxx)`` is the same loss as a differentiable op
-  (native reverse sweep, csrc/mm_compose_bwd.hip) where ``f.supports_grad(mx)``.  ``why``: a list that receives the reason
+  InverseLinkWrapper(KernelRegressor(SVGP with one latent per action), Chain[Scale, Shift, NormalCDF]), SVGP drift, no
+  diffusion, MomentMatchingEuler, GaussianObjective -- the cartpole wiring of
+  ``examples/cartpole_swingup/swingup_loops.py:41-91``; a policy with 2 to 4 actions runs in ``mm_rollout_composed_nd``
+  (csrc/mm_compose_nd.hip).  ``f.with_grad(mx, Sxx)`` is the same loss as a differentiable op
+  (native reverse sweep, csrc/mm_compose_bwd.hip) where ``f.supports_grad(mx)``: one action only.  ``why``: a list that receives the reason
   when None is returned."""
   from . import ops
   parts = _native_parts(system, objective, why, moment_solver=True)
@@ -142,6 +157,9 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     """None when ``with_grad`` covers everything that asks for a gradient here, else the reason it does not."""
     if mx.dtype not in (torch.float32, torch.float64):
       return f"state dtype {mx.dtype}"
+    if pm_.num_latent_gps > 1:
+      return (f"the policy has nu = {pm_.num_latent_gps} actions (nu > 1: the native rollout is forward only, its tape and "
+              "reverse sweep are one-action)")
     # the native reverse sweep returns gradients for the policy SVGP's parameters and the initial state only: the head's
     # Scale / Shift and the objective's target / precision enter as constants (float() / raw pointers)
     outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
@@ -177,7 +195,8 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   implements (``native_policy_loss``) and the state is on the GPU: forward only (one ``mm_rollout_composed`` call) when
   nothing requires a gradient, and as ONE differentiable op -- taped forward + native reverse sweep
   (``autodiff.ComposedRolloutFunction``) -- when the policy's parameters or the initial state do (float64, frozen
-  drift); False always takes the torch composition (``forward_sde`` over ``moment_matching``); True insists on the
+  drift, one action; with several actions a gradient takes the torch composition, which differentiates through
+  ``special.bvn_cdf``); False always takes the torch composition (``forward_sde`` over ``moment_matching``); True insists on the
   native path."""
   uniform = solution_times is None
   if solution_times is None:
@@ -346,7 +365,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   ``paths``: None = new sample paths on every call (pilco.py:281-284), else a ``pathwise.Paths`` to reuse.  Unit-spaced solution
   times ``dt, 2 dt, ...`` (pilco.py:257: ``arange(1, 1 + num_steps)``).
 
-  On the GPU, for the cartpole wiring (``_native_parts``) with drift inputs of dimension <= 8, the whole closure is the native
+  On the GPU, for the cartpole wiring (``_native_parts``, one action) with drift inputs of dimension <= 8, the whole closure is the native
   rollout (csrc/mm_pathwise_policy.hip): forward only when nothing requires a gradient, else ONE differentiable op
   (``pathwise.PolicyRolloutFunction``: the stream pass also emits the paths' Jacobians, the reverse sweep is one kernel).
   Otherwise -- ``native=False``, another wiring, a gradient the native sweep does not cover -- the torch composition through
@@ -361,6 +380,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False)
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
+  if native is True and parts[1].num_latent_gps > 1:
+    raise ValueError("native=True: the native pathwise rollout is one-action")
   warned = []
 
   def _fallback(reason):
@@ -392,6 +413,9 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       return _torch_loss(x0, pth)
     enc, pm_, _, bj, head_constants = parts
     nx, na = x0.shape[-1], len(enc.active_dims)
+    if pm_.num_latent_gps > 1:
+      _fallback(f"the policy has nu = {pm_.num_latent_gps} actions (nu > 1: the native pathwise rollout is one-action)")
+      return _torch_loss(x0, pth)
     if nx + na + 1 > 8 or pm_.inducing_variable.inducing_variables[0].Z.shape[0] > 256:
       _fallback("drift inputs of dimension > 8 or a policy of more than 256 centres")
       return _torch_loss(x0, pth)

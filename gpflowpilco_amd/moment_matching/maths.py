@@ -34,6 +34,8 @@ def _mm_gauss_identity(x: GaussianMoments, _, c=None):
 @dispatcher.register(GaussianMoments, _type_add, NumericalTypes)
 def _mm_gauss_add(x: GaussianMoments, _, c):
   """maths.py:48-52."""
+  if isinstance(c, torch.Tensor) and c.ndim:   # one shift per dim, given on any device
+    c = c.to(dtype=x.dtype, device=x.mean().device)
   y = GaussianMoments(moments=(x.mean() + c, x.covariance()), centered=True)
   return GaussianMatch(x=x, y=y, cross=(LinearOperatorDiag.identity_like(x.mean()), True))
 
@@ -50,7 +52,12 @@ def _mm_gauss_mul(x: GaussianMoments, _, c):
   """maths.py:62-79."""
   if isinstance(c, torch.Tensor):              # Python scalars stay scalars (no host->device upload per call)
     c = c.to(dtype=x.dtype, device=x.mean().device)
-  y2 = LinearOperatorDiag((c ** 2) * x[1].diag) if isinstance(x[1], LinearOperatorDiag) else (c ** 2) * x[1]
+  if isinstance(x[1], LinearOperatorDiag):
+    y2 = LinearOperatorDiag((c ** 2) * x[1].diag)
+  elif isinstance(c, torch.Tensor) and c.ndim:   # one factor per dim: the second moment scales by the outer product
+    y2 = _outer(torch.mul, c, c) * x[1]
+  else:
+    y2 = (c ** 2) * x[1]
   y = GaussianMoments(moments=(c * x[0], y2), centered=x.centered)
   return GaussianMatch(x=x, y=y, cross=(LinearOperatorDiag.identity_like(x.mean(), c), True))
 

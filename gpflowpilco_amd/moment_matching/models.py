@@ -26,8 +26,9 @@ from .gaussian import GaussianMatch, GaussianMoments
 @dispatcher.register(GaussianMoments, InverseLinkWrapper)
 def _mm_gauss_invlink(x: GaussianMoments, wrapper: InverseLinkWrapper, /, **kw):
   """models.py:27-31."""
+  from .bijectors import head_member
   base = partial(wrapper.model, **kw)
-  chain = Chain(wrapper.invlink, base)
+  chain = Chain(head_member(wrapper.invlink), base)
   return dispatcher(x, chain)
 
 

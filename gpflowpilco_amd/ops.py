@@ -375,34 +375,54 @@ class ComposedRollout:
   TrigonometricEncoder -> policy (SVGP mean, Chain[Scale, Shift, NormalCDF]) -> drift SVGP with the
   ``forward_sde`` cross-covariance bookkeeping -> Euler moment update -> per-step expected cost.
 
-  ``drift`` / ``policy``: PackedModel (drift with C; policy one latent).  ``__call__(mx, Sxx, H)`` returns
-  ``(mx_H, Sxx_H, cost [B, H])`` (and the trajectory if asked); the inputs are not modified.
+  ``drift`` / ``policy``: PackedModel (drift with C; policy with one latent per action, ``nu = policy.L``).  ``nu == 1`` is
+  ``mm_rollout_composed``; ``nu > 1`` (up to 4 actions) ``mm_rollout_composed_nd`` (csrc/mm_compose_nd.hip: the head's cross
+  moments are bivariate normal CDFs), forward only.  ``head_scale`` / ``head_shift``: a float or one value per action.
+  ``__call__(mx, Sxx, H)`` returns ``(mx_H, Sxx_H, cost [B, H])`` (and the trajectory if asked); the inputs are not modified.
   """
 
-  def __init__(self, drift: PackedModel, policy: PackedModel, nx: int, active_dims, head_scale: float, head_shift: float,
+  def __init__(self, drift: PackedModel, policy: PackedModel, nx: int, active_dims, head_scale, head_shift,
                target: torch.Tensor, precis: torch.Tensor):
     self.drift, self.policy = drift, policy
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
     self.na = len(self.active)
     self.ne = self.nx + self.na
-    self.nd = self.ne + 1
+    self.nu = int(policy.L)
+    self.nd = self.ne + self.nu
     if drift.dtype != policy.dtype:
       raise TypeError("drift and policy must be packed with the same dtype")
-    if drift.L != self.nx or drift.d != self.nd or policy.L != 1 or policy.d != self.ne:
+    if drift.L != self.nx or drift.d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: drift L={drift.L} d={drift.d} (want {self.nx}, {self.nd}), "
-                       f"policy L={policy.L} d={policy.d} (want 1, {self.ne})")
+                       f"policy L={policy.L} d={policy.d} (want {self.nu}, {self.ne})")
     if not drift.with_C:
       raise ValueError("the drift is evaluated with model uncertainty: pack it with C")
-    self.scale, self.shift = float(head_scale), float(head_shift)
+    if self.nu == 1:
+      self.scale, self.shift = float(head_scale), float(head_shift)
+    else:
+      self.scale, self.shift = self._per_action(head_scale, "head_scale"), self._per_action(head_shift, "head_shift")
+      self._scale_c = (_lib.C.c_double * self.nu)(*self.scale)
+      self._shift_c = (_lib.C.c_double * self.nu)(*self.shift)
     self.target = target.to(dtype=drift.dtype, device=drift.device).contiguous()
     self.precis = precis.to(dtype=drift.dtype, device=drift.device).contiguous()
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
     self._wsc = {}
 
+  def _per_action(self, v, name):
+    """A float (the same for every action) or a length-nu sequence / tensor -> tuple of nu floats."""
+    if isinstance(v, torch.Tensor):
+      v = v.detach().cpu().tolist()
+    vals = tuple(float(t) for t in v) if hasattr(v, "__len__") else (float(v),) * self.nu
+    if len(vals) != self.nu:
+      raise ValueError(f"{name}: expected a float or {self.nu} values (one per action), got {len(vals)}")
+    return vals
+
   def _compose_ws(self, B):
     ws = self._wsc.get(B)
     if ws is None:
-      n = lib().mm_compose_workspace_bytes(B, self.nx, self.na, _dtype_code(self.drift.dtype))
+      if self.nu == 1:
+        n = lib().mm_compose_workspace_bytes(B, self.nx, self.na, _dtype_code(self.drift.dtype))
+      else:
+        n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(self.drift.dtype))
       if n == 0:
         raise ValueError("mm_compose_workspace_bytes rejected the shape")
       ws = torch.empty(n, dtype=torch.uint8, device=self.drift.device)
@@ -442,6 +462,11 @@ class ComposedRollout:
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
     wc = self._compose_ws(B)
+    if self.nu > 1:
+      rc = self._call_nd(pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc)
+      check(rc, "mm_rollout_composed_nd")
+      out = (mx, Sxx, cost.T.contiguous())
+      return out + (tmu, tS) if keep_trajectory else out
     rc = lib().mm_rollout_composed(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
                                    pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
                                    _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act,
@@ -454,17 +479,51 @@ class ComposedRollout:
     return out + (tmu, tS) if keep_trajectory else out
 
 
+  def _call_nd(self, pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, scale=None, shift=None):
+    """``mm_rollout_composed_nd`` on prepared buffers (``scale`` / ``shift``: ctypes arrays of nu doubles)."""
+    dt_ = self.drift.dtype
+    return lib().mm_rollout_composed_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+                                        pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
+                                        _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act, self.nu,
+                                        self._scale_c if scale is None else scale, self._shift_c if shift is None else shift,
+                                        self.target.data_ptr(), self.precis.data_ptr(),
+                                        mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
+                                        wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
+                                        self.drift.status().data_ptr(), _stream(mx.device))
+
+  def call_nd_entry(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0):
+    """The same rollout through ``mm_rollout_composed_nd`` whatever nu is (a one-action rollout normally takes
+    ``mm_rollout_composed``): -> (mx_H, Sxx_H, cost [B, H]).  The two entries must agree for nu == 1."""
+    B = self._check_state(mx, Sxx)
+    dt_ = self.drift.dtype
+    mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
+    H = int(num_steps)
+    cost = torch.empty(H, B, dtype=dt_, device=mx.device)
+    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
+    wp = self.policy.workspace(B, MM_FULL_OUTPUT_COV)
+    n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(dt_))
+    if n == 0:
+      raise ValueError("mm_compose_nd_workspace_bytes rejected the shape")
+    wc = torch.empty(n, dtype=torch.uint8, device=mx.device)
+    as_c = lambda v: (_lib.C.c_double * self.nu)(*((v,) if self.nu == 1 else v))
+    rc = self._call_nd(self.policy, B, H, dt, mx, Sxx, cost, None, None, wd, wp, wc, as_c(self.scale), as_c(self.shift))
+    check(rc, "mm_rollout_composed_nd")
+    return mx, Sxx, cost.T.contiguous()
+
   # ---- differentiable form: tape + reverse sweep (csrc/mm_compose_bwd.hip) -------------------------------------------
   BACKWARD_MAX_POLICY_M = 256
 
   def supports_backward(self) -> bool:
-    """The native reverse sweep exists for f64 rollouts whose policy has M <= 256 centres on ne <= 8 encoded dims (one
-    workgroup per batch element sweeps the policy's M x M block from LDS: 120 KB at M = 256, ne = 8)."""
-    return self.drift.dtype == torch.float64 and self.policy.M <= self.BACKWARD_MAX_POLICY_M and self.ne <= 8
+    """The native reverse sweep exists for one-action f64 rollouts whose policy has M <= 256 centres on ne <= 8 encoded
+    dims (one workgroup per batch element sweeps the policy's M x M block from LDS: 120 KB at M = 256, ne = 8)."""
+    return (self.nu == 1 and self.drift.dtype == torch.float64 and self.policy.M <= self.BACKWARD_MAX_POLICY_M
+            and self.ne <= 8)
 
   def taped(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
     """``mm_rollout_composed_taped``: -> (mx_H, Sxx_H, cost [H, B], tape).  ``policy``: another pack of the same shape
     (the current parameters of a trainable policy)."""
+    if self.nu != 1:
+      raise NotImplementedError("the tape and the native reverse sweep are one-action (supports_backward() is False)")
     pol = self._policy_pack(policy)
     dt_ = self.drift.dtype
     B, H = self._check_state(mx, Sxx), int(num_steps)

@@ -199,8 +199,8 @@ int mm_route_estimates(const void* packed, size_t packed_bytes, int L, int M, in
  * policy: one latent, policy_d == ne, evaluated without model uncertainty (a KernelRegressor has none).
  * mx [B,nx] / Sxx [B,nx,nx] are updated in place; cost [H,B] (optional, needs target [ne], precis [ne,ne]) receives
  * the per-step statistic (the loss of pilco.py:199-205 is its sum over H); traj_* [H,B,..] optional.
- * active_dims: HOST array of na distinct state indices.  Only the 1-D action (Owen's T branch, bijectors.py:57-58)
- * is supported; the n-D branch needs the Genz BVN (utils/bvn.py), out of scope. */
+ * active_dims: HOST array of na distinct state indices.  One action (Owen's T branch, bijectors.py:57-58); several
+ * actions: mm_rollout_composed_nd below. */
 size_t mm_compose_workspace_bytes(int B, int nx, int na, int dtype);
 int mm_rollout_composed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
                         const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
@@ -209,6 +209,23 @@ int mm_rollout_composed(const void* drift_packed, size_t drift_bytes, int drift_
                         void* mx, void* Sxx, void* cost, void* traj_mu, void* traj_Sigma,
                         void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
                         void* ws_compose, size_t ws_compose_bytes, int32_t* status, void* stream);
+
+/* The same rollout for a policy with nu actions (1 <= nu <= 4, ne + nu <= 32, else MM_E_DIM): policy = InverseLinkWrapper(
+ * KernelRegressor(SVGP with nu latents), Chain[Scale, Shift, NormalCDF]), u_j = head_scale[j] (Phi(f_j(e)) + head_shift[j]),
+ * drift on d = joint(e, u) with nd = ne + nu (csrc/mm_compose_nd.hip).  The head is the n-D branch of bijectors.py:48-69:
+ * E[Phi(f_i) Phi(f_j)] is a bivariate normal CDF, evaluated by Plackett's integral on 4 x 48 Gauss-Legendre nodes (the diagonal
+ * keeps Owen's T).  policy: packed with L = nu latents, policy_d == ne; drift_d == nd; head_scale / head_shift: HOST arrays of
+ * nu doubles.  Everything else as mm_rollout_composed; nu == 1 computes what mm_rollout_composed computes (through the general
+ * policy match).  Forward only: the tape and the reverse sweep below are one-action. */
+size_t mm_compose_nd_workspace_bytes(int B, int nx, int na, int nu, int dtype);
+int mm_rollout_composed_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                           const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                           int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                           int nu, const double* head_scale, const double* head_shift,
+                           const void* target, const void* precis,
+                           void* mx, void* Sxx, void* cost, void* traj_mu, void* traj_Sigma,
+                           void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                           void* ws_compose, size_t ws_compose_bytes, int32_t* status, void* stream);
 
 /* The same rollout, RECORDED for differentiation: every per-step intermediate and the states x_0 .. x_H are written into
  * `tape` (mm_compose_tape_bytes) instead of a reused workspace; mx / Sxx / cost as above.  Where H copies of the drift's
