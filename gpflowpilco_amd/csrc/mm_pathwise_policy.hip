@@ -16,92 +16,7 @@
 // the steps backwards, the state's adjoint in registers) that reads the tape -- states, drift inputs, Jacobians: no second
 // pass over the weight stream -- and accumulates the packed policy's gradient per wave (fixed-order wave sums -> per-wave
 // slabs -> k_pw_grad_sum: deterministic).  All small algebra in f64 whatever the paths' element type.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include "mm_common.h"
-#include "mm_compose.h"
-
-int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
-                       const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
-                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s);
-
-#define MMP_NE 24            // largest encoded dimension (2 na + nb, na <= 8, nx <= 16)
-#define MMP_POLICY_MMAX 256
-
-struct MMPwTapeLayout {
-  size_t x;      // [H + 1][S][nx] T   states
-  size_t din;    // [H][S][nd] T       drift inputs (e_h, u_h)
-  size_t f;      // [S][nx] T          the current step's drift sample (scratch)
-  size_t jac;    // [H][S][nx][nd] T   d f / d d per step (0 bytes when not differentiating)
-  size_t total;
-};
-static inline MMPwTapeLayout mm_pw_tape_layout(int S, int H, int nx, int na, int dtype, int with_jac) {
-  MMPwTapeLayout o;
-  const size_t es = mm_elem_size(dtype), A = 256;
-  const int nd = nx + na + 1;
-  size_t off = 0;
-  o.x = off;   off = mm_align_up(off + (size_t)(H + 1) * S * nx * es, A);
-  o.din = off; off = mm_align_up(off + (size_t)H * S * nd * es, A);
-  o.f = off;   off = mm_align_up(off + (size_t)S * nx * es, A);
-  o.jac = off; off = mm_align_up(off + (with_jac ? (size_t)H * S * nx * nd * es : 0), A);
-  o.total = off;
-  return o;
-}
-
-__device__ __forceinline__ void mmp_encode(const MMComposeDims& D, const double* x, double* e) {
-  for (int i = 0; i < D.na; ++i) { double sn, cs; sincos(x[D.active[i]], &sn, &cs); e[i] = sn; e[D.na + i] = cs; }
-  for (int i = 0; i < D.nb; ++i) e[2 * D.na + i] = x[D.inactive[i]];
-}
-// adjoint of the encoder: ge [ne] -> gx [nx] (ACCUMULATED)
-__device__ __forceinline__ void mmp_encode_bwd(const MMComposeDims& D, const double* x, const double* ge, double* gx) {
-  for (int i = 0; i < D.na; ++i) {
-    double sn, cs;
-    sincos(x[D.active[i]], &sn, &cs);
-    gx[D.active[i]] += cs * ge[i] - sn * ge[D.na + i];
-  }
-  for (int i = 0; i < D.nb; ++i) gx[D.inactive[i]] += ge[2 * D.na + i];
-}
-// cost = -exp(-err^T W err / 2) of an encoded state; gq != NULL: also d cost / d e (W need not be symmetric)
-__device__ __forceinline__ double mmp_cost(int ne, const double* e, const double* target, const double* precis, double* gq) {
-  double err[MMP_NE], q = 0.0;
-  for (int i = 0; i < ne; ++i) err[i] = e[i] - target[i];
-  for (int i = 0; i < ne; ++i) {
-    double r = 0.0;
-    for (int j = 0; j < ne; ++j) r = fma(precis[i * ne + j], err[j], r);
-    q = fma(err[i], r, q);
-  }
-  const double c = -exp(-0.5 * q);
-  if (gq) {
-    for (int i = 0; i < ne; ++i) {
-      double r = 0.0;
-      for (int j = 0; j < ne; ++j) r = fma(precis[i * ne + j] + precis[j * ne + i], err[j], r);
-      gq[i] = -0.5 * c * r;                                  // d c = -c/2 dq,  dq = err^T (W + W^T) de
-    }
-  }
-  return c;
-}
-
-// policy block in LDS: Z [M][ne] | beta [M] | 1 / ls2 [ne]; var, mean in registers
-struct MMPwPolicy { const double* Z; const double* beta; const double* ils2; double var, mean; int M; };
-
-__device__ __forceinline__ double mmp_policy_mean(int ne, const MMPwPolicy& P, const double* e) {
-  double f = P.mean;
-  for (int m = 0; m < P.M; ++m) {
-    double r2 = 0.0;
-    for (int k = 0; k < ne; ++k) { const double t = e[k] - P.Z[m * ne + k]; r2 = fma(t * t, P.ils2[k], r2); }
-    f = fma(P.beta[m], P.var * exp(-0.5 * r2), f);
-  }
-  return f;
-}
-__device__ __forceinline__ double mmp_ndtr(double x) { return 0.5 * erfc(-x * 0.7071067811865476); }
-
-template <typename T>
-__device__ __forceinline__ void mmp_stage_policy(const double* Zg, const double* bg, const double* ls2g, int M, int ne, double* sm) {
-  for (int i = threadIdx.x; i < M * ne; i += blockDim.x) sm[i] = Zg[i];
-  for (int i = threadIdx.x; i < M; i += blockDim.x) sm[M * ne + i] = bg[i];
-  for (int i = threadIdx.x; i < ne; i += blockDim.x) sm[M * ne + M + i] = 1.0 / ls2g[i];
-  __syncthreads();
-}
+#include "mm_pathwise_policy_dev.h"
 
 // k_pw_head: grid ceil(S / 256), thread = sample.  h in [0, H]:
 //   h > 0: x_h = x_{h-1} + dt f_{h-1} -> tape; cost[h-1][s] of its encoding;    h < H: the drift input (e_h, u_h) -> tape.
@@ -141,12 +56,6 @@ __global__ __launch_bounds__(256) void k_pw_head(MMComposeDims D, int S, int h, 
     for (int i = 0; i < ne; ++i) din[(size_t)s * nd + i] = (T)e[i];
     din[(size_t)s * nd + ne] = (T)u;
   }
-}
-
-__device__ __forceinline__ double mmp_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // k_pw_policy_bwd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][npar] (ASSIGNED): per wave the
@@ -248,6 +157,12 @@ __global__ __launch_bounds__(256) void k_pw_grad_sum(const double* __restrict__ 
   g_policy[p] = sacc;
 }
 
+int mm_pw_grad_sum_launch(const double* gpart, int nslab, int npar, double* g_policy, hipStream_t s) {
+  hipLaunchKernelGGL(k_pw_grad_sum, dim3((npar + 255) / 256), dim3(256), 0, s, gpart, nslab, npar, g_policy);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 static int mmp_check(int S, int M, int K, int dtype, int H, int nx, int na, const int32_t* active_dims, int policy_M, MMComposeDims& D) {
   if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0) return MM_E_ARG;
   if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
@@ -260,7 +175,7 @@ static inline size_t mmp_head_lds(int pM, int ne) { return (size_t)(pM * ne + pM
 
 extern "C" size_t mm_pathwise_tape_bytes(int S, int H, int nx, int na, int dtype, int with_jacobians) {
   if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx) return 0;
-  return mm_pw_tape_layout(S, H, nx, na, dtype, with_jacobians).total;
+  return mm_pw_tape_layout(S, H, nx, na, 1, dtype, with_jacobians).total;
 }
 
 template <typename T>
@@ -303,7 +218,7 @@ extern "C" int mm_pathwise_policy_rollout(int S, int M, int K, int dtype, int H,
   if (rc) return rc;
   if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !target || !precis ||
       !x0 || !cost || !tape) return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, dtype, with_jacobians);
+  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, 1, dtype, with_jacobians);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(1, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
   if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
@@ -332,7 +247,7 @@ extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, doub
   int rc = mmp_check(S, 1, 1, dtype, H, nx, na, active_dims, policy_M, D);
   if (rc) return rc;
   if (!policy_packed || !target || !precis || !tape || !g_cost || !g_policy || !scratch) return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, dtype, 1);
+  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, 1, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   const int ne = D.ne, npar = policy_M * ne + policy_M + ne + 2;
   if (scratch_bytes < mm_pathwise_backward_scratch_bytes(S, policy_M, ne)) return MM_E_WORKSPACE;

@@ -1,0 +1,323 @@
+// Pathwise policy rollout and its reverse sweep for policies with SEVERAL actions (nu = 1 .. 4) on gfx950 -- the multi-action
+// companion of mm_pathwise_policy.hip (the double pendulum's wiring: nx 4, two angles, two torques).
+//
+// On sample paths the policy is evaluated pointwise, so the head has no cross moments: per sample path s and step h
+//     e   = encoder(x_h)                                                  [sin a, cos a, x_inactive]
+//     u_a = scale_a (Phi(f_a(e)) + shift_a),  a < nu                      f_a: the a-th latent's predictive mean
+//     x_{h+1} = x_h + dt f_s([e, u_0 .. u_{nu-1}])                        nd = ne + nu drift inputs, actions in latent order
+//     cost[h][s] = -exp(-(enc(x_{h+1}) - t)^T W (enc(x_{h+1}) - t) / 2)
+// (the torch composition's forward_sde tensor branch appends the policy's outputs to the encoding in this order).  The weight
+// stream (mm_pathwise_launch and its Jacobian variant) takes any d <= 8 and is used as it is.  New here: the head kernel
+// (k_pw_head_nd), the one-kernel reverse sweep (k_pw_policy_bwd_nd) and their entries.  The policy is an ordinary mm_pack_model
+// pack with L = nu; only its f64 blocks are read (Z64 [L][M][ne], beta64 [L][M], ls2 [L][ne], var [L], meanc [L]).
+//
+// Both kernels are templates in the action count: the loops over the latents unroll, the per-latent constants sit in
+// registers, and with NU = 1 the arithmetic is the one-action kernels' in the same order (outputs bit-equal).
+//
+// LDS of the reverse sweep (doubles per workgroup of four waves): the nu policy blocks nu (M ne + M + ne), target and W
+// (ne + ne^2, + 8 spare), and one gradient slab per wave 4 nu (M ne + M + ne + 2).  The kernel takes a shape when
+//     8 (nu (M ne + M + ne) + ne + ne^2 + 8 + 4 nu (M ne + M + ne + 2))  <=  160 KiB        (MMP_ND_LDS_MAX)
+// -- every shape with M <= 64 and ne + nu <= 8 (largest: nu 4, ne 4, M 64: 52 KB); at M = 256: nu (ne + 1) <= 15, i.e. nu = 1
+// (any ne <= 7), nu = 2 (ne <= 6: the double pendulum, 144 KB), nu = 3 with ne <= 4; not nu = 3 with ne = 5 (M <= 226 fits) and
+// not nu = 4 with ne = 4 (M <= 203 fits).  mm_pathwise_backward_scratch_bytes_nd returns 0 and the entry MM_E_DIM beyond it.
+#include "mm_pathwise_policy_dev.h"
+
+#define MMP_ND_LDS_MAX ((size_t)160 * 1024)
+
+
+// k_pw_head_nd: grid ceil(S / 256), thread = sample.  h in [0, H]:
+//   h > 0: x_h = x_{h-1} + dt f_{h-1} -> tape; cost[h-1][s] of its encoding;    h < H: the drift input (e_h, u_h[nu]) -> tape.
+// LDS: the NU policy blocks one after the other (each Z [M][ne] | beta [M] | 1 / ls2 [ne]), target [ne], W [ne][ne].
+template <typename T, int NU>
+__global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int h, int H, double dt, const T* __restrict__ xprev,
+                                                    const T* __restrict__ f, T* __restrict__ xcur, T* __restrict__ din,
+                                                    T* __restrict__ cost, const T* __restrict__ target,
+                                                    const T* __restrict__ precis, const double* __restrict__ pZ,
+                                                    const double* __restrict__ pbeta, const double* __restrict__ pls2,
+                                                    const double* __restrict__ pvar, const double* __restrict__ pmean, int pM,
+                                                    MMHeadND hd) {
+  extern __shared__ double sm[];
+  const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne;
+  double* pol = sm;                                        // [NU][M ne + M + ne]
+  double* tg = pol + NU * blk;                             // [ne]
+  double* W = tg + ne;                                     // [ne][ne]
+  for (int i = threadIdx.x; i < ne; i += 256) tg[i] = (double)target[i];
+  for (int i = threadIdx.x; i < ne * ne; i += 256) W[i] = (double)precis[i];
+#pragma unroll
+  for (int a = 0; a < NU; ++a)
+    mmp_stage_policy<T>(pZ + (size_t)a * pM * ne, pbeta + (size_t)a * pM, pls2 + (size_t)a * ne, pM, ne, pol + a * blk);
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  double x[MMC_NX], e[MMP_NE];
+  if (h > 0) {
+    for (int i = 0; i < nx; ++i) {
+      x[i] = (double)xprev[(size_t)s * nx + i] + dt * (double)f[(size_t)s * nx + i];   // Euler.step, solvers.py:50-65
+      xcur[(size_t)s * nx + i] = (T)x[i];
+    }
+  } else {
+    for (int i = 0; i < nx; ++i) x[i] = (double)xcur[(size_t)s * nx + i];
+  }
+  // (the state every later step reads is the STORED one: rounded to T once)
+  for (int i = 0; i < nx; ++i) x[i] = (double)(T)x[i];
+  mmp_encode(D, x, e);
+  if (h > 0) cost[(size_t)(h - 1) * S + s] = (T)mmp_cost(ne, e, tg, W, nullptr);
+  if (h < H) {
+    for (int i = 0; i < ne; ++i) din[(size_t)s * nd + i] = (T)e[i];
+#pragma unroll
+    for (int a = 0; a < NU; ++a) {
+      const double* pa = pol + a * blk;
+      const MMPwPolicy P{pa, pa + pM * ne, pa + pM * ne + pM, pvar[a], pmean[a], pM};
+      const double u = hd.scale[a] * (mmp_ndtr(mmp_policy_mean(ne, P, e)) + hd.shift[a]);
+      din[(size_t)s * nd + ne + a] = (T)u;
+    }
+  }
+}
+
+// k_pw_policy_bwd_nd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][NU][npar1] (ASSIGNED): per
+// wave the sum over its 64 samples and all steps of the packed policy's gradient, per latent dZ [M][ne], dbeta [M], dls2 [ne],
+// dvar, dmean (npar1 = M ne + M + ne + 2);  g_x0 [S][nx] (optional).  g_cost [H][S] f64.
+template <typename T, int NU>
+__global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
+                                                          const T* __restrict__ dins, const T* __restrict__ jacs,
+                                                          const double* __restrict__ g_cost, const T* __restrict__ target,
+                                                          const T* __restrict__ precis, const double* __restrict__ pZ,
+                                                          const double* __restrict__ pbeta, const double* __restrict__ pls2,
+                                                          const double* __restrict__ pvar, const double* __restrict__ pmean,
+                                                          int pM, MMHeadND hd, double* __restrict__ gpart,
+                                                          double* __restrict__ g_x0) {
+  extern __shared__ double sm[];
+  const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne, npar1 = blk + 2, npar = NU * npar1;
+  double* pol = sm;
+  double* tg = pol + NU * blk;
+  double* W = tg + ne;
+  double* acc = W + ne * ne;                               // [4 waves][NU][npar1]
+  for (int i = threadIdx.x; i < ne; i += 256) tg[i] = (double)target[i];
+  for (int i = threadIdx.x; i < ne * ne; i += 256) W[i] = (double)precis[i];
+  for (int i = threadIdx.x; i < 4 * npar; i += 256) acc[i] = 0.0;
+#pragma unroll
+  for (int a = 0; a < NU; ++a)
+    mmp_stage_policy<T>(pZ + (size_t)a * pM * ne, pbeta + (size_t)a * pM, pls2 + (size_t)a * ne, pM, ne, pol + a * blk);
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  const bool live = s < S;
+  const int sr = live ? s : S - 1;                         // (idle lanes recompute the last sample with zero adjoints)
+  double var[NU], mean[NU];
+#pragma unroll
+  for (int a = 0; a < NU; ++a) { var[a] = pvar[a]; mean[a] = pmean[a]; }
+  double gx[MMC_NX];
+  for (int i = 0; i < nx; ++i) gx[i] = 0.0;
+  for (int h = H - 1; h >= 0; --h) {
+    double x1[MMC_NX], e1[MMP_NE], ge[MMP_NE];
+    // adjoint of x_{h+1}: what later steps left in gx, plus this step's cost of its encoding
+    for (int i = 0; i < nx; ++i) x1[i] = (double)xs[((size_t)(h + 1) * S + sr) * nx + i];
+    mmp_encode(D, x1, e1);
+    mmp_cost(ne, e1, tg, W, ge);
+    const double gc = live ? g_cost[(size_t)h * S + sr] : 0.0;
+    for (int i = 0; i < ne; ++i) ge[i] *= gc;
+    mmp_encode_bwd(D, x1, ge, gx);
+    // x_{h+1} = x_h + dt f(d_h):  g d = dt J^T g x_{h+1}
+    double gd[MMP_NE + MMC_NU], e[MMP_NE];
+    const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
+    for (int k = 0; k < nd; ++k) {
+      double r = 0.0;
+      for (int i = 0; i < nx; ++i) r = fma((double)J[i * nd + k], gx[i], r);
+      gd[k] = dt * r;
+    }
+    const T* dn = dins + ((size_t)h * S + sr) * nd;
+    for (int i = 0; i < ne; ++i) e[i] = (double)dn[i];
+    for (int k = 0; k < ne; ++k) ge[k] = gd[k];
+#pragma unroll
+    for (int a = 0; a < NU; ++a) {
+      const double* pa = pol + a * blk;
+      const MMPwPolicy P{pa, pa + pM * ne, pa + pM * ne + pM, var[a], mean[a], pM};
+      double* wacc = acc + (wv * NU + a) * npar1;
+      // policy head: u_a = scale_a (Phi(fp) + shift_a);  g fp = g u_a scale_a phi(fp)
+      const double fp = mmp_policy_mean(ne, P, e);
+      const double gfp = gd[ne + a] * hd.scale[a] * 0.3989422804014327 * exp(-0.5 * fp * fp);
+      // policy mean fp = sum_m beta_m var exp(-sum_k (e_k - z_mk)^2 / (2 ls2_k)) + c: parameters (wave sums) and input
+      double gvar = 0.0, gls2[MMP_NE];
+      for (int k = 0; k < ne; ++k) gls2[k] = 0.0;
+      for (int m = 0; m < pM; ++m) {
+        double r2 = 0.0, df[MMP_NE];
+        for (int k = 0; k < ne; ++k) { df[k] = e[k] - P.Z[m * ne + k]; r2 = fma(df[k] * df[k], P.ils2[k], r2); }
+        const double km = exp(-0.5 * r2);                    // k_m / var
+        const double t = gfp * P.beta[m] * P.var * km;       // g fp * beta_m k_m
+        gvar = fma(gfp * P.beta[m], km, gvar);
+        const double sb = mmp_wave_sum(gfp * P.var * km);    // d / d beta_m
+        if (lane == 0) wacc[pM * ne + m] += sb;
+        for (int k = 0; k < ne; ++k) {
+          const double tz = t * df[k] * P.ils2[k];           // d k_m / d z_mk = k_m (e_k - z_mk) / ls2_k = - d k_m / d e_k
+          ge[k] -= tz;
+          gls2[k] = fma(0.5 * tz * df[k], P.ils2[k], gls2[k]);   // d k_m / d ls2_k = k_m (e_k - z_mk)^2 / (2 ls2_k^2)
+          const double sz = mmp_wave_sum(tz);
+          if (lane == 0) wacc[m * ne + k] += sz;
+        }
+      }
+      for (int k = 0; k < ne; ++k) {
+        const double sl = mmp_wave_sum(gls2[k]);
+        if (lane == 0) wacc[pM * ne + pM + k] += sl;
+      }
+      {
+        const double sv = mmp_wave_sum(gvar), sc = mmp_wave_sum(gfp);
+        if (lane == 0) { wacc[pM * ne + pM + ne] += sv; wacc[pM * ne + pM + ne + 1] += sc; }
+      }
+    }
+    // d_h = (enc(x_h), u): adjoint of x_h = that of x_{h+1} (identity part of the Euler step) + the encoder's
+    double x0[MMC_NX];
+    for (int i = 0; i < nx; ++i) x0[i] = (double)xs[((size_t)h * S + sr) * nx + i];
+    mmp_encode_bwd(D, x0, ge, gx);
+  }
+  if (g_x0 && live) for (int i = 0; i < nx; ++i) g_x0[(size_t)s * nx + i] = gx[i];
+  __syncthreads();
+  double* o = gpart + ((size_t)blockIdx.x * 4) * npar;
+  for (int i = threadIdx.x; i < 4 * npar; i += 256) o[i] = acc[i];
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+static inline size_t mmp_nd_head_lds(int pM, int ne, int nu) {
+  return ((size_t)nu * (pM * ne + pM + ne) + ne + ne * ne + 8) * sizeof(double);
+}
+static inline size_t mmp_nd_bwd_lds(int pM, int ne, int nu) {
+  return mmp_nd_head_lds(pM, ne, nu) + (size_t)4 * nu * (pM * ne + pM + ne + 2) * sizeof(double);
+}
+
+// everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions
+static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, int nu, const int32_t* active_dims, int policy_M,
+                        MMComposeDims& D) {
+  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || !active_dims) return MM_E_ARG;
+  if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
+  const int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
+  if (rc) return rc;
+  if (D.nd > 8 || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;   // the Jacobian pass of the weight stream: nd <= 8
+  return 0;
+}
+
+extern "C" size_t mm_pathwise_tape_bytes_nd(int S, int H, int nx, int na, int nu, int dtype, int with_jacobians) {
+  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return 0;
+  return mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians).total;
+}
+
+#define MMP_ND_DISPATCH(nu_, M_)                                                       \
+  switch (nu_) {                                                                       \
+    case 1: M_(1); break;                                                              \
+    case 2: M_(2); break;                                                              \
+    case 3: M_(3); break;                                                              \
+    default: M_(4); break;                                                             \
+  }
+
+template <typename T>
+static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K, int dtype, int H, double dt, const void* omega_t,
+                            const void* phase, const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                            const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
+                            int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
+                            char* tape, const MMPwTapeLayout& tl, hipStream_t s) {
+  const int nx = D.nx, ne = D.ne, nd = D.nd;
+  T* xs = (T*)(tape + tl.x); T* dins = (T*)(tape + tl.din); T* f = (T*)(tape + tl.f);
+  T* jac = tl.jac != tl.total ? (T*)(tape + tl.jac) : nullptr;
+  hipError_t e = hipMemcpyAsync(xs, x0, (size_t)S * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return (int)e;
+  const size_t lds = mmp_nd_head_lds(policy_M, ne, nu);
+  const dim3 grid((S + 255) / 256);
+  for (int h = 0; h <= H; ++h) {
+#define MMP_HEAD(NU_)                                                                                                            \
+    hipLaunchKernelGGL((k_pw_head_nd<T, NU_>), grid, dim3(256), lds, s, D, S, h, H, dt,                                          \
+                       h > 0 ? xs + (size_t)(h - 1) * S * nx : (const T*)nullptr, (const T*)f, xs + (size_t)h * S * nx,          \
+                       h < H ? dins + (size_t)h * S * nd : (T*)nullptr, cost, target, precis, (const double*)(pp + pl.Z64),      \
+                       (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),              \
+                       (const double*)(pp + pl.meanc), policy_M, hd)
+    MMP_ND_DISPATCH(nu, MMP_HEAD)
+#undef MMP_HEAD
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (h == H) break;
+    const int rc = mm_pathwise_launch(S, nx, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
+                                      prior_scale, variance, mean_c, wb, f, jac ? jac + (size_t)h * S * nx * nd : nullptr, s);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mm_pathwise_policy_rollout_nd(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                                             const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                                             const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                                             const double* variance, const double* mean_c, const void* wb,
+                                             const void* policy_packed, size_t policy_bytes, int policy_M,
+                                             const double* head_scale, const double* head_shift, const void* target,
+                                             const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                             int with_jacobians, void* stream) {
+  MMComposeDims D;
+  int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, D);
+  if (rc) return rc;
+  if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !head_scale ||
+      !head_shift || !target || !precis || !x0 || !cost || !tape) return MM_E_ARG;
+  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians);
+  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  const MMModelLayout pl = mm_model_layout(nu, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
+  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  MMHeadND hd;
+  for (int a = 0; a < MMC_NU; ++a) { hd.scale[a] = a < nu ? head_scale[a] : 0.0; hd.shift[a] = a < nu ? head_shift[a] : 0.0; }
+  const char* pp = (const char*)policy_packed;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MM_F64)
+    return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
+                                    wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
+                                    (double*)cost, (char*)tape, tl, s);
+  return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
+                                 pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
+                                 (char*)tape, tl, s);
+}
+
+// 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)
+extern "C" size_t mm_pathwise_backward_scratch_bytes_nd(int S, int policy_M, int ne, int nu) {
+  if (S <= 0 || policy_M <= 0 || policy_M > MMP_POLICY_MMAX || ne <= 0 || nu < 1 || nu > MMC_NU || ne + nu > 8) return 0;
+  if (mmp_nd_bwd_lds(policy_M, ne, nu) > MMP_ND_LDS_MAX) return 0;
+  return (size_t)((S + 255) / 256) * 4 * (size_t)nu * (size_t)(policy_M * ne + policy_M + ne + 2) * sizeof(double);
+}
+
+extern "C" int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, double dt, int nx, int na,
+                                                      const int32_t* active_dims, int nu, const void* policy_packed,
+                                                      size_t policy_bytes, int policy_M, const double* head_scale,
+                                                      const double* head_shift, const void* target, const void* precis,
+                                                      const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
+                                                      void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+  MMComposeDims D;
+  int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, D);
+  if (rc) return rc;
+  if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape || !g_cost || !g_policy || !scratch)
+    return MM_E_ARG;
+  const int ne = D.ne, npar = nu * (policy_M * ne + policy_M + ne + 2);
+  const size_t lds = mmp_nd_bwd_lds(policy_M, ne, nu);
+  if (lds > MMP_ND_LDS_MAX) return MM_E_DIM;
+  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, nu, dtype, 1);
+  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  if (scratch_bytes < mm_pathwise_backward_scratch_bytes_nd(S, policy_M, ne, nu)) return MM_E_WORKSPACE;
+  const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, MM_F64, 1);
+  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  MMHeadND hd;
+  for (int a = 0; a < MMC_NU; ++a) { hd.scale[a] = a < nu ? head_scale[a] : 0.0; hd.shift[a] = a < nu ? head_shift[a] : 0.0; }
+  const char* pp = (const char*)policy_packed; const char* tp = (const char*)tape;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((S + 255) / 256);
+#define MMP_BWD(T_, NU_)                                                                                                          \
+  do {                                                                                                                          \
+    if (lds > 64 * 1024) {                                                                                                      \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                          (int)lds);                                                                            \
+      if (ea != hipSuccess) return (int)ea;                                                                                     \
+    }                                                                                                                           \
+    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),              \
+                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const T_*)target,            \
+                       (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),                        \
+                       (const double*)(pp + pl.ls2), (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M, hd, \
+                       (double*)scratch, (double*)g_x0);                                                                        \
+  } while (0)
+#define MMP_BWD_F64(NU_) MMP_BWD(double, NU_)
+#define MMP_BWD_F32(NU_) MMP_BWD(float, NU_)
+  if (dtype == MM_F64) { MMP_ND_DISPATCH(nu, MMP_BWD_F64) } else { MMP_ND_DISPATCH(nu, MMP_BWD_F32) }
+#undef MMP_BWD_F64
+#undef MMP_BWD_F32
+#undef MMP_BWD
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  return mm_pw_grad_sum_launch((const double*)scratch, (int)grid.x * 4, npar, (double*)g_policy, s);
+}

@@ -355,7 +355,7 @@ class GraphedPolicyLoss:
 
 def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable, num_steps: int,
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
-                                 generator: Optional[torch.Generator] = None) -> Callable:
+                                 generator: Optional[torch.Generator] = None, native_actions: int = 1) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -369,7 +369,13 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   rollout (csrc/mm_pathwise_policy.hip): forward only when nothing requires a gradient, else ONE differentiable op
   (``pathwise.PolicyRolloutFunction``: the stream pass also emits the paths' Jacobians, the reverse sweep is one kernel).
   Otherwise -- ``native=False``, another wiring, a gradient the native sweep does not cover -- the torch composition through
-  ``DynamicalSystem.solve_forward`` runs, saying so once (the paths stay on the device and are differentiable in x)."""
+  ``DynamicalSystem.solve_forward`` runs, saying so once (the paths stay on the device and are differentiable in x).
+
+  ``native_actions``: the largest number of actions the closure may run natively.  The default 1 keeps a policy with several
+  actions on the torch composition (with the "nu > 1" warning; ``native=True`` raises).  With ``native_actions >= nu`` such a
+  policy runs in the multi-action native rollout (csrc/mm_pathwise_policy_nd.hip), forward and gradient, where
+  nx + na + nu <= 8, the policy has <= 256 centres and -- when a gradient is asked for -- the reverse sweep takes the shape
+  (``PolicyRollout.supports_backward``); every other case falls back and names its reason."""
   from . import ops
   from .pathwise import PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
   drift = system.drift
@@ -380,8 +386,10 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False)
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
-  if native is True and parts[1].num_latent_gps > 1:
-    raise ValueError("native=True: the native pathwise rollout is one-action")
+  max_native = int(native_actions)
+  if native is True and parts[1].num_latent_gps > max(1, max_native):
+    raise ValueError("native=True: the native pathwise rollout is one-action" if max_native <= 1 else
+                     f"native=True: the policy has {parts[1].num_latent_gps} actions, native_actions={max_native}")
   warned = []
 
   def _fallback(reason):
@@ -413,11 +421,18 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       return _torch_loss(x0, pth)
     enc, pm_, _, bj, head_constants = parts
     nx, na = x0.shape[-1], len(enc.active_dims)
-    if pm_.num_latent_gps > 1:
-      _fallback(f"the policy has nu = {pm_.num_latent_gps} actions (nu > 1: the native pathwise rollout is one-action)")
+    nu = int(pm_.num_latent_gps)
+    if nu > max(1, max_native):
+      _fallback(f"the policy has nu = {nu} actions (nu > 1: the native pathwise rollout is one-action)" if max_native <= 1 else
+                f"the policy has nu = {nu} actions (nu > 1) and native_actions = {max_native}")
       return _torch_loss(x0, pth)
-    if nx + na + 1 > 8 or pm_.inducing_variable.inducing_variables[0].Z.shape[0] > 256:
-      _fallback("drift inputs of dimension > 8 or a policy of more than 256 centres")
+    pol_M = max(iv.Z.shape[0] for iv in pm_.inducing_variable.inducing_variables[:nu])
+    if nu == 1:
+      if nx + na + 1 > 8 or pol_M > 256:
+        _fallback("drift inputs of dimension > 8 or a policy of more than 256 centres")
+        return _torch_loss(x0, pth)
+    elif nx + na + nu > 8 or pol_M > 256:
+      _fallback(f"drift inputs of dimension nx + na + nu = {nx + na + nu} > 8 or a policy of more than 256 centres ({pol_M})")
       return _torch_loss(x0, pth)
     outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
                "objective.target": objective.target, "objective.precis": objective.precis}
@@ -432,13 +447,16 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     roll = PolicyRollout(pth, pol_pack, nx=nx, active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
                          target=objective.target, precis=objective.precis)
     needs = grad and (x0.requires_grad or any(t.requires_grad for t in pm_._parameters()))
+    if needs and not roll.supports_backward():
+      _fallback(f"the native reverse sweep does not take nu = {nu} actions with {pol_M} centres on {nx + na} inputs (its LDS bound)")
+      return _torch_loss(x0, pth)
     if not needs:
       with torch.no_grad():
         cost, _ = roll(x0, H, dt=dt)
       return cost.sum(0)
     Zp, lsp, varp, betap, _, mcp = pm_.precompute(x0.device)
     if mcp is None:
-      mcp = torch.zeros(1, dtype=Zp.dtype, device=x0.device)
+      mcp = torch.zeros(nu, dtype=Zp.dtype, device=x0.device)
     return PolicyRolloutFunction.apply(x0, Zp, lsp, varp, betap, mcp, roll, H, dt).sum(1).to(x0.dtype)
 
   return _closure

@@ -242,27 +242,54 @@ class PathwiseSVGP(SVGP):
 
 
 class PolicyRollout:
-  """The pathwise policy rollout on the device (``mm_pathwise_policy_rollout``, csrc/mm_pathwise_policy.hip): per sample path
-  encoder -> policy mean through Chain[Scale, Shift, NormalCDF] -> drift sample -> Euler -> cost -- the body of
-  ``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).
+  """The pathwise policy rollout on the device (``mm_pathwise_policy_rollout``, csrc/mm_pathwise_policy.hip; several actions:
+  ``mm_pathwise_policy_rollout_nd``, csrc/mm_pathwise_policy_nd.hip): per sample path encoder -> policy mean through
+  Chain[Scale, Shift, NormalCDF] -> drift sample -> Euler -> cost -- the body of ``PathwisePILCO._policy_loss_closure``
+  (gpflow_pilco/loops/pilco.py:263-298).
 
-  ``paths``: the drift's sample paths (nx latents on nd = nx + na + 1 inputs, nd <= 8); ``policy``: a one-latent
-  ``ops.PackedModel`` on ne = nx + na inputs (any dtype: only its float64 blocks are read).  ``__call__(x0, H)`` ->
-  ``(cost [H, S], tape)``; ``backward(tape, g_cost)`` -> ``(g_policy [M ne + M + ne + 2], g_x0 [S, nx] | None)``."""
+  ``paths``: the drift's sample paths (nx latents on nd = nx + na + nu inputs, nd <= 8); ``policy``: an ``ops.PackedModel`` with
+  one latent per action (nu = 1 .. 4) on ne = nx + na inputs (any dtype: only its float64 blocks are read); ``head_scale`` /
+  ``head_shift``: a float, or one value per action.  The actions follow the encoding in latent order.  A one-latent pack with
+  float head constants runs the one-action entries; nu > 1 (or ``nd_entries=True``) the ``_nd`` entries.
+  ``__call__(x0, H)`` -> ``(cost [H, S], tape)``; ``backward(tape, g_cost)`` -> ``(g_policy, g_x0 [S, nx] | None)`` with
+  g_policy [M ne + M + ne + 2] from the one-action entries and [nu, M ne + M + ne + 2] from the ``_nd`` ones (per latent dZ,
+  dbeta, d ls^2, dvar, dmean).  ``supports_backward()``: whether the reverse sweep takes this shape (its LDS bound:
+  include/gpflowpilco_mm.h)."""
 
-  def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale: float, head_shift: float,
-               target: torch.Tensor, precis: torch.Tensor):
+  def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
+               target: torch.Tensor, precis: torch.Tensor, nd_entries: Optional[bool] = None):
     S, L, Mp, Kp, d = paths._dims()
     self.paths, self.policy = paths, policy
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
     self.na = len(self.active)
-    self.ne, self.nd = self.nx + self.na, self.nx + self.na + 1
-    if L != self.nx or d != self.nd or policy.L != 1 or policy.d != self.ne:
+    self.nu = int(policy.L)
+    self.ne, self.nd = self.nx + self.na, self.nx + self.na + self.nu
+    if not 1 <= self.nu <= 4:
+      raise ValueError(f"the pathwise policy rollout takes policies with 1 to 4 latents (one per action), got {self.nu}")
+    if L != self.nx or d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: paths L={L} d={d} (want {self.nx}, {self.nd}), policy L={policy.L} d={policy.d} "
-                       f"(want 1, {self.ne})")
+                       f"(want {self.nu}, {self.ne})")
     if self.nd > 8 or policy.M > 256:
       raise ValueError("the pathwise policy rollout takes drift inputs of dimension <= 8 and policies of <= 256 centres")
-    self.scale, self.shift = float(head_scale), float(head_shift)
+
+    def per_action(v, what):
+      if isinstance(v, torch.Tensor):
+        v = v.detach().reshape(-1).tolist()
+      vals = tuple(float(t) for t in v) if isinstance(v, (list, tuple)) else (float(v),) * self.nu
+      if len(vals) == 1 and self.nu > 1:
+        vals = vals * self.nu
+      if len(vals) != self.nu:
+        raise ValueError(f"{what}: expected a float or one value per action ({self.nu}), got {len(vals)}")
+      return vals
+    scales, shifts = per_action(head_scale, "head_scale"), per_action(head_shift, "head_shift")
+    self.nd_entries = (self.nu > 1) if nd_entries is None else bool(nd_entries)
+    if self.nu > 1 and not self.nd_entries:
+      raise ValueError("nd_entries=False: the one-action entries take one-latent policies")
+    if self.nd_entries:
+      self.scale, self.shift = scales, shifts
+      self._scale_c, self._shift_c = (_lib.C.c_double * self.nu)(*scales), (_lib.C.c_double * self.nu)(*shifts)
+    else:
+      self.scale, self.shift = scales[0], shifts[0]
     self.target = target.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
     self.precis = precis.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
@@ -273,6 +300,10 @@ class PolicyRollout:
       raise ValueError("the policy pack does not have the shape this rollout was built for")
     return pol
 
+  def supports_backward(self) -> bool:
+    """False where the reverse sweep's per-workgroup LDS (the nu policy blocks + four gradient slabs) exceeds 160 KiB."""
+    return _lib.lib().mm_pathwise_backward_scratch_bytes_nd(self.paths.num_samples, self.policy.M, self.ne, self.nu) > 0
+
   def __call__(self, x0: torch.Tensor, num_steps: int, dt: float = 1.0, with_jacobians: bool = False, policy=None):
     pol = self._policy(policy)
     P = self.paths
@@ -281,19 +312,33 @@ class PolicyRollout:
     if x0.shape != (S, self.nx) or x0.dtype != P.dtype:
       raise ValueError(f"expected x0 [{S},{self.nx}] of {P.dtype}, got {tuple(x0.shape)} {x0.dtype}")
     H, code = int(num_steps), _dtype_code(P.dtype)
-    n = _lib.lib().mm_pathwise_tape_bytes(S, H, self.nx, self.na, code, int(with_jacobians))
+    lib = _lib.lib()
+    if self.nd_entries:
+      n = lib.mm_pathwise_tape_bytes_nd(S, H, self.nx, self.na, self.nu, code, int(with_jacobians))
+    else:
+      n = lib.mm_pathwise_tape_bytes(S, H, self.nx, self.na, code, int(with_jacobians))
     if n == 0:
       raise ValueError("mm_pathwise_tape_bytes rejected the shape")
     tape = torch.empty(n, dtype=torch.uint8, device=x0.device)
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
-    rc = _lib.lib().mm_pathwise_policy_rollout(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act,
-                                               P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
-                                               P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
-                                               _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
-                                               self.scale, self.shift, self.target.data_ptr(), self.precis.data_ptr(),
-                                               x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                                               int(with_jacobians), _stream(x0.device))
+    if self.nd_entries:
+      rc = lib.mm_pathwise_policy_rollout_nd(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
+                                             P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
+                                             P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
+                                             _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
+                                             self._scale_c, self._shift_c, self.target.data_ptr(), self.precis.data_ptr(),
+                                             x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
+                                             int(with_jacobians), _stream(x0.device))
+      check(rc, "mm_pathwise_policy_rollout_nd")
+      return cost, tape
+    rc = lib.mm_pathwise_policy_rollout(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act,
+                                        P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
+                                        P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
+                                        _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
+                                        self.scale, self.shift, self.target.data_ptr(), self.precis.data_ptr(),
+                                        x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
+                                        int(with_jacobians), _stream(x0.device))
     check(rc, "mm_pathwise_policy_rollout")
     return cost, tape
 
@@ -313,24 +358,39 @@ class PolicyRollout:
     if g_cost.shape != (H, S):
       raise ValueError(f"g_cost must be [H={H}, S={S}]")
     npar = pol.M * self.ne + pol.M + self.ne + 2
-    g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
-    ns = _lib.lib().mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
+    lib = _lib.lib()
+    if self.nd_entries:
+      ns = lib.mm_pathwise_backward_scratch_bytes_nd(S, pol.M, self.ne, self.nu)
+      if ns == 0:
+        raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
+                         "slabs exceed 160 KiB of LDS (see supports_backward)")
+      g_pol = torch.empty(self.nu, npar, dtype=torch.float64, device=dev)
+      scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
+      rc = lib.mm_pathwise_policy_rollout_backward_nd(S, code, H, float(dt), self.nx, self.na, self._act, self.nu,
+                                                      pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c,
+                                                      self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(),
+                                                      tape.numel(), g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0),
+                                                      scratch.data_ptr(), scratch.numel(), _stream(dev))
+      check(rc, "mm_pathwise_policy_rollout_backward_nd")
+      return g_pol, g_x0
+    g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
+    ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
     scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
-    rc = _lib.lib().mm_pathwise_policy_rollout_backward(S, code, H, float(dt), self.nx, self.na, self._act, pol.buf.data_ptr(),
-                                                        pol.nbytes, pol.M, self.scale, self.shift, self.target.data_ptr(),
-                                                        self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
-                                                        g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
-                                                        scratch.numel(), _stream(dev))
+    rc = lib.mm_pathwise_policy_rollout_backward(S, code, H, float(dt), self.nx, self.na, self._act, pol.buf.data_ptr(),
+                                                 pol.nbytes, pol.M, self.scale, self.shift, self.target.data_ptr(),
+                                                 self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
+                                                 g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
+                                                 scratch.numel(), _stream(dev))
     check(rc, "mm_pathwise_policy_rollout_backward")
     return g_pol, g_x0
 
 
 class PolicyRolloutFunction(torch.autograd.Function):
   """The pathwise policy loss as ONE differentiable op: forward = ``mm_pathwise_policy_rollout`` with the Jacobian tape,
-  backward = ``mm_pathwise_policy_rollout_backward``.  The policy enters in packed coordinates (Z [1,M,ne], lengthscales
-  [1,ne], variance [1], beta [1,M], mean_c [1]) computed from its parameters by differentiable torch ops, as in
-  ``autodiff.ComposedRolloutFunction``.  Output: cost [S, H]."""
+  backward = ``mm_pathwise_policy_rollout_backward`` (several actions: the ``_nd`` entries).  The policy enters in packed
+  coordinates with a leading latent axis (Z [nu,M,ne], lengthscales [nu,ne], variance [nu], beta [nu,M], mean_c [nu]) computed from
+  its parameters by differentiable torch ops, as in ``autodiff.ComposedRolloutFunction``.  Output: cost [S, H]."""
 
   @staticmethod
   def forward(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt):
@@ -352,9 +412,10 @@ class PolicyRolloutFunction(torch.autograd.Function):
     g, g_x0 = ctx.roll.backward(ctx.tape, g_cost.T.contiguous(), ctx.H, dt=ctx.dt, policy=ctx.pol, want_state_grad=ctx.need_state)
     M, d = ctx.pol.M, ctx.pol.d
     zs, lss, vs, bs, ms = ctx.shapes
-    gZ = g[:M * d].reshape(zs)
-    gbeta = g[M * d:M * d + M].reshape(bs)
-    gls = (2.0 * ls.detach().reshape(-1) * g[M * d + M:M * d + M + d]).reshape(lss)        # d/d ls = 2 ls d/d ls^2
-    gvar = g[M * d + M + d].reshape(vs)
-    gmean = g[M * d + M + d + 1].reshape(ms)
+    g = g.reshape(ctx.pol.L, -1)                                                           # per latent: dZ, dbeta, d ls^2, dvar, dmean
+    gZ = g[:, :M * d].reshape(zs)
+    gbeta = g[:, M * d:M * d + M].reshape(bs)
+    gls = (2.0 * ls.detach().reshape(-1, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)  # d/d ls = 2 ls d/d ls^2
+    gvar = g[:, M * d + M + d].reshape(vs)
+    gmean = g[:, M * d + M + d + 1].reshape(ms)
     return (None if g_x0 is None else g_x0.to(ctx.x_dtype)), gZ, gls, gvar, gbeta, gmean, None, None, None

@@ -386,6 +386,38 @@ int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, double dt, int 
                                         const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                         void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the same for policies with SEVERAL actions (csrc/mm_pathwise_policy_nd.hip): 1 <= nu <= 4 ------------------------------
+ * On sample paths the policy is evaluated pointwise, so its nu actions are nu independent heads appended to the encoding in
+ * latent order: u_a = head_scale[a] (Phi(f_a(e)) + head_shift[a]), drift input d = (e, u_0 .. u_{nu-1}), nd = nx + na + nu <= 8
+ * (the double pendulum: nx 4, two angles, two torques -> nd = 8).  The policy is an mm_pack_model pack with L = nu latents
+ * (M <= 256 centres each on ne = nx + na inputs; only its f64 blocks are read); head_scale, head_shift: HOST arrays [nu].
+ * Everything else -- operands, tape (with nd = nx + na + nu), g_cost, g_x0 -- as in the one-action entries above;
+ * g_policy [nu][M ne + M + ne + 2] f64: per latent dZ, dbeta, d ls^2, dvar, dmean.  With nu = 1 the size queries return the
+ * one-action sizes and the rollout, the tape and the gradients equal the one-action entries' bit for bit.
+ * Refused before any HIP call: nu outside 1..4, nx + na + nu > 8 or policy_M > 256 (MM_E_DIM); a null pointer (MM_E_ARG); a dtype
+ * other than MM_F32 / MM_F64 (MM_E_DTYPE); a short tape, policy buffer or scratch (MM_E_WORKSPACE).
+ * The reverse sweep keeps the nu policy blocks and one gradient slab per wave in LDS and takes a shape when
+ *   8 (nu (M ne + M + ne) + ne + ne^2 + 8 + 4 nu (M ne + M + ne + 2)) <= 160 KiB:
+ * every shape with M <= 64; at M = 256 nu = 1, nu = 2 (ne <= 6: 144 KB) and nu = 3 with ne <= 4, but not nu = 3 with ne = 5
+ * (M <= 226) or nu = 4 with ne = 4 (M <= 203).  Beyond it mm_pathwise_backward_scratch_bytes_nd returns 0 (as for any shape the
+ * entry refuses) and mm_pathwise_policy_rollout_backward_nd MM_E_DIM; the forward entry has no such bound. */
+size_t mm_pathwise_tape_bytes_nd(int S, int H, int nx, int na, int nu, int dtype, int with_jacobians);
+int mm_pathwise_policy_rollout_nd(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                  int nu, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                                  const double* x_scale, const double* prior_scale, const double* variance,
+                                  const double* mean_c, const void* wb,
+                                  const void* policy_packed, size_t policy_bytes, int policy_M,
+                                  const double* head_scale, const double* head_shift,
+                                  const void* target, const void* precis, const void* x0, void* cost,
+                                  void* tape, size_t tape_bytes, int with_jacobians, void* stream);
+size_t mm_pathwise_backward_scratch_bytes_nd(int S, int policy_M, int ne, int nu);
+int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                           int nu, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                           const double* head_scale, const double* head_shift,
+                                           const void* target, const void* precis,
+                                           const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
+                                           void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,17 @@
 Device events around `inner` back-to-back rollouts of H steps, after warm-up; `repeats` windows; the median and the
 min .. max spread of the windows are reported, in ms per step.  ``--one-action-only`` times only the one-action rollout: run
 from the root of ANOTHER checkout (the package is imported from the current directory when it holds one) it gives that
-checkout's numbers for the unchanged path.  Prints one JSON line."""
+checkout's numbers for the unchanged path.  Prints one JSON line.
+
+``--pathwise``: the pathwise (sample-path) policy loss instead -- loops.pathwise_policy_loss_closure at the C5 shard's sizes (drift
+M = 2000, K = 1024 bases, policy M = 30, S = 8192 paths, H = 30), f32 and f64 paths, ms per step of
+  two actions (nx = 4, two angles, nd = 8): native forward and native loss + gradient (native_actions=2), and the torch
+    composition's forward and loss + gradient (native=False) on the same paths (float64 paths only: the torch composition
+    evaluates the float64 policy models);
+  one action (cartpole: nx = 4, one angle, nd = 6) through the existing entries, same four figures, same process: the yardstick.
+The variants of one shape are timed in alternation (window r of every variant before window r + 1 of any).  ``--samples`` /
+``--drift-M`` shrink the shape for a dry run; ``--native-only`` leaves the torch composition out (the run to put under
+``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv)."""
 import argparse
 import json
 import os
@@ -67,6 +77,98 @@ def windows(fn, H, inner, repeats, warmup):
           "rollouts_per_window": inner}
 
 
+def alternating(fns, H, inner, repeats, warmup):
+  """{name: ms-per-step stats}: device events around `inner` back-to-back calls; the variants take turns window by window."""
+  for fn in fns.values():
+    for _ in range(warmup):
+      fn()
+  torch.cuda.synchronize()
+  out = {k: [] for k in fns}
+  for _ in range(repeats):
+    for k, fn in fns.items():
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(inner):
+        fn()
+      e1.record()
+      e1.synchronize()
+      out[k].append(e0.elapsed_time(e1) / (inner * H))
+  return {k: {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "windows": len(v),
+              "calls_per_window": inner} for k, v in out.items()}
+
+
+def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True):
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  from gpflowpilco_amd.pathwise import PathwiseSVGP
+  na = len(active); ne = nx + na; nd = ne + nu
+  base = make_svgp(nx, Md, nd, seed=seed, device=device, ls_bounds=(0.8, 3.0)).to_model(device)
+  drift = PathwiseSVGP(kernel=base.kernel, inducing_variable=base.inducing_variable, q_mu=base.q_mu, q_sqrt=base.q_sqrt, whiten=True,
+                       num_latent_gps=nx)
+  pol_o = random_svgp_params(seed=seed + 1, L=nu, M=30, d=ne, whiten=True, ls_bounds=(0.8, 2.0), mean=True, separate_Z=True)
+  pol_o.q_mu = 0.3 * pol_o.q_mu
+  pol = gp_model_from_oracle(pol_o, device)
+  if nu == 1:
+    head = tfb.Chain([tfb.Scale(SCALE[0]), tfb.Shift(SHIFT[0]), tfb.NormalCDF()])
+  else:
+    head = tfb.Chain([tfb.Scale(to_dev(SCALE[:nu], device, F64)), tfb.Shift(to_dev(SHIFT[:nu], device, F64)), tfb.NormalCDF()])
+  system = dynamics.DynamicalSystem(drift=drift, policy=gp.InverseLinkWrapper(gp.KernelRegressor(pol), invlink=head),
+                                    encoder=TrigonometricEncoder(active_dims=active), solver=dynamics.Euler())
+  target = np.zeros(ne); target[na:2 * na] = 1.0
+  objective = GaussianObjective(target=to_dev(target, device, dtype), precis=to_dev(np.eye(ne), device, dtype))
+  g = torch.Generator(device=device).manual_seed(seed + 2)
+  x0 = 0.2 + 0.6 * torch.rand(S, nx, dtype=dtype, device=device, generator=g)
+  paths = drift.generate_paths(S, K, dtype=dtype, device=device, generator=g)
+  ks = pol.kernel.kernels
+  params = [pol.q_mu] + [iv.Z for iv in pol.inducing_variable.inducing_variables] + [k.lengthscales for k in ks] + [k.variance for k in ks]
+  for t in params:
+    t.requires_grad_(True)
+  native = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=True, native_actions=nu)
+  composed = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=False)
+
+  def forward(closure):
+    def run():
+      with torch.no_grad():
+        return closure()
+    return run
+
+  def loss_grad(closure):
+    def run():
+      for t in params:
+        t.grad = None
+      loss = closure().mean()
+      loss.backward()
+      return loss
+    return run
+  fns = {"native_forward": forward(native), "native_loss_and_grad": loss_grad(native)}
+  kinds = ["native"]
+  if with_torch and dtype == F64:          # (the torch composition evaluates the float64 policy models: it composes with float64 paths only)
+    fns.update({"torch_forward": forward(composed), "torch_loss_and_grad": loss_grad(composed)})
+    kinds.append("torch")
+  losses = {k: float(fns[f"{k}_loss_and_grad"]().detach()) for k in kinds}
+  res = alternating(fns, H, inner, repeats, 1)
+  res["mean_loss"] = losses
+  res["shape"] = {"nx": nx, "na": na, "nu": nu, "nd": nd, "drift_M": Md, "K": K, "policy_M": 30, "S": S, "H": H}
+  for k in kinds:
+    res[f"{k}_loss_and_grad_over_forward"] = res[f"{k}_loss_and_grad"]["median"] / res[f"{k}_forward"]["median"]
+  if "torch" in kinds:
+    res["torch_over_native_loss_and_grad"] = res["torch_loss_and_grad"]["median"] / res["native_loss_and_grad"]["median"]
+    res["torch_over_native_forward"] = res["torch_forward"]["median"] / res["native_forward"]["median"]
+  return res
+
+
+def main_pathwise(args):
+  device = "cuda"
+  res = {"tool": "bench_multiaction --pathwise", "label": args.label, "unit": "ms per step, eager"}
+  for nm, dtype in (("f32", torch.float32), ("f64", F64)):
+    res[nm] = {
+        "two_actions": pathwise_shape(4, (0, 1), 2, args.drift_M, 1024, args.samples, args.steps, dtype, 40, device, args.inner,
+                                      args.repeats, not args.native_only),
+        "one_action": pathwise_shape(4, (1,), 1, args.drift_M, 1024, args.samples, args.steps, dtype, 3, device, args.inner,
+                                     args.repeats, not args.native_only)}
+    torch.cuda.empty_cache()
+  print(json.dumps(res))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--steps", type=int, default=30)
@@ -74,9 +176,15 @@ def main():
   ap.add_argument("--inner", type=int, default=40)
   ap.add_argument("--one-action-only", action="store_true")
   ap.add_argument("--label", default="")
+  ap.add_argument("--pathwise", action="store_true")
+  ap.add_argument("--native-only", action="store_true", help="--pathwise without the torch composition (for a kernel trace)")
+  ap.add_argument("--samples", type=int, default=8192)
+  ap.add_argument("--drift-M", type=int, default=2000)
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit("bench_multiaction.py needs the GPU (no CPU timing is meaningful)")
+  if args.pathwise:
+    return main_pathwise(args)
   device = "cuda"
   H = args.steps
   res = {"tool": "bench_multiaction", "label": args.label, "H": H, "unit": "ms per step, f64, eager",
