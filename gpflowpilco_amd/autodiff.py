@@ -453,3 +453,39 @@ class ComposedRolloutFunction(torch.autograd.Function):
     gvar = g[M * d + M + d].reshape(vs)
     gmean = g[M * d + M + d + 1].reshape(ms)
     return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
+
+
+class ComposedRolloutNDFunction(torch.autograd.Function):
+  """``ComposedRolloutFunction`` for a policy with nu = 1..4 actions: forward = ``mm_rollout_composed_taped_nd``, backward =
+  ``mm_rollout_composed_backward_nd`` (csrc/mm_compose_bwd_nd.hip).
+
+  The packed coordinates carry a leading latent axis -- Z [nu,M,d], lengthscales [nu,d], variance [nu], beta [nu,M],
+  mean_c [nu] -- and ``g_policy`` comes back per latent; d/d lengthscales = 2 ls . d/d ls^2 per latent.  The drift and the
+  head's scale / shift are constants.  Output: cost [B, H]."""
+
+  @staticmethod
+  def forward(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
+    f64 = torch.float64
+    det = lambda t: t.detach().to(f64)
+    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
+    m_H, S_H, cost, tape = roll.taped_nd(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
+    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
+    ctx.save_for_backward(ls)
+    ctx.need_state = mx.requires_grad or Sxx.requires_grad
+    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+    return cost.T.contiguous()
+
+  @staticmethod
+  def backward(ctx, g_cost):
+    (ls,) = ctx.saved_tensors
+    g_pol, g_m, g_S = ctx.roll.backward_nd(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
+                                           want_state_grad=ctx.need_state)
+    nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
+    g = g_pol.sum(0)                                                                        # [nu, M d + M + d + 2]
+    zs, lss, vs, bs, ms = ctx.shapes
+    gZ = g[:, :M * d].reshape(zs)
+    gbeta = g[:, M * d:M * d + M].reshape(bs)
+    gls = (2.0 * ls.detach().reshape(nu, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)   # d/d ls = 2 ls d/d ls^2
+    gvar = g[:, M * d + M + d].reshape(vs)
+    gmean = g[:, M * d + M + d + 1].reshape(ms)
+    return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None

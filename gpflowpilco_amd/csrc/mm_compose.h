@@ -125,14 +125,15 @@ struct MMTapeLayout {
 // element).  Larger models re-run the q stage from the taped (md, Sdd).
 #define MM_TAPE_WS_LIMIT ((size_t)512 << 20)
 
-static inline MMTapeLayout mm_tape_layout(int B, int H, int nx, int na, int drift_M, int dtype) {
+// slot_bytes: one compose-workspace slot; nd: the drift's input dimension (ne + number of actions)
+static inline MMTapeLayout mm_tape_layout_slots(int B, int H, int nx, int nd, size_t slot_bytes, int drift_M, int dtype) {
   MMTapeLayout o;
   const size_t es = mm_elem_size(dtype), A = 256;
-  o.slot_bytes = mm_compose_layout(B, nx, na, dtype).total;
+  o.slot_bytes = slot_bytes;
   size_t off = (size_t)(H + 1) * o.slot_bytes;
   o.xm = off; off = mm_align_up(off + (size_t)(H + 1) * B * nx * es, A);
   o.xS = off; off = mm_align_up(off + (size_t)(H + 1) * B * nx * nx * es, A);
-  const size_t wsb = mm_align_up(mm_workspace_layout(B, nx, drift_M, nx + na + 1, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY).total, A);
+  const size_t wsb = mm_align_up(mm_workspace_layout(B, nx, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY).total, A);
   o.ws = off; o.ws_stride = 0;
   if (wsb * (size_t)H <= MM_TAPE_WS_LIMIT) { o.ws_stride = wsb; off += wsb * (size_t)H; }
   // ... and, where they fit too, the sums of the drift match's backward sweeps: nothing in them depends on the incoming
@@ -140,13 +141,35 @@ static inline MMTapeLayout mm_tape_layout(int B, int H, int nx, int na, int drif
   // (mm_moment_match_with_sums) and the reverse step is the chain rule alone -- two launches less per step and direction
   o.gp = off; o.gp_stride = 0;
   if (o.ws_stride) {
-    const size_t gpb = mm_align_up(mm_moment_match_backward_bytes_dtype(B, nx, drift_M, nx + na + 1, dtype,
+    const size_t gpb = mm_align_up(mm_moment_match_backward_bytes_dtype(B, nx, drift_M, nd, dtype,
                                                                         MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY), A);
     if (gpb && (wsb + gpb) * (size_t)H <= MM_TAPE_WS_LIMIT) { o.gp_stride = gpb; off += gpb * (size_t)H; }
   }
   o.total = off;
   return o;
 }
+
+static inline MMTapeLayout mm_tape_layout(int B, int H, int nx, int na, int drift_M, int dtype) {
+  return mm_tape_layout_slots(B, H, nx, nx + na + 1, mm_compose_layout(B, nx, na, dtype).total, drift_M, dtype);
+}
+
+// several actions (mm_compose_nd.hip, mm_compose_bwd_nd.hip): slots of mm_compose_layout_nd, the drift on nd = ne + nu dims
+static inline MMTapeLayout mm_tape_layout_nd(int B, int H, int nx, int na, int nu, int drift_M, int dtype) {
+  return mm_tape_layout_slots(B, H, nx, nx + na + nu, mm_compose_layout_nd(B, nx, na, nu, dtype).total, drift_M, dtype);
+}
+
+// mm_compose_bwd.hip: the adjoint of one GP moment match (general in d), shared by the two reverse sweeps.
+//   mode: MMB_MODE_ALL = sweeps + chain rule; MMB_MODE_SWEEPS = everything that does not depend on the incoming gradient;
+//   MMB_MODE_CHAIN = the chain rule alone on sums a MMB_MODE_SWEEPS call left on bwd_ws.
+enum { MMB_MODE_ALL = 0, MMB_MODE_SWEEPS = 1, MMB_MODE_CHAIN = 2 };
+int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B,
+                                  const void* mu, const void* Sigma, int flags,
+                                  const void* g_f1, const void* g_Sff, const void* g_cross,
+                                  void* g_mu, void* g_Sigma, int accumulate_Sigma,
+                                  void* workspace, size_t workspace_bytes, void* bwd_ws, size_t bwd_ws_bytes,
+                                  int32_t* status, void* stream, bool workspace_is_current, bool skip_sum, int mode, bool verify_sums);
+// byte offset, inside the backward buffer of a match, of its (latent | pair) items [B][L + P][d^2 + d] (skip_sum: the consumer sums them)
+size_t mm_gp_bwd_items_offset(int B, int L, int M, int d, int dtype, int flags);
 
 // gradient slab of the packed one-latent policy, per batch element: dZ [M][d], dbeta [M], dls2 [d], dvar, dmean_c
 static inline size_t mm_policy_grad_len(int M, int d) { return (size_t)M * d + M + d + 2; }

@@ -37,8 +37,6 @@ extern "C" void mm_stage_profile_set_bwd(void* device_buffer) {
 #define MMB_PROF_CTX(c_) do {} while (0)
 #endif
 
-enum { MMB_MODE_ALL = 0, MMB_MODE_SWEEPS = 1, MMB_MODE_CHAIN = 2 };
-
 // f32 packs, all stages in one call: the aggregate chain of the off-diagonal pairs (re-reduce of the routed items 0.6 ms + full
 // moment GEMM 0.5 ms + k_pair_agg 1.4 ms at C3 shape: latency-bound, few or short workgroups) runs on a SIDE STREAM beside the diagonal pairs' f64 sweep,
 // which leaves 96 VGPRs per SIMD lane and 112 KB of LDS per CU free: with 256-thread workgroups the chain hides completely
@@ -198,13 +196,16 @@ extern "C" size_t mm_moment_match_backward_bytes_dtype(int B, int L, int M, int 
 // Re-runs the q stage for (mu, Sigma) on `workspace`, then the M x M sweeps, the items and their sum.
 // workspace_is_current: `workspace` already holds the q stage of exactly this (mu, Sigma, flags) -- the reverse sweep of a
 // rollout whose tape kept the drift's workspace per step -- so the q stage is not run again
-static int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B,
-                                         const void* mu, const void* Sigma, int flags,
-                                         const void* g_f1, const void* g_Sff, const void* g_cross,
-                                         void* g_mu, void* g_Sigma, int accumulate_Sigma,
-                                         void* workspace, size_t workspace_bytes, void* bwd_ws, size_t bwd_ws_bytes,
-                                         int32_t* status, void* stream, bool workspace_is_current, bool skip_sum = false,
-                                         int mode = MMB_MODE_ALL, bool verify_sums = true /* check the caller's MM_*_CURRENT promises on the device */) {
+size_t mm_gp_bwd_items_offset(int B, int L, int M, int d, int dtype, int flags) { return mm_gp_bwd_layout(B, L, M, d, dtype, flags).items; }
+
+// (declared in mm_compose.h: the multi-action reverse sweep of mm_compose_bwd_nd.hip runs the drift's adjoint through it too)
+int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B,
+                                  const void* mu, const void* Sigma, int flags,
+                                  const void* g_f1, const void* g_Sff, const void* g_cross,
+                                  void* g_mu, void* g_Sigma, int accumulate_Sigma,
+                                  void* workspace, size_t workspace_bytes, void* bwd_ws, size_t bwd_ws_bytes,
+                                  int32_t* status, void* stream, bool workspace_is_current, bool skip_sum = false,
+                                  int mode = MMB_MODE_ALL, bool verify_sums = true /* check the caller's MM_*_CURRENT promises on the device */) {
   // mode: MMB_MODE_ALL = sweeps + chain rule; MMB_MODE_SWEEPS = everything that does NOT depend on the incoming gradient (the two
   // M x M sweeps, the full moment GEMM, the pair aggregates: mm_moment_match_with_sums leaves them on bwd_ws);
   // MMB_MODE_CHAIN = the chain rule alone on sums a MMB_MODE_SWEEPS call left on bwd_ws (MM_SUMS_CURRENT)

@@ -12,7 +12,11 @@
 //   mm_moment_match(drift)
 //   k_compose_tail_nd : forward_sde.py:105-131 with nu policy columns + solvers.py:110-135, then the shared encoding and
 //                       expected-cost bodies (mm_compose_dev.h, mm_cost.h), one launch
-// Forward only: the tape and the reverse sweep (mm_compose_bwd.hip) are written for one action.
+// mm_rollout_composed_taped_nd is the same rollout writing into a tape (mm_tape_layout_nd) that the reverse sweep of
+// mm_compose_bwd_nd.hip reads: step h works in tape slot h, the states x_0 .. x_H go to the state block, and -- by the rules of
+// mm_tape_layout_slots (mm_compose.h), as for one action -- the drift match runs in the tape's own workspace of the step where H of
+// them fit, and leaves the sums of its backward sweeps there too (mm_moment_match_with_sums_impl) where those fit as well.
+// The policy match's workspace is not kept: the reverse sweep recomputes the policy from (me, See).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "mm_common.h"
@@ -181,14 +185,16 @@ __device__ __forceinline__ void mmc_step_body_nd(const MMComposeDims& D, double 
 
 // the end of a step in one launch, as k_compose_tail: Euler update, the new state's encoding, its expected cost.  One wave per
 // batch element; the stages communicate through the wave's own global writes (visible after the workgroup barrier).
+// Sxe_in: Cov(x, e) of the state the step starts from; (me, See, Sxe): the encoding of the new state (untaped: Sxe_in == Sxe, the one
+// workspace; taped: the next slot)
 template <typename T>
 __global__ __launch_bounds__(64) void k_compose_tail_nd(MMComposeDims D, double dt, const double* cpol, const T* Sdd,
-                                                        const T* df1, const T* dSff, const T* dcross, T* mx, T* Sxx,
-                                                        T* traj_mu, T* traj_S, T* me, T* See, double* Sxe,
+                                                        const T* df1, const T* dSff, const T* dcross, const double* Sxe_in,
+                                                        T* mx, T* Sxx, T* traj_mu, T* traj_S, T* me, T* See, double* Sxe,
                                                         const T* target, const T* precis, T* cost) {
   extern __shared__ double csm[];
   const int b = blockIdx.x, lane = threadIdx.x;
-  mmc_step_body_nd<T>(D, dt, Sxe, cpol, Sdd, df1, dSff, dcross, mx, Sxx, traj_mu, traj_S, b, lane);
+  mmc_step_body_nd<T>(D, dt, Sxe_in, cpol, Sdd, df1, dSff, dcross, mx, Sxx, traj_mu, traj_S, b, lane);
   __syncthreads();
   mmc_encode_body<T>(D, mx, Sxx, me, See, Sxe, b, lane);
   if (cost) {
@@ -207,21 +213,37 @@ extern "C" size_t mm_compose_nd_workspace_bytes(int B, int nx, int na, int nu, i
   return mm_compose_layout_nd(B, nx, na, nu, dtype).total;
 }
 
+// tape == nullptr: every step reuses the one compose workspace `w`; else step h works in tape slot h (see the header comment)
 template <typename T>
 static int mm_rollout_composed_nd_t(const void* drift, size_t drift_bytes, int Md, const void* policy, size_t policy_bytes,
                                     int Mpol, int dtype, int B, int H, double dt, const MMComposeDims& D, const MMHeadND& hd,
                                     const T* target, const T* precis, T* mx, T* Sxx, T* cost, T* traj_mu, T* traj_S,
                                     void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
-                                    char* w, const MMComposeLayout& cl, int32_t* status, hipStream_t s) {
+                                    char* w, const MMComposeLayout& cl, char* tape, const MMTapeLayout& tl, int32_t* status,
+                                    hipStream_t s) {
   const int nx = D.nx, ne = D.ne, nd = D.nd, nu = nd - ne;
-  T *me = (T*)(w + cl.me), *See = (T*)(w + cl.See), *pf1 = (T*)(w + cl.pf1), *pSff = (T*)(w + cl.pSff);
-  T *pcross = (T*)(w + cl.pcross), *md = (T*)(w + cl.md), *Sdd = (T*)(w + cl.Sdd), *df1 = (T*)(w + cl.df1);
-  T *dSff = (T*)(w + cl.dSff), *dcross = (T*)(w + cl.dcross);
-  double *Sxe = (double*)(w + cl.Sxe), *cpol = (double*)(w + cl.cpol);
+  auto slot = [&](int h) { return tape ? tape + (size_t)h * tl.slot_bytes : w; };
+  T* xm = tape ? (T*)(tape + tl.xm) : nullptr;
+  T* xS = tape ? (T*)(tape + tl.xS) : nullptr;
 #define MMC_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-  hipLaunchKernelGGL((k_compose_encode_nd<T>), dim3(B), dim3(64), 0, s, D, (const T*)mx, (const T*)Sxx, me, See, Sxe);
-  MMC_CHECK();
+  if (tape) {
+    hipError_t e1 = hipMemcpyAsync(xm, mx, (size_t)B * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
+    hipError_t e2 = hipMemcpyAsync(xS, Sxx, (size_t)B * nx * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e1 != hipSuccess) return (int)e1;
+    if (e2 != hipSuccess) return (int)e2;
+  }
+  {
+    char* c0 = slot(0);
+    hipLaunchKernelGGL((k_compose_encode_nd<T>), dim3(B), dim3(64), 0, s, D, (const T*)mx, (const T*)Sxx, (T*)(c0 + cl.me),
+                       (T*)(c0 + cl.See), (double*)(c0 + cl.Sxe));
+    MMC_CHECK();
+  }
   for (int h = 0; h < H; ++h) {
+    char* c = slot(h); char* n = slot(h + 1);
+    T *me = (T*)(c + cl.me), *See = (T*)(c + cl.See), *pf1 = (T*)(c + cl.pf1), *pSff = (T*)(c + cl.pSff);
+    T *pcross = (T*)(c + cl.pcross), *md = (T*)(c + cl.md), *Sdd = (T*)(c + cl.Sdd), *df1 = (T*)(c + cl.df1);
+    T *dSff = (T*)(c + cl.dSff), *dcross = (T*)(c + cl.dcross);
+    double *Sxe = (double*)(c + cl.Sxe), *cpol = (double*)(c + cl.cpol);
     // policy: mean-only regressor (models.py:34-41: model_uncertainty = False), nu latents, full covariance between them
     int rc = mm_moment_match(policy, policy_bytes, nu, Mpol, ne, dtype, B, me, See, MM_FULL_OUTPUT_COV, 0.0, pf1, pSff, pcross,
                              ws_policy, ws_policy_bytes, status, (void*)s);
@@ -229,14 +251,22 @@ static int mm_rollout_composed_nd_t(const void* drift, size_t drift_bytes, int M
     hipLaunchKernelGGL((k_compose_head_nd<T>), dim3(B), dim3(256), 0, s, D, hd, (const T*)me, (const T*)See, (const T*)pf1,
                        (const T*)pSff, (const T*)pcross, md, Sdd, cpol);
     MMC_CHECK();
-    rc = mm_moment_match(drift, drift_bytes, nx, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY, 0.0,
-                         df1, dSff, dcross, ws_drift, ws_drift_bytes, status, (void*)s);
+    // (taped, small enough: the match runs in the tape's own workspace slot of this step, which the reverse sweep reads)
+    void* wsd = (tape && tl.ws_stride) ? (void*)(tape + tl.ws + (size_t)h * tl.ws_stride) : ws_drift;
+    const size_t wsd_bytes = (tape && tl.ws_stride) ? tl.ws_stride : ws_drift_bytes;
+    if (tape && tl.gp_stride)     // the sums of the backward's sweeps stay on the tape and give this step's value too (mm_compose.h)
+      rc = mm_moment_match_with_sums_impl(drift, drift_bytes, nx, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY,
+                                          0.0, df1, dSff, dcross, wsd, wsd_bytes, tape + tl.gp + (size_t)h * tl.gp_stride,
+                                          tl.gp_stride, status, (void*)s, false);
+    else
+      rc = mm_moment_match(drift, drift_bytes, nx, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY, 0.0,
+                           df1, dSff, dcross, wsd, wsd_bytes, status, (void*)s);
     if (rc) return rc;
+    T* tm = tape ? xm + (size_t)(h + 1) * B * nx : (traj_mu ? traj_mu + (size_t)h * B * nx : (T*)nullptr);
+    T* tS = tape ? xS + (size_t)(h + 1) * B * nx * nx : (traj_S ? traj_S + (size_t)h * B * nx * nx : (T*)nullptr);
     hipLaunchKernelGGL((k_compose_tail_nd<T>), dim3(B), dim3(64), mm_cost_lds_bytes(ne), s, D, dt, (const double*)cpol,
-                       (const T*)Sdd, (const T*)df1, (const T*)dSff, (const T*)dcross, mx, Sxx,
-                       traj_mu ? traj_mu + (size_t)h * B * nx : (T*)nullptr,
-                       traj_S ? traj_S + (size_t)h * B * nx * nx : (T*)nullptr, me, See, Sxe, target, precis,
-                       cost ? cost + (size_t)h * B : (T*)nullptr);
+                       (const T*)Sdd, (const T*)df1, (const T*)dSff, (const T*)dcross, (const double*)Sxe, mx, Sxx, tm, tS, (T*)(n + cl.me),
+                       (T*)(n + cl.See), (double*)(n + cl.Sxe), target, precis, cost ? cost + (size_t)h * B : (T*)nullptr);
     MMC_CHECK();
   }
 #undef MMC_CHECK
@@ -274,9 +304,49 @@ extern "C" int mm_rollout_composed_nd(const void* drift_packed, size_t drift_byt
     return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
                                             dt, D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
                                             (double*)cost, (double*)traj_mu, (double*)traj_Sigma, ws_drift, ws_drift_bytes,
-                                            ws_policy, ws_policy_bytes, (char*)ws_compose, cl, status, s);
+                                            ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s);
   return mm_rollout_composed_nd_t<float>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
                                          dt, D, hd, (const float*)target, (const float*)precis, (float*)mx, (float*)Sxx,
                                          (float*)cost, (float*)traj_mu, (float*)traj_Sigma, ws_drift, ws_drift_bytes,
-                                         ws_policy, ws_policy_bytes, (char*)ws_compose, cl, status, s);
+                                         ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s);
+}
+
+// ---- the same rollout, recorded (f64 only, as the reverse sweep) -------------------------------------------------------------
+// 0: dims out of range or a dtype other than MM_F64
+extern "C" size_t mm_compose_tape_bytes_nd(int B, int H, int nx, int na, int nu, int drift_M, int dtype) {
+  if (B <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
+  if (nu < 1 || nu > MMC_NU || 2 * na + (nx - na) + nu > MMC_ND) return 0;
+  if (dtype != MM_F64) return 0;
+  return mm_tape_layout_nd(B, H, nx, na, nu, drift_M, dtype).total;
+}
+
+extern "C" int mm_rollout_composed_taped_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                            int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                            int nu, const double* head_scale, const double* head_shift,
+                                            const void* target, const void* precis, void* mx, void* Sxx, void* cost,
+                                            void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                                            void* tape, size_t tape_bytes, int32_t* status, void* stream) {
+  if (!drift_packed || !policy_packed || !mx || !Sxx || !head_scale || !head_shift) return MM_E_ARG;
+  if (!ws_drift || !ws_policy || !tape) return MM_E_ARG;
+  if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
+  if (dtype != MM_F64) return MM_E_DTYPE;
+  if (cost && (!target || !precis)) return MM_E_ARG;
+  MMComposeDims D;
+  int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
+  if (rc) return rc;
+  if (drift_L != nx || drift_d != D.nd || policy_d != D.ne) return MM_E_STATE;
+  const MMTapeLayout tl = mm_tape_layout_nd(B, H, nx, na, nu, drift_M, dtype);
+  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  if (ws_policy_bytes < mm_workspace_bytes(B, nu, policy_M, D.ne, dtype, MM_FULL_OUTPUT_COV)) return MM_E_WORKSPACE;
+  if (ws_drift_bytes < mm_workspace_bytes(B, nx, drift_M, D.nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)) return MM_E_WORKSPACE;
+  if (policy_bytes < mm_packed_model_bytes(nu, policy_M, D.ne, dtype, 0)) return MM_E_WORKSPACE;
+  if (drift_bytes < mm_packed_model_bytes(nx, drift_M, D.nd, dtype, 1)) return MM_E_WORKSPACE;
+  MMHeadND hd = {};
+  for (int j = 0; j < nu; ++j) { hd.scale[j] = head_scale[j]; hd.shift[j] = head_shift[j]; }
+  const MMComposeLayout cl = mm_compose_layout_nd(B, nx, na, nu, dtype);
+  return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H, dt,
+                                          D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
+                                          (double*)cost, nullptr, nullptr, ws_drift, ws_drift_bytes, ws_policy, ws_policy_bytes, nullptr, cl,
+                                          (char*)tape, tl, status, (hipStream_t)stream);
 }

@@ -86,6 +86,17 @@ def _residual(A: torch.Tensor, L: torch.Tensor) -> float:
   return float(r.abs().max() / (n * A.abs().max() * v.abs().max()))
 
 
+def _batched_off_the_default_stream(A: torch.Tensor) -> bool:
+  """A batch of several small matrices (the Kuu of a policy with several latents) factorised while a HIP graph is being captured
+  or on a stream other than the default one.  The BATCHED ``cholesky_ex`` is not usable there: under capture it invalidates the
+  capture (hipErrorStreamCaptureInvalidated), and on the warm-up side stream of ``loops.GraphedPolicyLoss`` it returned an
+  ``info`` word that was never written (380314348 for n = 30).  The single-matrix call -- what a one-latent policy has always
+  taken, in both situations -- is used item by item instead; on the default stream nothing changes."""
+  if not A.is_cuda or A.ndim < 3 or A.numel() == A.shape[-1] * A.shape[-2]:
+    return False
+  return torch.cuda.is_current_stream_capturing() or torch.cuda.current_stream(A.device) != torch.cuda.default_stream(A.device)
+
+
 def cholesky(A: torch.Tensor) -> torch.Tensor:
   """Lower Cholesky factor of the model set-up matrices (Kuu + jitter, K + s2 I); never on the per-step path.
 
@@ -100,7 +111,14 @@ def cholesky(A: torch.Tensor) -> torch.Tensor:
   after each replay (``check_capture_status``).
   """
   big = A.is_cuda and A.shape[-1] > _BLOCK
-  L, info = _blocked_cholesky_ex(A) if big else torch.linalg.cholesky_ex(A)
+  if big:
+    L, info = _blocked_cholesky_ex(A)
+  elif _batched_off_the_default_stream(A):
+    items = [torch.linalg.cholesky_ex(a) for a in A.reshape((-1,) + A.shape[-2:])]
+    L = torch.stack([it[0] for it in items]).reshape(A.shape)
+    info = torch.stack([it[1] for it in items]).reshape(A.shape[:-2])
+  else:
+    L, info = torch.linalg.cholesky_ex(A)
   if A.is_cuda and torch.cuda.is_current_stream_capturing():
     bad = info != 0
     code = info.abs().max().reshape(1).to(torch.int32)

@@ -62,16 +62,28 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   if not (bj and len(bj) == 3 and isinstance(bj[0], tfb.Scale) and isinstance(bj[1], tfb.Shift) and isinstance(bj[2], tfb.NormalCDF)):
     return no("the policy head is not Chain[Scale, Shift, NormalCDF]")
 
+  memo = {}
+
   def _constant(v):
+    # a tensor's values are read back once per version: the closures ask on every call, and a read-back from the device is not
+    # allowed while a HIP graph is being captured (GraphedPolicyLoss warms up first)
+    src = v if isinstance(v, torch.Tensor) else None
+    if src is not None:
+      hit = memo.get(id(src))
+      if hit is not None and hit[0] is src and hit[1] == src._version:
+        return hit[2]
     if isinstance(v, torch.Tensor):
       v = v.detach()
       v = float(v) if v.numel() == 1 else [float(t) for t in v.reshape(-1).tolist()]
     if nu == 1:
-      return float(v)
-    vals = tuple(float(t) for t in v) if isinstance(v, (list, tuple)) else (float(v),) * nu
-    if len(vals) != nu:
-      raise ValueError("not one value per action")
-    return vals
+      out = float(v)
+    else:
+      out = tuple(float(t) for t in v) if isinstance(v, (list, tuple)) else (float(v),) * nu
+      if len(out) != nu:
+        raise ValueError("not one value per action")
+    if src is not None:
+      memo[id(src)] = (src, src._version, out)
+    return out
 
   def head_constants():
     return _constant(bj[0].scale), _constant(bj[1].shift)
@@ -83,20 +95,26 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
 
 
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
-                       why: Optional[list] = None):
+                       why: Optional[list] = None, native_actions: int = 1):
   """``f(mx, Sxx) -> loss [B]`` running the whole rollout in ``mm_rollout_composed`` (csrc/mm_compose.hip), or None
   when the system is not the shape that entry point implements: TrigonometricEncoder, policy =
   InverseLinkWrapper(KernelRegressor(SVGP with one latent per action), Chain[Scale, Shift, NormalCDF]), SVGP drift, no
   diffusion, MomentMatchingEuler, GaussianObjective -- the cartpole wiring of
   ``examples/cartpole_swingup/swingup_loops.py:41-91``; a policy with 2 to 4 actions runs in ``mm_rollout_composed_nd``
   (csrc/mm_compose_nd.hip).  ``f.with_grad(mx, Sxx)`` is the same loss as a differentiable op
-  (native reverse sweep, csrc/mm_compose_bwd.hip) where ``f.supports_grad(mx)``: one action only.  ``why``: a list that receives the reason
-  when None is returned."""
+  (native reverse sweep, csrc/mm_compose_bwd.hip) where ``f.supports_grad(mx)``: one action only by default.  ``why``: a list that
+  receives the reason when None is returned.
+
+  ``native_actions``: the largest number of actions ``with_grad`` may differentiate natively.  The default 1 keeps a policy with
+  several actions forward only (``grad_obstacle`` names ``nu > 1``); with ``native_actions >= nu`` its gradient runs through the
+  multi-action tape and reverse sweep (csrc/mm_compose_bwd_nd.hip, ``autodiff.ComposedRolloutNDFunction``) where
+  ``ComposedRollout.backward_nd_refusal`` has no objection."""
   from . import ops
   parts = _native_parts(system, objective, why, moment_solver=True)
   if parts is None:
     return None
   enc, pm_, drift, bj, head_constants = parts
+  max_native = int(native_actions)
   cache = {}
 
   def current_roll(mx: torch.Tensor, fresh_policy: bool = True):
@@ -131,15 +149,16 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     the taped native rollout, backward = the native reverse sweep (autodiff.ComposedRolloutFunction); the policy enters
     in packed coordinates computed from its parameters by differentiable torch ops (a 30 x 30 precompute).  The tape and
     the reverse sweep are float64; a float32 state is cast up on the way in and the loss back down (autograd carries both)."""
-    from .autodiff import ComposedRolloutFunction
+    from .autodiff import ComposedRolloutFunction, ComposedRolloutNDFunction
     out_dtype = mx.dtype
     if mx.dtype != torch.float64:
       mx, Sxx = mx.double(), Sxx.double()
     roll = current_roll(mx, fresh_policy=False)
     Zp, lsp, varp, betap, _, mcp = pm_.precompute(mx.device)
     if mcp is None:
-      mcp = torch.zeros(1, dtype=Zp.dtype, device=mx.device)
-    cost = ComposedRolloutFunction.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
+      mcp = torch.zeros(roll.nu, dtype=Zp.dtype, device=mx.device)
+    fn = ComposedRolloutFunction if roll.nu == 1 else ComposedRolloutNDFunction      # (several actions: native_actions >= nu)
+    cost = fn.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
     return cost.sum(1).to(out_dtype)
 
   def run_from_parameters(mx: torch.Tensor, Sxx: torch.Tensor):
@@ -157,9 +176,12 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     """None when ``with_grad`` covers everything that asks for a gradient here, else the reason it does not."""
     if mx.dtype not in (torch.float32, torch.float64):
       return f"state dtype {mx.dtype}"
-    if pm_.num_latent_gps > 1:
+    nu = int(pm_.num_latent_gps)
+    if nu > 1 and max_native <= 1:
       return (f"the policy has nu = {pm_.num_latent_gps} actions (nu > 1: the native rollout is forward only, its tape and "
               "reverse sweep are one-action)")
+    if nu > max(1, max_native):
+      return f"the policy has nu = {nu} actions (nu > 1) and native_actions = {max_native}"
     # the native reverse sweep returns gradients for the policy SVGP's parameters and the initial state only: the head's
     # Scale / Shift and the objective's target / precision enter as constants (float() / raw pointers)
     outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
@@ -171,6 +193,8 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       return "the drift is being trained (the native reverse sweep takes a frozen drift)"
     mx64 = mx if mx.dtype == torch.float64 else torch.empty(mx.shape, dtype=torch.float64, device=mx.device)
     roll = current_roll(mx64, fresh_policy=False)
+    if nu > 1:
+      return roll.backward_nd_refusal()
     if not roll.supports_backward():
       return (f"the policy has M = {roll.policy.M} centres on {roll.ne} encoded dims (the native reverse sweep takes "
               f"M <= {ops.ComposedRollout.BACKWARD_MAX_POLICY_M}, encoded dim <= 8)")
@@ -187,7 +211,7 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
 def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable,
                         num_steps: int, initial_time: float = 0.0,
                         solution_times: Optional[Sequence[float]] = None, native: Optional[bool] = None,
-                        **kwargs) -> Callable:
+                        native_actions: int = 1, **kwargs) -> Callable:
   """pilco.py:176-220.  Returns ``closure() -> loss [B]``; ``system.solver`` should be a
   ``MomentMatchingEuler`` (pilco.py:141-144).
 
@@ -197,7 +221,13 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   (``autodiff.ComposedRolloutFunction``) -- when the policy's parameters or the initial state do (float64, frozen
   drift, one action; with several actions a gradient takes the torch composition, which differentiates through
   ``special.bvn_cdf``); False always takes the torch composition (``forward_sde`` over ``moment_matching``); True insists on the
-  native path."""
+  native path.
+
+  ``native_actions``: the largest number of actions whose GRADIENT may run natively (a named parameter, not a solver option).
+  The default 1 is the routing described above.  With ``native_actions >= nu`` a gradient of the policy SVGP's parameters and / or
+  the initial state of a policy with 2 to 4 actions runs as one differentiable op too (``autodiff.ComposedRolloutNDFunction``: the
+  multi-action tape and reverse sweep, csrc/mm_compose_bwd_nd.hip) -- frozen drift, constant head and objective, float64 tape
+  (a float32 state is cast up), inside the sweep's LDS bound; every other case falls back once and names its reason."""
   uniform = solution_times is None
   if solution_times is None:
     solution_times = np.arange(1, 1 + num_steps, dtype=np.float64)     # pilco.py:186
@@ -211,7 +241,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       shape_reason = f"solver options {sorted(kwargs)}"
     else:
       why_not = []
-      fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not)
+      fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not, native_actions=native_actions)
       if fast is None:
         shape_reason = why_not[0] if why_not else "the system is not the shape mm_rollout_composed implements"
   if native is True and fast is None:

@@ -377,7 +377,8 @@ class ComposedRollout:
 
   ``drift`` / ``policy``: PackedModel (drift with C; policy with one latent per action, ``nu = policy.L``).  ``nu == 1`` is
   ``mm_rollout_composed``; ``nu > 1`` (up to 4 actions) ``mm_rollout_composed_nd`` (csrc/mm_compose_nd.hip: the head's cross
-  moments are bivariate normal CDFs), forward only.  ``head_scale`` / ``head_shift``: a float or one value per action.
+  moments are bivariate normal CDFs); ``taped`` / ``backward`` are one-action, ``taped_nd`` / ``backward_nd`` the tape and reverse
+  sweep for 1 to 4 actions (csrc/mm_compose_bwd_nd.hip).  ``head_scale`` / ``head_shift``: a float or one value per action.
   ``__call__(mx, Sxx, H)`` returns ``(mx_H, Sxx_H, cost [B, H])`` (and the trajectory if asked); the inputs are not modified.
   """
 
@@ -575,6 +576,87 @@ class ComposedRollout:
                                             wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
                                             self.drift.status().data_ptr(), _stream(dev))
     check(rc, "mm_rollout_composed_backward")
+    return g_pol, g_m, g_S
+
+  # ---- the same for 1 to 4 actions (csrc/mm_compose_nd.hip, csrc/mm_compose_bwd_nd.hip) -----------------------------------
+  def _head_arrays(self):
+    """(scale, shift) as ctypes arrays of nu doubles (a one-action rollout keeps them as floats)."""
+    if self.nu > 1:
+      return self._scale_c, self._shift_c
+    return (_lib.C.c_double * 1)(self.scale), (_lib.C.c_double * 1)(self.shift)
+
+  def backward_nd_refusal(self) -> Optional[str]:
+    """Why ``taped_nd`` / ``backward_nd`` do not take this rollout (None: they do)."""
+    if self.drift.dtype != torch.float64:
+      return "the multi-action tape and reverse sweep are float64 only"
+    if lib().mm_compose_backward_workspace_bytes_nd(1, self.nx, self.na, self.nu, self.drift.M, self.policy.M) == 0:
+      return (f"the policy (M = {self.policy.M} centres on ne = {self.ne} dims, {self.nu} actions) is past the LDS bound of the "
+              "multi-action reverse sweep (M <= 256, ne <= 8 and 160 KB of LDS per workgroup: M <= 166 at ne = 8)")
+    return None
+
+  def supports_backward_nd(self) -> bool:
+    """The multi-action tape and reverse sweep (``taped_nd`` / ``backward_nd``) take this rollout: f64, policy M <= 256 centres
+    on ne <= 8 encoded dims, up to 4 actions, inside the sweep's LDS bound (``backward_nd_refusal`` names the reason if not)."""
+    return self.backward_nd_refusal() is None
+
+  def taped_nd(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
+    """``mm_rollout_composed_taped_nd``: -> (mx_H, Sxx_H, cost [H, B], tape), for any nu in 1..4."""
+    pol = self._policy_pack(policy)
+    dt_ = self.drift.dtype
+    B, H = self._check_state(mx, Sxx), int(num_steps)
+    why = self.backward_nd_refusal()
+    if why is not None:
+      raise ValueError(why)
+    mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
+    cost = torch.empty(H, B, dtype=dt_, device=mx.device)
+    n = lib().mm_compose_tape_bytes_nd(B, H, self.nx, self.na, self.nu, self.drift.M, _dtype_code(dt_))
+    tape = torch.empty(n, dtype=torch.uint8, device=mx.device)
+    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
+    wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
+    scale, shift = self._head_arrays()
+    rc = lib().mm_rollout_composed_taped_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+                                            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(dt_), B, H, float(dt),
+                                            self.nx, self.na, self._act, self.nu, scale, shift, self.target.data_ptr(),
+                                            self.precis.data_ptr(), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
+                                            wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
+                                            self.drift.status().data_ptr(), _stream(mx.device))
+    check(rc, "mm_rollout_composed_taped_nd")
+    return mx, Sxx, cost, tape
+
+  def backward_nd(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
+                  policy: Optional[PackedModel] = None, want_state_grad: bool = True):
+    """``mm_rollout_composed_backward_nd``: g_cost [H, B] -> (g_policy [B, nu, M d + M + d + 2], g_mx0 [B,nx] | None,
+    g_Sxx0 [B,nx,nx] | None): per batch element and latent the gradient w.r.t. the packed policy (Z, beta, lengthscales^2,
+    variance, mean), and the gradient w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with."""
+    pol = self._policy_pack(policy)
+    dev = tape.device
+    H = int(num_steps)
+    f64 = torch.float64
+    g_cost = g_cost.to(f64).contiguous()
+    if g_cost.shape != (H, B):
+      raise ValueError(f"g_cost must be [H={H}, B={B}]")
+    npar = pol.M * pol.d + pol.M + pol.d + 2
+    g_pol = torch.empty(B, self.nu, npar, dtype=f64, device=dev)
+    g_m = torch.empty(B, self.nx, dtype=f64, device=dev) if want_state_grad else None
+    g_S = torch.empty(B, self.nx, self.nx, dtype=f64, device=dev) if want_state_grad else None
+    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
+    key = ("bwd_nd", B)
+    wb = self._wsc.get(key)
+    if wb is None:
+      n = lib().mm_compose_backward_workspace_bytes_nd(B, self.nx, self.na, self.nu, self.drift.M, pol.M)
+      if n == 0:
+        raise ValueError("mm_compose_backward_workspace_bytes_nd rejected the shape")
+      wb = torch.empty(n, dtype=torch.uint8, device=dev)
+      self._wsc[key] = wb
+    scale, shift = self._head_arrays()
+    rc = lib().mm_rollout_composed_backward_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+                                               pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
+                                               float(dt), self.nx, self.na, self._act, self.nu, scale, shift,
+                                               self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
+                                               g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_m), _ptr(g_S),
+                                               wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
+                                               self.drift.status().data_ptr(), _stream(dev))
+    check(rc, "mm_rollout_composed_backward_nd")
     return g_pol, g_m, g_S
 
 

@@ -216,7 +216,7 @@ int mm_rollout_composed(const void* drift_packed, size_t drift_bytes, int drift_
  * E[Phi(f_i) Phi(f_j)] is a bivariate normal CDF, evaluated by Plackett's integral on 4 x 48 Gauss-Legendre nodes (the diagonal
  * keeps Owen's T).  policy: packed with L = nu latents, policy_d == ne; drift_d == nd; head_scale / head_shift: HOST arrays of
  * nu doubles.  Everything else as mm_rollout_composed; nu == 1 computes what mm_rollout_composed computes (through the general
- * policy match).  Forward only: the tape and the reverse sweep below are one-action. */
+ * policy match).  Its tape and reverse sweep are mm_rollout_composed_taped_nd / mm_rollout_composed_backward_nd further down. */
 size_t mm_compose_nd_workspace_bytes(int B, int nx, int na, int nu, int dtype);
 int mm_rollout_composed_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
@@ -261,6 +261,41 @@ int mm_rollout_composed_backward(const void* drift_packed, size_t drift_bytes, i
                                  void* g_policy, void* g_mx0, void* g_Sxx0,
                                  void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                  int32_t* status, void* stream);
+
+/* ---- the same for a policy with nu actions (csrc/mm_compose_nd.hip, csrc/mm_compose_bwd_nd.hip; f64 only, else MM_E_DTYPE) ----
+ * mm_rollout_composed_taped_nd is mm_rollout_composed_nd writing into a tape: H + 1 slots of the multi-action compose workspace,
+ * the states x_0 .. x_H, and -- where H of them fit in 512 MB, by the rules of mm_compose_tape_bytes -- per step the drift match's
+ * q-stage workspace and the sums of its backward sweeps (the reverse sweep re-runs what the tape did not keep).  The policy
+ * match's workspace is not kept: the reverse sweep recomputes the policy from the taped (me, See).
+ * mm_rollout_composed_backward_nd is the reverse sweep:
+ *   g_cost   [H][B]  (in)
+ *   g_policy [B][nu][M d + M + d + 2] (out, overwritten; mm_policy_grad_bytes_nd): per batch element and latent, in latent
+ *            order, the gradient w.r.t. the packed policy -- Z [M][d], beta [M], ls2 [d], variance, mean_c; the centres in the
+ *            caller's order (M <= 256: the pack does not permute them)
+ *   g_mx0 [B][nx], g_Sxx0 [B][nx][nx] (out, both or neither)
+ * One workgroup per batch element runs the nu latent and nu (nu - 1) / 2 pair adjoints of the policy match in turn, from LDS;
+ * no floating-point atomics: two sweeps over one tape are bit-equal.  Shapes taken: policy M <= 256, ne <= 8, nu <= 4 and the
+ * workgroup's LDS (88 KB at M = 64, ne = 8, nu = 4) <= 160 KB, i.e. M <= 166 at ne = 8 -- every policy with M <= 64; beyond,
+ * mm_compose_backward_workspace_bytes_nd returns 0 and mm_rollout_composed_backward_nd MM_E_DIM.  A non-PD state is reported
+ * through `status` as by mm_rollout_composed_backward.  nu == 1 computes what the one-action entries compute. */
+size_t mm_compose_tape_bytes_nd(int B, int H, int nx, int na, int nu, int drift_M, int dtype);
+int mm_rollout_composed_taped_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                 const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                 int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                 int nu, const double* head_scale, const double* head_shift,
+                                 const void* target, const void* precis, void* mx, void* Sxx, void* cost,
+                                 void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                                 void* tape, size_t tape_bytes, int32_t* status, void* stream);
+size_t mm_compose_backward_workspace_bytes_nd(int B, int nx, int na, int nu, int drift_M, int policy_M);
+size_t mm_policy_grad_bytes_nd(int B, int nu, int policy_M, int policy_d);
+int mm_rollout_composed_backward_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                    const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                    int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                    int nu, const double* head_scale, const double* head_shift,
+                                    const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                    const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
+                                    void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                    int32_t* status, void* stream);
 
 /* ---- backward w.r.t. the input moments, stage A (f64 mode) ---------------------
  * The M x M part of d(f1, Sff, cross)/d(mu, Sigma) reduced to M-sized sums (see csrc/mm_backward.hip);

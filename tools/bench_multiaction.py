@@ -18,7 +18,16 @@ M = 2000, K = 1024 bases, policy M = 30, S = 8192 paths, H = 30), f32 and f64 pa
   one action (cartpole: nx = 4, one angle, nd = 6) through the existing entries, same four figures, same process: the yardstick.
 The variants of one shape are timed in alternation (window r of every variant before window r + 1 of any).  ``--samples`` /
 ``--drift-M`` shrink the shape for a dry run; ``--native-only`` leaves the torch composition out (the run to put under
-``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv)."""
+``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv).
+
+``--grad``: the moment-matched policy LOSS + GRADIENT (loops.policy_loss_closure; every policy parameter trainable), f64, H = 30, ms
+per step, for system A at B = 1, 64 and 256:
+  native (native_actions=2: csrc/mm_compose_bwd_nd.hip), eager and replayed from a ``GraphedPolicyLoss``; the native forward, eager
+    and replayed;
+  the torch composition's loss + gradient (native=False), eager -- the path the native one replaces;
+  the one-action native loss + gradient and forward at cartpole sizes, eager and replayed: the yardstick.
+All variants of one B in the same process, in alternating windows.  ``--native-only`` leaves the torch composition out (the run for
+a kernel trace: profiles/multiaction_grad_kernel_stats.csv); ``--batches 1,64`` picks the batch sizes."""
 import argparse
 import json
 import os
@@ -78,7 +87,9 @@ def windows(fn, H, inner, repeats, warmup):
 
 
 def alternating(fns, H, inner, repeats, warmup):
-  """{name: ms-per-step stats}: device events around `inner` back-to-back calls; the variants take turns window by window."""
+  """{name: ms-per-step stats}: device events around `inner` back-to-back calls; the variants take turns window by window.
+  ``inner``: one count for every variant, or {name: count}."""
+  inners = inner if isinstance(inner, dict) else {k: inner for k in fns}
   for fn in fns.values():
     for _ in range(warmup):
       fn()
@@ -88,13 +99,95 @@ def alternating(fns, H, inner, repeats, warmup):
     for k, fn in fns.items():
       e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
       e0.record()
-      for _ in range(inner):
+      for _ in range(inners[k]):
         fn()
       e1.record()
       e1.synchronize()
-      out[k].append(e0.elapsed_time(e1) / (inner * H))
+      out[k].append(e0.elapsed_time(e1) / (inners[k] * H))
   return {k: {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "windows": len(v),
-              "calls_per_window": inner} for k, v in out.items()}
+              "calls_per_window": inners[k]} for k, v in out.items()}
+
+
+def grad_closures(nx, active, nu, seed, B, H, device, native_actions):
+  """(native closure, torch-composition closure, trainable parameters) of the moment-matched policy loss of ``build``'s system."""
+  from gpflowpilco_amd.loops import get_state_initializer, policy_loss_closure
+  _, drift, pol, mx, Sxx, target, precis = build(nx, active, nu, 100, seed, B, device)
+  if nu == 1:
+    head = tfb.Chain([tfb.Scale(SCALE[0]), tfb.Shift(SHIFT[0]), tfb.NormalCDF()])
+  else:
+    head = tfb.Chain([tfb.Scale(to_dev(SCALE[:nu], device, F64)), tfb.Shift(to_dev(SHIFT[:nu], device, F64)), tfb.NormalCDF()])
+  system = dynamics.DynamicalSystem(drift=drift, policy=gp.InverseLinkWrapper(gp.KernelRegressor(pol), invlink=head),
+                                    encoder=TrigonometricEncoder(active_dims=active), solver=dynamics.MomentMatchingEuler())
+  objective = GaussianObjective(target=to_dev(target, device, F64), precis=to_dev(precis, device, F64))
+  ks = pol.kernel.kernels
+  params = [pol.q_mu] + [iv.Z for iv in pol.inducing_variable.inducing_variables] + [k.lengthscales for k in ks] + [k.variance for k in ks]
+  for t in params:
+    t.requires_grad_(True)
+  init = get_state_initializer(mx, Sxx)
+  native = policy_loss_closure(system, objective, init, H, native_actions=native_actions)
+  composed = policy_loss_closure(system, objective, init, H, native=False)
+  return native, composed, params, drift
+
+
+def main_grad(args):
+  import warnings
+  from gpflowpilco_amd.loops import GraphedPolicyLoss
+  device, H = "cuda", args.steps
+  res = {"tool": "bench_multiaction --grad", "label": args.label, "H": H, "unit": "ms per step, f64"}
+
+  def eager_pair(closure, params):
+    def forward():
+      with torch.no_grad():
+        return closure()
+
+    def loss_grad():
+      for t in params:
+        t.grad = None
+      loss = closure()
+      loss.sum().backward()
+      return loss
+    return forward, loss_grad
+  for B in [int(b) for b in args.batches.split(",")]:
+    with warnings.catch_warnings():
+      warnings.simplefilter("error", RuntimeWarning)          # a fall-back to the torch composition would be timed as native: refuse
+      nat2, tor2, par2, drift2 = grad_closures(4, (0, 1), 2, 20, B, H, device, 2)
+      nat1, _, par1, _ = grad_closures(4, (1,), 1, 10, B, H, device, 1)
+      f2, g2 = eager_pair(nat2, par2)
+      f1, g1 = eager_pair(nat1, par1)
+      # the captures come first, on fresh parameters: a backward that ran eagerly before pins the parameters' gradient accumulation
+      # to the default stream, which a later capture on another stream cannot record
+      gr2, gr1 = GraphedPolicyLoss(nat2, par2), GraphedPolicyLoss(nat1, par1)
+      loss_native = g2().detach().clone()
+    fns = {"two_actions_forward": f2, "two_actions_loss_and_grad": g2, "two_actions_forward_replayed": gr2.loss,
+           "two_actions_loss_and_grad_replayed": gr2.loss_and_grad, "one_action_forward": f1, "one_action_loss_and_grad": g1,
+           "one_action_forward_replayed": gr1.loss, "one_action_loss_and_grad_replayed": gr1.loss_and_grad}
+    inners = {k: args.inner for k in fns}
+    out = {}
+    if not args.native_only:
+      _, gt = eager_pair(tor2, par2)
+      loss_torch = gt().detach()
+      out["loss_native_vs_torch"] = float((loss_native - loss_torch).abs().max())
+      fns["two_actions_torch_loss_and_grad"] = gt
+      inners["two_actions_torch_loss_and_grad"] = 1
+    out.update(alternating(fns, H, inners, args.repeats, 2))
+    try:
+      drift2.packed(F64, True, device).check_status(B)
+    except Exception as e:                     # noqa: BLE001
+      out["status"] = str(e)
+    med = lambda k: out[k]["median"]
+    out["two_actions_loss_and_grad_over_forward"] = med("two_actions_loss_and_grad") / med("two_actions_forward")
+    out["two_actions_loss_and_grad_over_forward_replayed"] = (med("two_actions_loss_and_grad_replayed")
+                                                              / med("two_actions_forward_replayed"))
+    out["two_over_one_action_loss_and_grad_replayed"] = (med("two_actions_loss_and_grad_replayed")
+                                                         / med("one_action_loss_and_grad_replayed"))
+    if "two_actions_torch_loss_and_grad" in fns:
+      out["torch_over_native_loss_and_grad"] = med("two_actions_torch_loss_and_grad") / med("two_actions_loss_and_grad")
+      out["torch_over_native_loss_and_grad_replayed"] = (med("two_actions_torch_loss_and_grad")
+                                                         / med("two_actions_loss_and_grad_replayed"))
+    res[f"B{B}"] = out
+    del fns, gr2, gr1
+    torch.cuda.empty_cache()
+  print(json.dumps(res))
 
 
 def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True):
@@ -180,11 +273,15 @@ def main():
   ap.add_argument("--native-only", action="store_true", help="--pathwise without the torch composition (for a kernel trace)")
   ap.add_argument("--samples", type=int, default=8192)
   ap.add_argument("--drift-M", type=int, default=2000)
+  ap.add_argument("--grad", action="store_true", help="moment-matched loss + gradient, native vs torch composition (see the docstring)")
+  ap.add_argument("--batches", default="1,64,256")
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit("bench_multiaction.py needs the GPU (no CPU timing is meaningful)")
   if args.pathwise:
     return main_pathwise(args)
+  if args.grad:
+    return main_grad(args)
   device = "cuda"
   H = args.steps
   res = {"tool": "bench_multiaction", "label": args.label, "H": H, "unit": "ms per step, f64, eager",
