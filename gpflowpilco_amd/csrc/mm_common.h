@@ -21,6 +21,9 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // forward off-diagonal f32 sweep: take k_qred_f32_mfma (one grid slot per (b, pair)) even where the persistent work-list sweep
 // k_qred_f32_mfma_persist applies (mm_mfma.hip) -- A/B tests and measurements of the two on one build; the slabs are bit-identical
 #define MM_ISTAGE_OLD_OFFDIAG (1 << 23)
+// degree-4..6 contraction at d = 8: take the generic steps (mm6_step: every size a run-time value) even where the d = 8
+// specialisation mm6_step8 applies (mm_moments6.hip) -- A/B tests and measurements on one build; s56 and estS are bit-identical
+#define MM_ISTAGE_OLD_SPOLY56 (1 << 24)
 
 static inline int mm_num_pairs(int L, int flags) {
   return (flags & MM_FULL_OUTPUT_COV) ? L * (L + 1) / 2 : L;

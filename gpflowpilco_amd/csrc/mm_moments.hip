@@ -420,7 +420,7 @@ int mm_launch_wmom_full(const char* packed, const MMModelLayout& ml, char* ws, c
 }
 
 int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
-                        int B, int L, int d, int allow, hipStream_t stream);
+                        int B, int L, int d, int allow, int old_spoly56, hipStream_t stream);
 
 int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
                       int B, int L, int d, const void* mu_f32, int flags, hipStream_t stream) {
@@ -482,7 +482,7 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
     return es == hipSuccess ? 0 : (int)es;
   }
   // orders 5 and 6 of the collapsed items (f32 moments on the bf16 matrix pipe: mm_moments6.hip) -> s56, estS
-  return mm_launch_moments56(packed, ml, ws, wl, B, L, d, some ? 1 : 0, stream);
+  return mm_launch_moments56(packed, ml, ws, wl, B, L, d, some ? 1 : 0, (flags & MM_ISTAGE_OLD_SPOLY56) ? 1 : 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

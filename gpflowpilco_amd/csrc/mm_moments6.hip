@@ -361,6 +361,199 @@ __device__ __forceinline__ void mm6_step(const float* __restrict__ Tin, int nJin
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// d = 8: the same step with every size a compile-time constant.  mm6_step above issues ~270 instructions for a full two-chunk unit
+// (16 gathers, 64 packed FMAs, 16 stores): the rest finds the largest index t of I, decodes (c, I), and decides, forms the row
+// address and masks the second chunk once per OUTPUT -- all because d, the sym(k) sizes and t are run-time values.  Here
+//   - sym(k), the chunk count, the row stride and the row term C(i + K, K + 1) x stride are constants: a store (MODE 2: a read of X)
+//     is one ds instruction on a per-chunk base address with the row term as its immediate offset;
+//   - t is resolved by two scalar compares on I into the output PAIR (I0, I0 + 1) it starts in, I0 = 0, 2, 4, 6 -- the packed FMAs
+//     work on aligned pairs, so four variants of the product waste nothing -- and one flag `first` (t == I0: output I0 is stored too);
+//   - a wave keeps its chunk group for the whole step (MODE 0 / 1 store exact values: their unit-to-wave mapping is free), so the
+//     gather offsets are loaded once per step; the second chunk's stores sit in one exec region.
+// Every stored value and every sum keeps its operation order: per output the chain G[0] v_0, fma j = 1 .. 7; MODE 1 (m3 mj) s;
+// MODE 2 the wave's units u = wave, wave + NW, .. and inside a unit (i ascending, q ascending) -- s56 is bit-equal to mm6_step's.
+// ---------------------------------------------------------------------------------------------
+typedef float mm6_f2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) float mm6_lds_f;
+constexpr int mm6_cbinom(int n, int k) {
+  if (k < 0 || k > n) return 0;
+  int r = 1;
+  for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i;
+  return r;
+}
+constexpr int mm6_sym8(int k) { return mm6_cbinom(8 + k - 1, k); }   // sym(k) at d = 8: 1, 8, 36, 120, 330, 792, 1716
+
+template <int K, int MODE, int NJIN, int NJP, int XS, int NC, int NW>
+__device__ __forceinline__ void mm6_step8(const float* __restrict__ Tin_, float* __restrict__ Tout_, const short* __restrict__ ins,
+                                          const float (&G)[64], const float* __restrict__ multJ, float& acc, int wave, int lane) {
+  // (the lane's table addresses are formed here, per step: hoisted out of the item loop for every step at once -- they depend on
+  // the lane alone -- they were spilled to scratch)
+  asm volatile("" : "+v"(lane));
+  // the two tensors' LDS addresses as opaque scalars: with every size a constant the compiler otherwise folds the tensor's own
+  // offset into the row term, which then no longer fits the 16-bit ds offset (one v_add per store instead)
+  unsigned a_in = (unsigned)(size_t)(const mm6_lds_f*)Tin_, a_out = (unsigned)(size_t)(mm6_lds_f*)Tout_;
+  asm volatile("" : "+s"(a_in));
+  asm volatile("" : "+s"(a_out));
+  const mm6_lds_f* Tin = (const mm6_lds_f*)(size_t)a_in;
+  mm6_lds_f* Tout = (mm6_lds_f*)(size_t)a_out;
+  constexpr int NI = mm6_sym8(K);
+  constexpr int CH = (NJP + 64 * NC - 1) / (64 * NC);
+  constexpr int ST = MODE == 0 ? NJP : XS;               // row stride of the stored tensor
+  static_assert(K >= 0 && K <= 2, "K of the n <= 6 chains");
+  static_assert(mm6_cbinom(7 + K, K + 1) * ST * 4 < 65536, "the row term is a 16-bit ds offset");
+  // lowest rank of a K-tuple with largest index t (K = 0: one empty tuple)
+  auto low = [](int t) constexpr { return mm6_cbinom(t + K - 1, K); };
+  auto row = [](int i) constexpr { return mm6_cbinom(i + K, K + 1); };   // rank of I with i appended = I + row(i) (colex)
+  int off[NC][8], Jc[NC];
+  bool jv[NC];
+  float mj[NC];
+  auto load_c = [&](int c) __attribute__((always_inline)) {
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      const int Jp = (c * NC + q) * 64 + lane;
+      jv[q] = Jp < NJP;
+      Jc[q] = jv[q] ? Jp : NJP - 1;                      // lanes past the end gather a valid (clamped) entry and store / add nothing
+      const short4 ia = *reinterpret_cast<const short4*>(ins + (size_t)Jc[q] * 8);
+      const short4 ib = *reinterpret_cast<const short4*>(ins + (size_t)Jc[q] * 8 + 4);
+      off[q][0] = ia.x; off[q][1] = ia.y; off[q][2] = ia.z; off[q][3] = ia.w;
+      off[q][4] = ib.x; off[q][5] = ib.y; off[q][6] = ib.z; off[q][7] = ib.w;
+      if constexpr (MODE == 1) mj[q] = multJ[Jc[q]];
+    }
+  };
+  // one unit whose outputs start in the pair (I0, I0 + 1): t = I0 (first) or I0 + 1
+  auto body = [&](auto i0c, int I, bool first) __attribute__((always_inline)) {
+    constexpr int I0 = decltype(i0c)::value;
+    const mm6_lds_f* tin = Tin + I * NJIN;
+    float v[NC][8], s[NC][8];
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[q][j] = tin[off[q][j]];
+    // (the variants' chains stay in their own branch, all chains of a unit in one block: merged across the variants into a cascade
+    // of blocks of two chains each they run at the FMA's latency)
+#pragma unroll
+    for (int q = 0; q < NC; ++q) asm volatile("; unit %c1" : "+v"(v[q][0]) : "n"(I0 * 16 + K * 4 + MODE));
+    // the output pairs (2 p, 2 p + 1), p >= I0 / 2, as packed FMAs: G is output-fastest, so a pair is an aligned register pair
+    mm6_f2 s2[NC][4];
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int p = I0 / 2; p < 4; ++p) s2[q][p] = mm6_f2{G[2 * p], G[2 * p + 1]} * mm6_f2{v[q][0], v[q][0]};
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+#pragma unroll
+      for (int q = 0; q < NC; ++q)
+#pragma unroll
+        for (int p = I0 / 2; p < 4; ++p)
+          s2[q][p] = __builtin_elementwise_fma(mm6_f2{G[j * 8 + 2 * p], G[j * 8 + 2 * p + 1]}, mm6_f2{v[q][j], v[q][j]}, s2[q][p]);
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+#pragma unroll
+      for (int p = I0 / 2; p < 4; ++p) {
+        asm volatile("" : "+v"(s2[q][p]));               // (formed for every lane, not inside the stores' exec regions)
+        s[q][2 * p] = s2[q][p].x; s[q][2 * p + 1] = s2[q][p].y;
+      }
+    if constexpr (MODE == 0) {
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        mm6_lds_f* o = Tout + I * ST + Jc[q];
+        if (jv[q]) {
+          if (first) o[row(I0) * ST] = s[q][I0];
+#pragma unroll
+          for (int i = I0 + 1; i < 8; ++i) o[row(i) * ST] = s[q][i];
+          asm volatile("; stores %c0" : : "n"((I0 * 16 + K * 4 + MODE) * 2 + q));   // (not merged across the variants: see above)
+        }
+      }
+    } else if constexpr (MODE == 1) {
+      // multinomial of the sorted tuple (I, i): m_eq where i == t, m_gt where i > t
+      float m_eq = 1.0f, m_gt = 2.0f;                    // K = 1: I = (t)
+      if constexpr (K == 2) {                            // I = (a, t), a = I - C(t + 1, 2)
+        const bool aeq = first ? (I - low(I0) == I0) : (I - low(I0 + 1) == I0 + 1);
+        m_eq = aeq ? 1.0f : 3.0f;
+        m_gt = aeq ? 3.0f : 6.0f;
+      }
+      const float m_1 = first ? m_gt : m_eq;             // (output I0 + 1)
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        mm6_lds_f* o = Tout + I * ST + Jc[q];
+        if (jv[q]) {
+          if (first) o[row(I0) * ST] = (m_eq * mj[q]) * s[q][I0];
+          o[row(I0 + 1) * ST] = (m_1 * mj[q]) * s[q][I0 + 1];
+#pragma unroll
+          for (int i = I0 + 2; i < 8; ++i) o[row(i) * ST] = (m_gt * mj[q]) * s[q][i];
+          asm volatile("; stores %c0" : : "n"((I0 * 16 + K * 4 + MODE) * 2 + q));
+        }
+      }
+    } else {
+      const mm6_lds_f* x[NC];                                // (Tout = X here: X[J'][I + row(i)])
+#pragma unroll
+      for (int q = 0; q < NC; ++q) x[q] = Tout + Jc[q] * ST + I;
+      if (first) {
+#pragma unroll
+        for (int q = 0; q < NC; ++q) acc = (q == 0 || jv[q]) ? fmaf(s[q][I0], x[q][row(I0)], acc) : acc;
+      }
+#pragma unroll
+      for (int i = I0 + 1; i < 8; ++i)
+#pragma unroll
+        for (int q = 0; q < NC; ++q) acc = (q == 0 || jv[q]) ? fmaf(s[q][i], x[q][row(i)], acc) : acc;
+    }
+    asm volatile("; end %c0" : : "n"(I0 * 16 + K * 4 + MODE));
+  };
+  auto unit = [&](int I) __attribute__((always_inline)) {
+    if constexpr (K == 0) {
+      body(std::integral_constant<int, 0>{}, 0, true);
+    } else {
+      if (I < low(4)) {
+        if (I < low(2)) body(std::integral_constant<int, 0>{}, I, I < low(1));
+        else body(std::integral_constant<int, 2>{}, I, I < low(3));
+      } else {
+        if (I < low(6)) body(std::integral_constant<int, 4>{}, I, I < low(5));
+        else body(std::integral_constant<int, 6>{}, I, I < low(7));
+      }
+    }
+  };
+  // (chunk 0 of a group is never wholly past the end: jv[0] is a lane mask)
+  if constexpr (CH == 1) {
+    if (wave < NI) {
+      load_c(0);
+      for (int I = wave; I < NI; I += NW)
+        if (jv[0]) unit(I);
+    }
+  } else if constexpr (NI == 1) {
+    for (int c = wave; c < CH; c += NW) {
+      load_c(c);
+      if (jv[0]) unit(0);
+    }
+  } else if constexpr (MODE != 2 && NW % CH == 0) {
+    // wave -> (chunk group wave % CH, I = wave / CH, + NW / CH, ..)
+    const int c = wave % CH;
+    load_c(c);
+    for (int I = wave / CH; I < NI; I += NW / CH)
+      if (jv[0]) unit(I);
+  } else {
+    // units (c, I), I fastest, round robin as in mm6_step (the fused dot keeps its order of summation whatever NC is): the offsets
+    // are reloaded when c changes
+    int cprev = -1;
+    for (int u = wave; u < CH * NI; u += NW) {
+      const int c = u / NI, I = u - c * NI;
+      if (c != cprev) { cprev = c; load_c(c); }
+      if (jv[0]) unit(I);
+    }
+  }
+}
+
+// one contraction step of the kernels below: from sym(KIN) to sym(KIN - 1) values of J'; D8: the d = 8 form
+template <bool D8, int K, bool TRANSG, int MODE, int NC, int NW, int KIN, int XS8>
+__device__ __forceinline__ void mm6_do(const float* __restrict__ Tin, float* __restrict__ Tout, const int* sy, const short* __restrict__ tabi,
+                                       const MMTab56& tb, int d, const float (&G)[64], const float* __restrict__ multJ, int xs,
+                                       float& acc, int wave, int lane) {
+  if constexpr (D8)
+    mm6_step8<K, MODE, mm6_sym8(KIN), mm6_sym8(KIN - 1), XS8, NC, NW>(Tin, Tout, tabi + tb.ins[KIN - 1], G, multJ, acc, wave, lane);
+  else
+    mm6_step<K, TRANSG, MODE, NC, NW>(Tin, sy[KIN], sy[K], Tout, sy[KIN - 1], tabi + tb.ins[KIN - 1], d, G, multJ, xs, acc, wave, lane);
+}
+
 // Work lists by collapse degree (MMWorkspaceLayout::ilist): the contractions run over the items that need them, the degree-6/5 ones
 // in workgroups of MM6_THREADS threads with 160 KB of LDS (one per CU), the degree-4 ones -- every item of the pilco recipe --
 // in workgroups of 256 threads with 13 KB (k_spoly4): as ONE grid over all (b, pair) a degree-4 item cost a 768-thread, whole-CU
@@ -406,15 +599,18 @@ __device__ __forceinline__ float mm6_estS(float bound2, bool need5, bool need6, 
   return (float)fmin((double)MM_C6_SYS2 * (amp * amp) * r2 * c2, 3.0e38);
 }
 
-// grid: persistent over the degree-6 / degree-5 items of ilist (any size; one workgroup per CU fits)
+// grid: persistent over the degree-6 / degree-5 items of ilist (any size; one workgroup per CU fits).  D8: d == 8, the steps are mm6_step8
+template <bool D8>
 __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict__ mom56, int N56p, const double* __restrict__ pairmat,
                                                  const double* __restrict__ zmax2, const unsigned int* __restrict__ amaxc,
                                                  const unsigned char* __restrict__ gflag,
                                                  const double* __restrict__ whR, const double* __restrict__ whC,
-                                                 const char* __restrict__ tab, MMTab56 tb, int L, int d, int P, int Mp,
+                                                 const char* __restrict__ tab, MMTab56 tb, int L, int d_, int P, int Mp,
                                                  const int* __restrict__ ilist,
                                                  double* __restrict__ s56, float* __restrict__ estS) {
   extern __shared__ __align__(16) float sm6[];
+  const int d = D8 ? 8 : d_;
+  constexpr int NW = MM6_WAVES, NC = MM6_NC;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int Po = P - L;
@@ -489,18 +685,18 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
     const float* Q6 = nq + n56 + sy[4] + sy[5];
     const float* N6 = nq + sy[4] + sy[5];
     load_G(1);
-    mm6_step<0, false, 0>(Q6, sy[6], 1, Bf, sy[5], tabi + tb.ins[5], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, false, 0, NC, NW, 6, 0>(Q6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<1, false, 0>(Bf, sy[5], sy[1], A, sy[4], tabi + tb.ins[4], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 1, false, 0, NC, NW, 5, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<2, false, 1>(A, sy[4], sy[2], X, sy[3], tabi + tb.ins[3], d, G, mult3, xs, dummy, wave, lane);
+    mm6_do<D8, 2, false, 1, NC, NW, 4, 121>(A, X, sy, tabi, tb, d, G, mult3, xs, dummy, wave, lane);
     __syncthreads();
     load_G(0);
-    mm6_step<0, true, 0>(N6, sy[6], 1, Bf, sy[5], tabi + tb.ins[5], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, true, 0, NC, NW, 6, 0>(N6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<1, true, 0>(Bf, sy[5], sy[1], A, sy[4], tabi + tb.ins[4], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 1, true, 0, NC, NW, 5, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<2, true, 2>(A, sy[4], sy[2], X, sy[3], tabi + tb.ins[3], d, G, nullptr, xs, acc6, wave, lane);
+    mm6_do<D8, 2, true, 2, NC, NW, 4, 121>(A, X, sy, tabi, tb, d, G, nullptr, xs, acc6, wave, lane);
     __syncthreads();
   }
   // ---- n = 5 (X [sym3][sym2] = three indices of Q_5 through G; Y = two indices of N_5 through G^T, fused dot) and n = 4 (every
@@ -515,22 +711,22 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
     const float* N4 = nq;
     const int xs4 = sy[2] + 1;
     load_G(1);
-    if (need5) mm6_step<0, false, 0>(Q5, sy[5], 1, Bf, sy[4], tabi + tb.ins[4], d, G, nullptr, 0, dummy, wave, lane);
-    mm6_step<0, false, 0>(Q4, sy[4], 1, Bf4, sy[3], tabi + tb.ins[3], d, G, nullptr, 0, dummy, wave, lane);
+    if (need5) mm6_do<D8, 0, false, 0, NC, NW, 5, 0>(Q5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, false, 0, NC, NW, 4, 0>(Q4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    if (need5) mm6_step<1, false, 0>(Bf, sy[4], sy[1], A, sy[3], tabi + tb.ins[3], d, G, nullptr, 0, dummy, wave, lane);
-    mm6_step<1, false, 1, 1>(Bf4, sy[3], sy[1], X4, sy[2], tabi + tb.ins[2], d, G, mult2, xs4, dummy, wave, lane);   // (J' = sym2 <= 36: one chunk)
+    if (need5) mm6_do<D8, 1, false, 0, NC, NW, 4, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 1, false, 1, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, mult2, xs4, dummy, wave, lane);   // (J' = sym2 <= 36: one chunk)
     __syncthreads();
     if (need5) {
-      mm6_step<2, false, 1, 1>(A, sy[3], sy[2], X, sy[2], tabi + tb.ins[2], d, G, mult2, xs, dummy, wave, lane);
+      mm6_do<D8, 2, false, 1, 1, NW, 3, 121>(A, X, sy, tabi, tb, d, G, mult2, xs, dummy, wave, lane);
       __syncthreads();
     }
     load_G(0);
-    if (need5) mm6_step<0, true, 0>(N5, sy[5], 1, Bf, sy[4], tabi + tb.ins[4], d, G, nullptr, 0, dummy, wave, lane);
-    mm6_step<0, true, 0>(N4, sy[4], 1, Bf4, sy[3], tabi + tb.ins[3], d, G, nullptr, 0, dummy, wave, lane);
+    if (need5) mm6_do<D8, 0, true, 0, NC, NW, 5, 0>(N5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, true, 0, NC, NW, 4, 0>(N4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    if (need5) mm6_step<1, true, 2>(Bf, sy[4], sy[1], X, sy[3], tabi + tb.ins[3], d, G, nullptr, xs, acc5, wave, lane);
-    mm6_step<1, true, 2, 1>(Bf4, sy[3], sy[1], X4, sy[2], tabi + tb.ins[2], d, G, nullptr, xs4, acc4, wave, lane);
+    if (need5) mm6_do<D8, 1, true, 2, NC, NW, 4, 121>(Bf, X, sy, tabi, tb, d, G, nullptr, xs, acc5, wave, lane);
+    mm6_do<D8, 1, true, 2, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, nullptr, xs4, acc4, wave, lane);
   }
   double tot = (double)MM_C6_C1 * (double)acc4 + (double)MM_C6_C2 * (double)acc5 + (double)MM_C6_C3 * (double)acc6;
 #pragma unroll
@@ -554,14 +750,19 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
 // k_spoly4: the degree-4 items (bound X <= 1/40: orders 5 and 6 are below p6's own error) -- s56 = C1 <N_4, G^{(x)4} Q_4>, the n = 4
 // steps of k_spoly56 alone: 256 threads, 13 KB of LDS, persistent over the back part of ilist
 // ---------------------------------------------------------------------------------------------
+template <bool D8>
 __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56, int N56p, const double* __restrict__ pairmat,
                                                 const double* __restrict__ zmax2, const unsigned int* __restrict__ amaxc,
                                                 const unsigned char* __restrict__ gflag,
                                                 const double* __restrict__ whR, const double* __restrict__ whC,
-                                                const char* __restrict__ tab, MMTab56 tb, int L, int d, int P, int Mp, int ntotal,
+                                                const char* __restrict__ tab, MMTab56 tb, int L, int d_, int P, int Mp, int ntotal,
                                                 const int* __restrict__ ilist,
                                                 double* __restrict__ s56, float* __restrict__ estS) {
   extern __shared__ __align__(16) float sm4[];
+  const int d = D8 ? 8 : d_;
+  // (d = 8: the first step's 120 values of J' as two one-chunk units on two waves -- as one two-chunk unit a single wave of the
+  // four worked: pilco recipe 120 -> 91 us)
+  constexpr int NC0 = D8 ? 1 : MM6_NC;
   constexpr int NW = 4;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -619,14 +820,14 @@ __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56,
     const float* Q4 = nq + sy[4];
     const float* N4 = nq;
     load_G(1);
-    mm6_step<0, false, 0, MM6_NC, NW>(Q4, sy[4], 1, Bf4, sy[3], tabi + tb.ins[3], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, false, 0, NC0, NW, 4, 0>(Q4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<1, false, 1, 1, NW>(Bf4, sy[3], sy[1], X4, sy[2], tabi + tb.ins[2], d, G, mult2, xs4, dummy, wave, lane);
+    mm6_do<D8, 1, false, 1, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, mult2, xs4, dummy, wave, lane);
     __syncthreads();
     load_G(0);
-    mm6_step<0, true, 0, MM6_NC, NW>(N4, sy[4], 1, Bf4, sy[3], tabi + tb.ins[3], d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, true, 0, NC0, NW, 4, 0>(N4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
     __syncthreads();
-    mm6_step<1, true, 2, 1, NW>(Bf4, sy[3], sy[1], X4, sy[2], tabi + tb.ins[2], d, G, nullptr, xs4, acc4, wave, lane);
+    mm6_do<D8, 1, true, 2, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, nullptr, xs4, acc4, wave, lane);
     double tot = (double)MM_C6_C1 * (double)acc4;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -647,7 +848,7 @@ __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56,
 // Degree-5/6 moments + contraction for the collapsed items of the last q stage (after k_wmom_perm on the same stream).
 // allow == 0 (forced worst tier): nothing is collapsed; s56 / estS are zeroed.
 int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
-                        int B, int L, int d, int allow, hipStream_t stream) {
+                        int B, int L, int d, int allow, int old_spoly56, hipStream_t stream) {
   const int N56p = mm_moment56_cols(d);
   if (N56p <= 0 || wl.Po <= 0) return 0;
   if (allow) {
@@ -701,7 +902,8 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
   const unsigned long long bit2 = (dev >= 0 && dev < 64) ? (1ull << dev) : 0ull;
   int ncu = bit2 ? ncu_cached[dev].load() : 0;
   if (!bit2 || !(attr2_done.load() & bit2)) {
-    const hipError_t ea = hipFuncSetAttribute((const void*)k_spoly56, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t ea = hipFuncSetAttribute((const void*)k_spoly56<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_spoly56<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (ea != hipSuccess) return (int)ea;
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev < 64 ? dev : 0) != hipSuccess || v <= 0) v = 256;
@@ -711,7 +913,9 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
   if (ncu <= 0) ncu = 256;
   // persistent grids over the lists: one 160 KB workgroup per CU for the degree-6/5 items, eight small ones for the degree-4 items
   const int g56 = nitem < ncu ? nitem : ncu, g4 = nitem < 8 * ncu ? nitem : 8 * ncu;
-  hipLaunchKernelGGL(k_spoly56, dim3(g56), dim3(MM6_THREADS), shm, stream, (const float*)(ws + wl.mom56), N56p,
+  // d = 8: the steps with compile-time sizes (mm6_step8), unless the caller asks for the generic ones (MM_ISTAGE_OLD_SPOLY56)
+  const bool d8 = d == 8 && !old_spoly56;
+  hipLaunchKernelGGL((d8 ? k_spoly56<true> : k_spoly56<false>), dim3(g56), dim3(MM6_THREADS), shm, stream, (const float*)(ws + wl.mom56), N56p,
                      (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zmax2), (const unsigned int*)(ws + wl.amaxc),
                      (const unsigned char*)(ws + wl.gflag), (const double*)(ws + wl.whR), (const double*)(ws + wl.whC),
                      packed + ml.tab56, mm_tab56(d), L, d, wl.P, wl.Mp, (const int*)ilist, (double*)(ws + wl.s56), (float*)(ws + wl.estS));
@@ -720,7 +924,7 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
     if (e5 != hipSuccess) return (int)e5;
   }
   const size_t shm4 = (size_t)(((2 * sy[4] + sy[1] * sy[3] + sy[2] * (sy[2] + 1) + 3) & ~3) + 128 + 2 * 3 * 4 + 8) * sizeof(float);
-  hipLaunchKernelGGL(k_spoly4, dim3(g4), dim3(256), shm4, stream, (const float*)(ws + wl.mom56), N56p,
+  hipLaunchKernelGGL((d8 ? k_spoly4<true> : k_spoly4<false>), dim3(g4), dim3(256), shm4, stream, (const float*)(ws + wl.mom56), N56p,
                      (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zmax2), (const unsigned int*)(ws + wl.amaxc),
                      (const unsigned char*)(ws + wl.gflag), (const double*)(ws + wl.whR), (const double*)(ws + wl.whC),
                      packed + ml.tab56, mm_tab56(d), L, d, wl.P, wl.Mp, nitem, (const int*)ilist, (double*)(ws + wl.s56),
