@@ -159,6 +159,15 @@ SIGNATURES = {
                                                + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
                                                + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
                                                + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mm_pathwise_policy_rollout_wide": (C.c_int, [C.c_int] * 5 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                        + [C.c_void_p] * 9
+                                        + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                        + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "mm_pathwise_backward_scratch_bytes_wide": (C.c_size_t, [C.c_int] * 4),
+    "mm_pathwise_policy_rollout_backward_wide": (C.c_int, [C.c_int] * 3 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                                 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                                 + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+                                                 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mm_rollout_closed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_double, C.c_int, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -92,6 +92,367 @@ __device__ __forceinline__ float pw_wave_sum63(float v) {
   return v;
 }
 
+// ---- the Jacobian pass for 8 < d <= 16 (DK = 16): HALF-GROUPS ----------------------------------------------------------------
+// The [NS][DK] Jacobian sums of a whole group do not fit beside the DK operand vectors (f64: 128 + 64 VGPRs; enabled as they
+// are, the templates below spill ~1 KB per lane inside the term loop).  The weight stream is blocked wb[g][a][tb][sl][BT], so the
+// samples of a group are separate 64 * W-element rows of every block: a wave walks a (group, latent) TWICE, each time over
+// PW_WIDE_NH = 2 of its samples -- first the rows sl = 0, 1 of all NB blocks, then the rows sl = 2, 3.  No weight is read twice
+// (HBM traffic unchanged), the accumulators are [2][DK] (f64: 64 VGPRs, as [4][8] at DK = 8), every per-term quantity (argument,
+// transcendental, t = w sin / v 2^arg) is computed once, and per sample the terms are added in the plain pass's order by the
+// plain pass's expressions: f stays bit-equal.  What is paid twice is the read of the shared operands (LDS resp. L2): DK + 1
+// vector loads per block against 2 * W * (2 + 2 DK) FMA-class operations.
+#define PW_WIDE_NH 2
+
+// k_pathwise<T, DK, true, false>, DK > 8: wave wv owns the latents wv, wv + 4, ... of the workgroup's NS samples, two at a time
+template <typename T, int DK>
+__device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, const T* __restrict__ x,
+                                            const T* __restrict__ omega, const T* __restrict__ phase, const T* __restrict__ zs,
+                                            const T* __restrict__ hz, const double* __restrict__ xscale,
+                                            const double* __restrict__ pscale, const double* __restrict__ var,
+                                            const double* __restrict__ meanc, const T* __restrict__ wb, T* __restrict__ out,
+                                            T* __restrict__ traj, T* __restrict__ jac, int euler, double dt) {
+  typedef typename PwVec<T>::type VT;
+  constexpr int W = PwVec<T>::W, NS = MM_PW_NS, NH = PW_WIDE_NH, BT = 64 * W;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int g = blockIdx.x;
+  const int nbK = K / BT, nbM = M / BT, NB = nbK + nbM;
+  for (int a = wv; a < L; a += 4) {
+#pragma unroll 1
+    for (int hf = 0; hf < NS / NH; ++hf) {
+      const int s0 = g * NS + hf * NH;
+      T xr[NH][DK], accp[NH], accu[NH], accJ[NH][DK];
+#pragma unroll
+      for (int s = 0; s < NH; ++s) {
+        const int row = (s0 + s < S) ? s0 + s : S - 1;
+        accp[s] = (T)0; accu[s] = (T)0;
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          const T v = x[(size_t)row * d + (k < d ? k : 0)];
+          xr[s][k] = (k < d) ? v : (T)0;
+          accJ[s][k] = (T)0;
+        }
+      }
+      const T* hrow = wb + (((size_t)g * L + a) * NB) * NS * BT + (size_t)hf * NH * BT + lane * W;   // this half's rows of block 0
+      // ---- prior part
+      {
+        const T* om = omega + (size_t)a * K * d;
+        const T* ph = phase + (size_t)a * K;
+        VT wq[3][NH];
+#pragma unroll
+        for (int pf = 0; pf < 2; ++pf)
+#pragma unroll
+          for (int s = 0; s < NH; ++s)
+            wq[pf][s] = *reinterpret_cast<const VT*>(hrow + ((size_t)(pf < nbK ? pf : nbK - 1) * NS + s) * BT);
+        for (int pidx = 0; pidx < nbK; ++pidx) {
+          const int k0 = lane * W + pidx * BT;
+#pragma unroll
+          for (int s = 0; s < NH; ++s)
+            wq[2][s] = *reinterpret_cast<const VT*>(hrow + ((size_t)(pidx + 2 < nbK ? pidx + 2 : nbK - 1) * NS + s) * BT);
+          T wv4[NH][W], cv[DK][W], bv[W];
+#pragma unroll
+          for (int s = 0; s < NH; ++s) pw_unpack<T>(wq[0][s], wv4[s]);
+#pragma unroll
+          for (int k = 0; k < DK; ++k) {
+            pw_unpack<T>(*reinterpret_cast<const VT*>(om + (size_t)(k < d ? k : 0) * K + k0), cv[k]);
+            if (k >= d) {
+#pragma unroll
+              for (int j = 0; j < W; ++j) cv[k][j] = (T)0;
+            }
+          }
+          pw_unpack<T>(*reinterpret_cast<const VT*>(ph + k0), bv);
+#pragma unroll
+          for (int j = 0; j < W; ++j)
+#pragma unroll
+            for (int s = 0; s < NH; ++s) {
+              T arg = bv[j];
+#pragma unroll
+              for (int k = 0; k < DK; ++k) arg += cv[k][j] * xr[s][k];
+              T cs, sn;
+              pw_sincos(arg, cs, sn);
+              accp[s] += wv4[s][j] * cs;
+              const T t = wv4[s][j] * sn;
+#pragma unroll
+              for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+            }
+#pragma unroll
+          for (int s = 0; s < NH; ++s) { wq[0][s] = wq[1][s]; wq[1][s] = wq[2][s]; }
+        }
+        // ONE accumulator set for both halves of the stream, as in the narrow pass
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          const double scv = xscale[a * d + (k < d ? k : 0)];
+          const double den = 0.6931471805599453 * var[a] * scv;
+          const T fj = (k < d && den != 0.0) ? (T)(-6.283185307179586 * pscale[a] / den) : (T)0;
+#pragma unroll
+          for (int s = 0; s < NH; ++s) accJ[s][k] *= fj;
+        }
+      }
+      // ---- update part
+      {
+        T xsc[NH][DK], hx[NH];
+#pragma unroll
+        for (int s = 0; s < NH; ++s) {
+          T h = (T)0;
+#pragma unroll
+          for (int k = 0; k < DK; ++k) {
+            const T scv = (T)xscale[a * d + (k < d ? k : 0)];
+            const T sc = (k < d) ? scv : (T)0;
+            xsc[s][k] = xr[s][k] * sc; h += xsc[s][k] * xsc[s][k];
+          }
+          hx[s] = (T)0.5 * h;
+        }
+        const T* zz = zs + (size_t)a * M * d;
+        const T* hh = hz + (size_t)a * M;
+        const T* vrow = hrow + (size_t)nbK * NS * BT;
+        VT vq[3][NH];
+#pragma unroll
+        for (int pf = 0; pf < 2; ++pf)
+#pragma unroll
+          for (int s = 0; s < NH; ++s)
+            vq[pf][s] = *reinterpret_cast<const VT*>(vrow + ((size_t)(pf < nbM ? pf : nbM - 1) * NS + s) * BT);
+        for (int pidx = 0; pidx < nbM; ++pidx) {
+          const int m0 = lane * W + pidx * BT;
+#pragma unroll
+          for (int s = 0; s < NH; ++s)
+            vq[2][s] = *reinterpret_cast<const VT*>(vrow + ((size_t)(pidx + 2 < nbM ? pidx + 2 : nbM - 1) * NS + s) * BT);
+          T vv[NH][W], cv[DK][W], hv[W];
+#pragma unroll
+          for (int s = 0; s < NH; ++s) pw_unpack<T>(vq[0][s], vv[s]);
+#pragma unroll
+          for (int k = 0; k < DK; ++k) {
+            pw_unpack<T>(*reinterpret_cast<const VT*>(zz + (size_t)(k < d ? k : 0) * M + m0), cv[k]);
+            if (k >= d) {
+#pragma unroll
+              for (int j = 0; j < W; ++j) cv[k][j] = (T)0;
+            }
+          }
+          pw_unpack<T>(*reinterpret_cast<const VT*>(hh + m0), hv);
+#pragma unroll
+          for (int j = 0; j < W; ++j)
+#pragma unroll
+            for (int s = 0; s < NH; ++s) {
+              T arg = -hv[j] - hx[s];
+#pragma unroll
+              for (int k = 0; k < DK; ++k) arg += cv[k][j] * xsc[s][k];
+              const T e = PW_EXP(arg);
+              const T t = vv[s][j] * e;
+              accu[s] += t;
+#pragma unroll
+              for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+            }
+#pragma unroll
+          for (int s = 0; s < NH; ++s) { vq[0][s] = vq[1][s]; vq[1][s] = vq[2][s]; }
+        }
+        const T fj = (T)(0.6931471805599453 * var[a]);
+#pragma unroll
+        for (int s = 0; s < NH; ++s)
+#pragma unroll
+          for (int k = 0; k < DK; ++k) {
+            const T scv = (T)xscale[a * d + (k < d ? k : 0)];
+            const T sc = (k < d) ? scv : (T)0;
+            accJ[s][k] = fj * sc * (accJ[s][k] - xsc[s][k] * accu[s]);
+          }
+      }
+      // ---- wave reduction, one value and DK Jacobian entries per sample
+      const double ps = pscale[a], vr = var[a], mc = meanc ? meanc[a] : 0.0;
+#pragma unroll
+      for (int s = 0; s < NH; ++s) {
+        const double t = pw_wave_sum63(ps * (double)accp[s] + vr * (double)accu[s]);
+        if (lane == 63 && s0 + s < S) {
+          double f = t + mc;
+          if (euler) f = (double)x[(size_t)(s0 + s) * d + a] + dt * f;
+          out[(size_t)(s0 + s) * L + a] = (T)f;
+          if (traj) traj[(size_t)(s0 + s) * L + a] = (T)f;
+        }
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          const T jv = pw_wave_sum63(accJ[s][k]);
+          if (lane == 63 && s0 + s < S && k < d) jac[((size_t)(s0 + s) * L + a) * d + k] = jv;
+        }
+      }
+    }
+  }
+}
+
+// k_pathwise_lds<T, DK, true, false>, DK > 8, after the operands are staged: the wave's work is ONE flat sequence of
+// half-blocks (its groups back to back, per group first half then second, NB blocks each) through the same register ring.
+// f32: the two samples of a half are ONE packed pair (the PK form of the narrow pass, with NP = 1).
+template <typename T, int DK>
+__device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, int NB, int d, int nW, int a, int wgi, int wv,
+                                                int lane, const T* __restrict__ op, const T (&sc)[DK], double ps, double vr,
+                                                double mc, const T* __restrict__ x, const T* __restrict__ wb,
+                                                T* __restrict__ out, T* __restrict__ traj, T* __restrict__ jac, int euler,
+                                                double dt) {
+  typedef typename PwVec<T>::type VT;
+  constexpr int W = PwVec<T>::W, NS = MM_PW_NS, NH = PW_WIDE_NH, NHALF = NS / NH, BT = 64 * W, NWAVE = PW_LDS_WAVES;
+  constexpr bool PK = sizeof(T) == 4;
+  static_assert(NH == 2, "a half is one packed sample pair");
+  const int ngroups = (S + NS - 1) / NS;
+  const int g_first = wgi * NWAVE + wv, g_stride = nW * NWAVE;
+  if (g_first >= ngroups) return;
+  const int n_mine = (ngroups - g_first + g_stride - 1) / g_stride;
+  const int total = n_mine * NHALF * NB;
+  int ld_g = g_first, ld_h = 0, ld_tb = 0;               // next half-block to load (past the end: the last one again)
+  auto load_next = [&](VT (&q)[NH]) {
+    const T* ptr = wb + ((((size_t)ld_g * L + a) * NB + ld_tb) * NS + ld_h * NH) * BT + lane * W;
+#pragma unroll
+    for (int s = 0; s < NH; ++s) q[s] = *reinterpret_cast<const VT*>(ptr + (size_t)s * BT);
+    if (ld_tb + 1 < NB) ++ld_tb;
+    else if (ld_h + 1 < NHALF) { ++ld_h; ld_tb = 0; }
+    else if (ld_g + g_stride < ngroups) { ld_g += g_stride; ld_h = 0; ld_tb = 0; }
+  };
+  int cg = g_first, ch = 0, ctb = 0;                     // half-block being consumed
+  T xr[NH][DK], hx[NH], accp[NH], accu[NH], accJ[NH][PK ? 1 : DK];
+  pwf2 xr2[PK ? DK : 1], hx2, accp2, accu2, accJ2[PK ? DK : 1];
+  auto consume = [&](const VT (&q)[NH]) {
+    const int s0 = cg * NS + ch * NH;
+    if (ctb == 0) {                                      // new half: its two states (wave-uniform loads)
+#pragma unroll
+      for (int s = 0; s < NH; ++s) {
+        const int row = (s0 + s < S) ? s0 + s : S - 1;
+        T h = (T)0;
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          const T v = x[(size_t)row * d + (k < d ? k : 0)];
+          xr[s][k] = (k < d) ? v : (T)0;
+          const T xs = xr[s][k] * sc[k];
+          h += xs * xs;
+        }
+        hx[s] = (T)0.5 * h;
+        accp[s] = (T)0; accu[s] = (T)0;
+#pragma unroll
+        for (int k = 0; k < (PK ? 1 : DK); ++k) accJ[s][k] = (T)0;
+      }
+      if constexpr (PK) {
+        hx2 = (pwf2){(float)hx[0], (float)hx[1]};
+        accp2 = (pwf2){0.0f, 0.0f}; accu2 = (pwf2){0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          xr2[k] = (pwf2){(float)xr[0][k], (float)xr[1][k]};
+          accJ2[k] = (pwf2){0.0f, 0.0f};
+        }
+      }
+    }
+    T wv4[NH][W], cv[DK][W], sv[W];
+#pragma unroll
+    for (int s = 0; s < NH; ++s) pw_unpack<T>(q[s], wv4[s]);
+    const int col = ctb * BT + lane * W;
+#pragma unroll
+    for (int k = 0; k < DK; ++k) pw_unpack<T>(*reinterpret_cast<const VT*>(op + (size_t)k * KT + col), cv[k]);
+    pw_unpack<T>(*reinterpret_cast<const VT*>(op + (size_t)DK * KT + col), sv);
+    const double den = 0.6931471805599453 * vr;
+    const T fjp = den != 0.0 ? (T)(-6.283185307179586 * ps / den) : (T)0;   // prior sums -> the update half's units
+    if constexpr (PK) {
+      if (ctb < nbK) {                                   // wave-uniform: prior block
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          pwf2 arg = PW_B2(sv[j]);
+#pragma unroll
+          for (int k = 0; k < DK; ++k) arg = __builtin_elementwise_fma(PW_B2(cv[k][j]), xr2[k], arg);
+          float c0, s0f, c1, s1f;
+          pw_sincos(arg[0], c0, s0f); pw_sincos(arg[1], c1, s1f);
+          const pwf2 w2 = {(float)wv4[0][j], (float)wv4[1][j]};
+          accp2 = __builtin_elementwise_fma(w2, (pwf2){c0, c1}, accp2);
+          const pwf2 t2 = w2 * (pwf2){s0f, s1f};
+#pragma unroll
+          for (int k = 0; k < DK; ++k) accJ2[k] = __builtin_elementwise_fma(t2, PW_B2(cv[k][j]), accJ2[k]);
+        }
+        if (ctb == nbK - 1) {
+#pragma unroll
+          for (int k = 0; k < DK; ++k) accJ2[k] = accJ2[k] * PW_B2(fjp);
+        }
+      } else {                                           // update block
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          pwf2 arg = PW_B2(-(float)sv[j]) - hx2;
+#pragma unroll
+          for (int k = 0; k < DK; ++k) arg = __builtin_elementwise_fma(PW_B2(cv[k][j]), xr2[k], arg);
+          const pwf2 e2 = {pw_exp(arg[0]), pw_exp(arg[1])};
+          const pwf2 t2 = (pwf2){(float)wv4[0][j], (float)wv4[1][j]} * e2;
+          accu2 = accu2 + t2;
+#pragma unroll
+          for (int k = 0; k < DK; ++k) accJ2[k] = __builtin_elementwise_fma(t2, PW_B2(cv[k][j]), accJ2[k]);
+        }
+      }
+    } else {
+      if (ctb < nbK) {
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+#pragma unroll
+          for (int s = 0; s < NH; ++s) {
+            T arg = sv[j];
+#pragma unroll
+            for (int k = 0; k < DK; ++k) arg += cv[k][j] * xr[s][k];
+            T cs, sn;
+            pw_sincos(arg, cs, sn);
+            accp[s] += wv4[s][j] * cs;
+            const T t = wv4[s][j] * sn;
+#pragma unroll
+            for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+          }
+        if (ctb == nbK - 1) {
+#pragma unroll
+          for (int s = 0; s < NH; ++s)
+#pragma unroll
+            for (int k = 0; k < DK; ++k) accJ[s][k] *= fjp;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+#pragma unroll
+          for (int s = 0; s < NH; ++s) {
+            T arg = -sv[j] - hx[s];
+#pragma unroll
+            for (int k = 0; k < DK; ++k) arg += cv[k][j] * xr[s][k];
+            const T e = PW_EXP(arg);
+            const T t = wv4[s][j] * e;
+            accu[s] += t;
+#pragma unroll
+            for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+          }
+      }
+    }
+    if (ctb == NB - 1) {                                 // half done: reduce, Euler update, store
+      if constexpr (PK) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) { accp[hh] = (T)accp2[hh]; accu[hh] = (T)accu2[hh]; }
+      }
+      const T fj = (T)(0.6931471805599453 * vr);
+#pragma unroll
+      for (int s = 0; s < NH; ++s) {
+        const double t = pw_wave_sum63(ps * (double)accp[s] + vr * (double)accu[s]);
+        if (lane == 63 && s0 + s < S) {
+          double f = t + mc;
+          if (euler) f = (double)x[(size_t)(s0 + s) * d + a] + dt * f;
+          out[(size_t)(s0 + s) * L + a] = (T)f;
+          if (traj) traj[(size_t)(s0 + s) * L + a] = (T)f;
+        }
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          T aj;
+          if constexpr (PK) aj = (T)accJ2[k][s]; else aj = accJ[s][k];
+          const T jv = pw_wave_sum63(fj * (aj - sc[k] * sc[k] * xr[s][k] * accu[s]));
+          if (lane == 63 && s0 + s < S && k < d) jac[((size_t)(s0 + s) * L + a) * d + k] = jv;
+        }
+      }
+      ctb = 0;
+      if (ch + 1 < NHALF) ++ch; else { ch = 0; cg += g_stride; }
+    } else {
+      ++ctb;
+    }
+  };
+  VT q[PW_RING][NH];
+#pragma unroll
+  for (int r = 0; r < PW_RING - 1; ++r) load_next(q[r]);
+  for (int i = 0; i < total; i += PW_RING) {
+#pragma unroll
+    for (int r = 0; r < PW_RING; ++r) {
+      load_next(q[(r + PW_RING - 1) % PW_RING]);
+      if (r == 0 || i + r < total) consume(q[r]);
+    }
+  }
+}
+
 // JAC (both kernels): the same pass also emits the per-sample Jacobian d f_{s,a} / d x_s [S][L][d] -- what the reverse sweep of
 // a differentiated sample rollout needs (the reference differentiates the pathwise loss with a gradient tape:
 // examples/cartpole_swingup/train_utils.py:108-135 through loops/pilco.py:263-298):
@@ -128,6 +489,10 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
   typedef typename PwVec<T>::type VT;
   constexpr int W = PwVec<T>::W, NS = MM_PW_NS, BT = 64 * W;     // BT terms per pass of a wave
   constexpr int NJ = JAC ? DK : 1;
+  if constexpr (JAC && DK > 8) {                    // the wide Jacobian pass: half-groups (pw_wide_jac above)
+    pw_wide_jac<T, DK>(S, L, M, K, d, x, omega, phase, zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, euler, dt);
+    return;
+  }
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int g = blockIdx.x, s0 = g * NS;
   const int nbK = K / BT, nbM = M / BT, NB = nbK + nbM;
@@ -371,6 +736,10 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
     sc[k] = (k < d) ? v : (T)0;
   }
   const double ps = pscale[a], vr = var[a], mc = meanc ? meanc[a] : 0.0;
+  if constexpr (JAC && DK > 8) {                    // the wide Jacobian pass: half-groups (pw_wide_jac_lds above)
+    pw_wide_jac_lds<T, DK>(S, L, KT, nbK, NB, d, nW, a, wgi, wv, lane, op, sc, ps, vr, mc, x, wb, out, traj, jac, euler, dt);
+    return;
+  }
 
   // The wave's work is ONE flat sequence of weight blocks (its groups back to back, NB blocks each),
   // consumed through PW_RING register sets in rotation: blocks i + 1 .. i + PW_RING - 1 are in flight
@@ -591,7 +960,7 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
                      const double* meanc, const T* wb, T* out, T* traj, int euler, double dt, hipStream_t s,
                      T* jac = nullptr, T* cnd = nullptr) {
   if (jac && cnd) return MM_E_ARG;                  // (one extra output per pass)
-  if (jac && d > 8) return MM_E_DIM;               // the Jacobian pass keeps (1 + d) accumulators per sample: d <= 8
+  if (jac && d > 16) return MM_E_DIM;              // the Jacobian pass: d <= 8 whole groups, 8 < d <= 16 half-groups
   // LDS-resident operands when one latent's (d + 1) x (K + M) block fits (<= 144 KB)
   const int dk = d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : 32;
   const size_t lds_bytes = (size_t)(dk + 1) * (K + M) * sizeof(T);      // rows d..dk-1 are zero padding
@@ -619,7 +988,7 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
 #define PW_LAUNCH_LDS_NJ(DK_) do { if (cnd) PW_LAUNCH_LDS_(DK_, false, true); else PW_LAUNCH_LDS_(DK_, false, false); } while (0)
     if (d <= 4) PW_LAUNCH_LDS(4);
     else if (d <= 8) PW_LAUNCH_LDS(8);
-    else if (d <= 16) PW_LAUNCH_LDS_NJ(16);
+    else if (d <= 16) PW_LAUNCH_LDS(16);
     else PW_LAUNCH_LDS_NJ(32);
 #undef PW_LAUNCH_LDS_NJ
 #undef PW_LAUNCH_LDS
@@ -634,7 +1003,7 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
 #define PW_LAUNCH_NJ(DK_) do { if (cnd) PW_LAUNCH_(DK_, false, true); else PW_LAUNCH_(DK_, false, false); } while (0)
   if (d <= 4) PW_LAUNCH(4);
   else if (d <= 8) PW_LAUNCH(8);
-  else if (d <= 16) PW_LAUNCH_NJ(16);
+  else if (d <= 16) PW_LAUNCH(16);
   else PW_LAUNCH_NJ(32);
 #undef PW_LAUNCH_NJ
 #undef PW_LAUNCH

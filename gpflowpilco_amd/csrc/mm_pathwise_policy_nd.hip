@@ -7,7 +7,9 @@
 //     x_{h+1} = x_h + dt f_s([e, u_0 .. u_{nu-1}])                        nd = ne + nu drift inputs, actions in latent order
 //     cost[h][s] = -exp(-(enc(x_{h+1}) - t)^T W (enc(x_{h+1}) - t) / 2)
 // (the torch composition's forward_sde tensor branch appends the policy's outputs to the encoding in this order).  The weight
-// stream (mm_pathwise_launch and its Jacobian variant) takes any d <= 8 and is used as it is.  New here: the head kernel
+// stream (mm_pathwise_launch and its Jacobian variant: d <= 16) is used as it is.  Two sets of entries share ONE implementation:
+// the _nd entries keep their bound nd <= 8, the _wide entries (same signatures) take nd <= 16 -- the cart-double-pendulum (nx 6,
+// two angles, one force: nd 9), a three-link arm (nd 13).  New here: the head kernel
 // (k_pw_head_nd), the one-kernel reverse sweep (k_pw_policy_bwd_nd) and their entries.  The policy is an ordinary mm_pack_model
 // pack with L = nu; only its f64 blocks are read (Z64 [L][M][ne], beta64 [L][M], ls2 [L][ne], var [L], meanc [L]).
 //
@@ -17,9 +19,9 @@
 // LDS of the reverse sweep (doubles per workgroup of four waves): the nu policy blocks nu (M ne + M + ne), target and W
 // (ne + ne^2, + 8 spare), and one gradient slab per wave 4 nu (M ne + M + ne + 2).  The kernel takes a shape when
 //     8 (nu (M ne + M + ne) + ne + ne^2 + 8 + 4 nu (M ne + M + ne + 2))  <=  160 KiB        (MMP_ND_LDS_MAX)
-// -- every shape with M <= 64 and ne + nu <= 8 (largest: nu 4, ne 4, M 64: 52 KB); at M = 256: nu (ne + 1) <= 15, i.e. nu = 1
+// -- every shape with M <= 64 and ne + nu <= 16 (tightest: nu 4, ne 12, which stops at M = 77); within ne + nu <= 8 at M = 256: nu (ne + 1) <= 15, i.e. nu = 1
 // (any ne <= 7), nu = 2 (ne <= 6: the double pendulum, 144 KB), nu = 3 with ne <= 4; not nu = 3 with ne = 5 (M <= 226 fits) and
-// not nu = 4 with ne = 4 (M <= 203 fits).  mm_pathwise_backward_scratch_bytes_nd returns 0 and the entry MM_E_DIM beyond it.
+// not nu = 4 with ne = 4 (M <= 203 fits).  mm_pathwise_backward_scratch_bytes_nd / _wide return 0 and the entries MM_E_DIM beyond it.
 #include "mm_pathwise_policy_dev.h"
 
 #define MMP_ND_LDS_MAX ((size_t)160 * 1024)
@@ -183,12 +185,13 @@ static inline size_t mmp_nd_bwd_lds(int pM, int ne, int nu) {
 
 // everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions
 static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, int nu, const int32_t* active_dims, int policy_M,
-                        MMComposeDims& D) {
+                        int nd_max, MMComposeDims& D) {
   if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || !active_dims) return MM_E_ARG;
   if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
   const int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
   if (rc) return rc;
-  if (D.nd > 8 || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;   // the Jacobian pass of the weight stream: nd <= 8
+  // nd_max: 8 for the _nd entries (the Jacobian pass over whole sample groups), 16 for the _wide ones (+ its half-group form)
+  if (D.nd > nd_max || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;
   return 0;
 }
 
@@ -220,6 +223,11 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
   const dim3 grid((S + 255) / 256);
   for (int h = 0; h <= H; ++h) {
 #define MMP_HEAD(NU_)                                                                                                            \
+    if (h == 0 && lds > 64 * 1024) {   /* nu >= 3 policies on wide encodings: up to 108 KB at M = 256 */                          \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_head_nd<T, NU_>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
+                                          (int)lds);                                                                             \
+      if (ea != hipSuccess) return (int)ea;                                                                                      \
+    }                                                                                                                            \
     hipLaunchKernelGGL((k_pw_head_nd<T, NU_>), grid, dim3(256), lds, s, D, S, h, H, dt,                                          \
                        h > 0 ? xs + (size_t)(h - 1) * S * nx : (const T*)nullptr, (const T*)f, xs + (size_t)h * S * nx,          \
                        h < H ? dins + (size_t)h * S * nd : (T*)nullptr, cost, target, precis, (const double*)(pp + pl.Z64),      \
@@ -237,16 +245,17 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
   return 0;
 }
 
-extern "C" int mm_pathwise_policy_rollout_nd(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
-                                             const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
-                                             const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
-                                             const double* variance, const double* mean_c, const void* wb,
-                                             const void* policy_packed, size_t policy_bytes, int policy_M,
-                                             const double* head_scale, const double* head_shift, const void* target,
-                                             const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
-                                             int with_jacobians, void* stream) {
+// the forward entries: _nd (nd_max = 8) and _wide (nd_max = 16) are this function
+static int mmp_nd_rollout(int nd_max, int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                          const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                          const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                          const double* variance, const double* mean_c, const void* wb,
+                          const void* policy_packed, size_t policy_bytes, int policy_M,
+                          const double* head_scale, const double* head_shift, const void* target,
+                          const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                          int with_jacobians, void* stream) {
   MMComposeDims D;
-  int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, D);
+  int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
   if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !head_scale ||
       !head_shift || !target || !precis || !x0 || !cost || !tape) return MM_E_ARG;
@@ -267,21 +276,43 @@ extern "C" int mm_pathwise_policy_rollout_nd(int S, int M, int K, int dtype, int
                                  (char*)tape, tl, s);
 }
 
+#define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
+  extern "C" int name_(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,      \
+                       const void* omega_t, const void* phase, const void* zs_t, const void* hz, const double* x_scale,          \
+                       const double* prior_scale, const double* variance, const double* mean_c, const void* wb,                  \
+                       const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
+                       const double* head_shift, const void* target, const void* precis, const void* x0, void* cost, void* tape, \
+                       size_t tape_bytes, int with_jacobians, void* stream) {                                                    \
+    return mmp_nd_rollout(nd_max_, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz, x_scale,            \
+                          prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,      \
+                          target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);                                   \
+  }
+MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_nd, 8)
+MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_wide, 16)
+#undef MMP_ROLLOUT_ENTRY
+
 // 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)
-extern "C" size_t mm_pathwise_backward_scratch_bytes_nd(int S, int policy_M, int ne, int nu) {
-  if (S <= 0 || policy_M <= 0 || policy_M > MMP_POLICY_MMAX || ne <= 0 || nu < 1 || nu > MMC_NU || ne + nu > 8) return 0;
+static size_t mmp_nd_scratch_bytes(int nd_max, int S, int policy_M, int ne, int nu) {
+  if (S <= 0 || policy_M <= 0 || policy_M > MMP_POLICY_MMAX || ne <= 0 || nu < 1 || nu > MMC_NU || ne + nu > nd_max) return 0;
   if (mmp_nd_bwd_lds(policy_M, ne, nu) > MMP_ND_LDS_MAX) return 0;
   return (size_t)((S + 255) / 256) * 4 * (size_t)nu * (size_t)(policy_M * ne + policy_M + ne + 2) * sizeof(double);
 }
+extern "C" size_t mm_pathwise_backward_scratch_bytes_nd(int S, int policy_M, int ne, int nu) {
+  return mmp_nd_scratch_bytes(8, S, policy_M, ne, nu);
+}
+extern "C" size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, int ne, int nu) {
+  return mmp_nd_scratch_bytes(16, S, policy_M, ne, nu);
+}
 
-extern "C" int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, double dt, int nx, int na,
-                                                      const int32_t* active_dims, int nu, const void* policy_packed,
-                                                      size_t policy_bytes, int policy_M, const double* head_scale,
-                                                      const double* head_shift, const void* target, const void* precis,
-                                                      const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
-                                                      void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+// the backward entries: _nd (nd_max = 8) and _wide (nd_max = 16) are this function
+static int mmp_nd_backward(int nd_max, int S, int dtype, int H, double dt, int nx, int na,
+                           const int32_t* active_dims, int nu, const void* policy_packed,
+                           size_t policy_bytes, int policy_M, const double* head_scale,
+                           const double* head_shift, const void* target, const void* precis,
+                           const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
+                           void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
   MMComposeDims D;
-  int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, D);
+  int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
   if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape || !g_cost || !g_policy || !scratch)
     return MM_E_ARG;
@@ -290,7 +321,7 @@ extern "C" int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, d
   if (lds > MMP_ND_LDS_MAX) return MM_E_DIM;
   const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, nu, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
-  if (scratch_bytes < mm_pathwise_backward_scratch_bytes_nd(S, policy_M, ne, nu)) return MM_E_WORKSPACE;
+  if (scratch_bytes < mmp_nd_scratch_bytes(nd_max, S, policy_M, ne, nu)) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, MM_F64, 1);
   if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
   MMHeadND hd;
@@ -321,3 +352,15 @@ extern "C" int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, d
   if (e != hipSuccess) return (int)e;
   return mm_pw_grad_sum_launch((const double*)scratch, (int)grid.x * 4, npar, (double*)g_policy, s);
 }
+
+#define MMP_BACKWARD_ENTRY(name_, nd_max_)                                                                                         \
+  extern "C" int name_(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,                    \
+                       const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
+                       const double* head_shift, const void* target, const void* precis, const void* tape, size_t tape_bytes,    \
+                       const void* g_cost, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {      \
+    return mmp_nd_backward(nd_max_, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M, head_scale,  \
+                           head_shift, target, precis, tape, tape_bytes, g_cost, g_policy, g_x0, scratch, scratch_bytes, stream); \
+  }
+MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_nd, 8)
+MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_wide, 16)
+#undef MMP_BACKWARD_ENTRY

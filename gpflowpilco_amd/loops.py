@@ -385,7 +385,8 @@ class GraphedPolicyLoss:
 
 def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable, num_steps: int,
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
-                                 generator: Optional[torch.Generator] = None, native_actions: int = 1) -> Callable:
+                                 generator: Optional[torch.Generator] = None, native_actions: int = 1,
+                                 native_inputs: int = 8) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -405,7 +406,14 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   actions on the torch composition (with the "nu > 1" warning; ``native=True`` raises).  With ``native_actions >= nu`` such a
   policy runs in the multi-action native rollout (csrc/mm_pathwise_policy_nd.hip), forward and gradient, where
   nx + na + nu <= 8, the policy has <= 256 centres and -- when a gradient is asked for -- the reverse sweep takes the shape
-  (``PolicyRollout.supports_backward``); every other case falls back and names its reason."""
+  (``PolicyRollout.supports_backward``); every other case falls back and names its reason.
+
+  ``native_inputs``: the largest drift input dimension nd = nx + na + nu the closure may run natively.  The default 8 is the
+  routing above.  With ``native_inputs=16`` a system with 8 < nd <= 16 (the cart-double-pendulum: nx 6, two angles, one force,
+  nd 9) runs in the wide entries (``PolicyRollout(wide=True)``: the Jacobian pass of the weight stream over half sample groups),
+  forward and gradient, for any number of actions ``native_actions`` admits; nd > 16 or a gradient outside the reverse sweep's
+  LDS bound falls back once, naming the bound (the forward stays native in the latter case).  Values above 16 behave as 16.
+  The torch composition itself is differentiable for nd <= 16 (``Paths.__call__``)."""
   from . import ops
   from .pathwise import PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
   drift = system.drift
@@ -417,6 +425,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
   max_native = int(native_actions)
+  max_nd = min(16, int(native_inputs))
   if native is True and parts[1].num_latent_gps > max(1, max_native):
     raise ValueError("native=True: the native pathwise rollout is one-action" if max_native <= 1 else
                      f"native=True: the policy has {parts[1].num_latent_gps} actions, native_actions={max_native}")
@@ -457,12 +466,17 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
                 f"the policy has nu = {nu} actions (nu > 1) and native_actions = {max_native}")
       return _torch_loss(x0, pth)
     pol_M = max(iv.Z.shape[0] for iv in pm_.inducing_variable.inducing_variables[:nu])
-    if nu == 1:
-      if nx + na + 1 > 8 or pol_M > 256:
+    nd = nx + na + nu
+    if max_nd > 8:
+      if nd > max_nd or pol_M > 256:
+        _fallback(f"drift inputs of dimension nx + na + nu = {nd} > {max_nd} or a policy of more than 256 centres ({pol_M})")
+        return _torch_loss(x0, pth)
+    elif nu == 1:
+      if nd > 8 or pol_M > 256:
         _fallback("drift inputs of dimension > 8 or a policy of more than 256 centres")
         return _torch_loss(x0, pth)
-    elif nx + na + nu > 8 or pol_M > 256:
-      _fallback(f"drift inputs of dimension nx + na + nu = {nx + na + nu} > 8 or a policy of more than 256 centres ({pol_M})")
+    elif nd > 8 or pol_M > 256:
+      _fallback(f"drift inputs of dimension nx + na + nu = {nd} > 8 or a policy of more than 256 centres ({pol_M})")
       return _torch_loss(x0, pth)
     outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
                "objective.target": objective.target, "objective.precis": objective.precis}
@@ -475,7 +489,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     scale, shift = head_constants()
     pol_pack = pm_.packed(torch.float64, False, x0.device)
     roll = PolicyRollout(pth, pol_pack, nx=nx, active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
-                         target=objective.target, precis=objective.precis)
+                         target=objective.target, precis=objective.precis, wide=nd > 8)
     needs = grad and (x0.requires_grad or any(t.requires_grad for t in pm_._parameters()))
     if needs and not roll.supports_backward():
       _fallback(f"the native reverse sweep does not take nu = {nu} actions with {pol_M} centres on {nx + na} inputs (its LDS bound)")

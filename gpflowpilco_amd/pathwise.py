@@ -57,7 +57,7 @@ class Paths:
     return self.num_samples, L, self.zs.shape[-1], Kp, d
 
   def __call__(self, x: torch.Tensor) -> torch.Tensor:
-    """f_s(x_s): x [S, d] -> [S, L].  Differentiable in x where the Jacobian pass exists (d <= 8): the torch composition of a
+    """f_s(x_s): x [S, d] -> [S, L].  Differentiable in x where the Jacobian pass exists (d <= 16): the torch composition of a
     sample rollout (``loops.pathwise_policy_loss_closure``'s fallback) then carries gradients through the paths."""
     if torch.is_grad_enabled() and x.requires_grad:
       return _PathsEval.apply(x, self)
@@ -76,7 +76,8 @@ class Paths:
     return out
 
   def eval_jac(self, x: torch.Tensor):
-    """f_s(x_s) and its Jacobian: x [S, d] -> (f [S, L], d f / d x [S, L, d]) from ONE pass over the weight stream (d <= 8)."""
+    """f_s(x_s) and its Jacobian: x [S, d] -> (f [S, L], d f / d x [S, L, d]) from ONE pass over the weight stream (d <= 16; for
+    d > 8 a wave takes the four samples of a group two at a time).  f is bit-equal to ``__call__``'s."""
     _require_device(x, self.wb)
     S, L, Mp, Kp, d = self._dims()
     if x.shape != (S, d) or x.dtype != self.dtype:
@@ -247,17 +248,18 @@ class PolicyRollout:
   Chain[Scale, Shift, NormalCDF] -> drift sample -> Euler -> cost -- the body of ``PathwisePILCO._policy_loss_closure``
   (gpflow_pilco/loops/pilco.py:263-298).
 
-  ``paths``: the drift's sample paths (nx latents on nd = nx + na + nu inputs, nd <= 8); ``policy``: an ``ops.PackedModel`` with
+  ``paths``: the drift's sample paths (nx latents on nd = nx + na + nu inputs, nd <= 8; ``wide=True``: nd <= 16); ``policy``: an ``ops.PackedModel`` with
   one latent per action (nu = 1 .. 4) on ne = nx + na inputs (any dtype: only its float64 blocks are read); ``head_scale`` /
   ``head_shift``: a float, or one value per action.  The actions follow the encoding in latent order.  A one-latent pack with
-  float head constants runs the one-action entries; nu > 1 (or ``nd_entries=True``) the ``_nd`` entries.
+  float head constants runs the one-action entries; nu > 1 (or ``nd_entries=True``) the ``_nd`` entries.  ``wide=True``: the
+  ``_wide`` entries (same signatures and results, any nu), which take nd <= 16.
   ``__call__(x0, H)`` -> ``(cost [H, S], tape)``; ``backward(tape, g_cost)`` -> ``(g_policy, g_x0 [S, nx] | None)`` with
   g_policy [M ne + M + ne + 2] from the one-action entries and [nu, M ne + M + ne + 2] from the ``_nd`` ones (per latent dZ,
   dbeta, d ls^2, dvar, dmean).  ``supports_backward()``: whether the reverse sweep takes this shape (its LDS bound:
   include/gpflowpilco_mm.h)."""
 
   def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
-               target: torch.Tensor, precis: torch.Tensor, nd_entries: Optional[bool] = None):
+               target: torch.Tensor, precis: torch.Tensor, nd_entries: Optional[bool] = None, wide: bool = False):
     S, L, Mp, Kp, d = paths._dims()
     self.paths, self.policy = paths, policy
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
@@ -269,8 +271,10 @@ class PolicyRollout:
     if L != self.nx or d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: paths L={L} d={d} (want {self.nx}, {self.nd}), policy L={policy.L} d={policy.d} "
                        f"(want {self.nu}, {self.ne})")
-    if self.nd > 8 or policy.M > 256:
-      raise ValueError("the pathwise policy rollout takes drift inputs of dimension <= 8 and policies of <= 256 centres")
+    self.wide = bool(wide)
+    if self.nd > (16 if self.wide else 8) or policy.M > 256:
+      raise ValueError(f"the pathwise policy rollout takes drift inputs of dimension <= {16 if self.wide else 8} and policies of "
+                       "<= 256 centres")
 
     def per_action(v, what):
       if isinstance(v, torch.Tensor):
@@ -282,7 +286,9 @@ class PolicyRollout:
         raise ValueError(f"{what}: expected a float or one value per action ({self.nu}), got {len(vals)}")
       return vals
     scales, shifts = per_action(head_scale, "head_scale"), per_action(head_shift, "head_shift")
-    self.nd_entries = (self.nu > 1) if nd_entries is None else bool(nd_entries)
+    self.nd_entries = (self.nu > 1 or self.wide) if nd_entries is None else bool(nd_entries)
+    if self.wide and not self.nd_entries:
+      raise ValueError("nd_entries=False: the wide entries have the _nd signatures")
     if self.nu > 1 and not self.nd_entries:
       raise ValueError("nd_entries=False: the one-action entries take one-latent policies")
     if self.nd_entries:
@@ -293,6 +299,7 @@ class PolicyRollout:
     self.target = target.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
     self.precis = precis.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
+    self._sfx = "wide" if self.wide else "nd"                  # which set of entries with the _nd signatures
 
   def _policy(self, policy):
     pol = self.policy if policy is None else policy
@@ -302,7 +309,8 @@ class PolicyRollout:
 
   def supports_backward(self) -> bool:
     """False where the reverse sweep's per-workgroup LDS (the nu policy blocks + four gradient slabs) exceeds 160 KiB."""
-    return _lib.lib().mm_pathwise_backward_scratch_bytes_nd(self.paths.num_samples, self.policy.M, self.ne, self.nu) > 0
+    query = getattr(_lib.lib(), f"mm_pathwise_backward_scratch_bytes_{self._sfx}")
+    return query(self.paths.num_samples, self.policy.M, self.ne, self.nu) > 0
 
   def __call__(self, x0: torch.Tensor, num_steps: int, dt: float = 1.0, with_jacobians: bool = False, policy=None):
     pol = self._policy(policy)
@@ -323,14 +331,15 @@ class PolicyRollout:
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
     if self.nd_entries:
-      rc = lib.mm_pathwise_policy_rollout_nd(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
-                                             P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
-                                             P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
-                                             _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
-                                             self._scale_c, self._shift_c, self.target.data_ptr(), self.precis.data_ptr(),
-                                             x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                                             int(with_jacobians), _stream(x0.device))
-      check(rc, "mm_pathwise_policy_rollout_nd")
+      entry = f"mm_pathwise_policy_rollout_{self._sfx}"
+      rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
+                               P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
+                               P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
+                               _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
+                               self._scale_c, self._shift_c, self.target.data_ptr(), self.precis.data_ptr(),
+                               x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
+                               int(with_jacobians), _stream(x0.device))
+      check(rc, entry)
       return cost, tape
     rc = lib.mm_pathwise_policy_rollout(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act,
                                         P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
@@ -361,18 +370,19 @@ class PolicyRollout:
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
     lib = _lib.lib()
     if self.nd_entries:
-      ns = lib.mm_pathwise_backward_scratch_bytes_nd(S, pol.M, self.ne, self.nu)
+      ns = getattr(lib, f"mm_pathwise_backward_scratch_bytes_{self._sfx}")(S, pol.M, self.ne, self.nu)
       if ns == 0:
         raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
                          "slabs exceed 160 KiB of LDS (see supports_backward)")
       g_pol = torch.empty(self.nu, npar, dtype=torch.float64, device=dev)
       scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
-      rc = lib.mm_pathwise_policy_rollout_backward_nd(S, code, H, float(dt), self.nx, self.na, self._act, self.nu,
-                                                      pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c,
-                                                      self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(),
-                                                      tape.numel(), g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0),
-                                                      scratch.data_ptr(), scratch.numel(), _stream(dev))
-      check(rc, "mm_pathwise_policy_rollout_backward_nd")
+      entry = f"mm_pathwise_policy_rollout_backward_{self._sfx}"
+      rc = getattr(lib, entry)(S, code, H, float(dt), self.nx, self.na, self._act, self.nu,
+                               pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c,
+                               self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(),
+                               tape.numel(), g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0),
+                               scratch.data_ptr(), scratch.numel(), _stream(dev))
+      check(rc, entry)
       return g_pol, g_x0
     g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
     ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)

@@ -386,8 +386,10 @@ int mm_pathwise_rollout(int S, int L, int M, int K, int d, int dtype, int H, dou
                         const double* variance, const double* mean_c, const void* wb,
                         void* traj, void* stream);
 
-/* The same evaluation that also emits the per-sample Jacobian d f[s,a] / d x[s,:]  (jac_out [S,L,d] T; d <= 8): in the SAME pass
- * over the weight stream (d more FMAs and, in the prior blocks, one more transcendental per term and sample). */
+/* The same evaluation that also emits the per-sample Jacobian d f[s,a] / d x[s,:]  (jac_out [S,L,d] T; d <= 16, MM_E_DIM beyond):
+ * in the SAME pass over the weight stream (d more FMAs and, in the prior blocks, one more transcendental per term and sample).
+ * d <= 8: a wave keeps the sums of a whole group of four samples; 8 < d <= 16: it walks the group's blocks twice, two samples at
+ * a time (their weights are separate rows of every block, so nothing is read twice).  f_out is bit-equal to mm_pathwise_eval's. */
 int mm_pathwise_eval_jac(int S, int L, int M, int K, int d, int dtype,
                          const void* x, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
                          const double* x_scale, const double* prior_scale, const double* variance,
@@ -452,6 +454,28 @@ int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, double dt, i
                                            const void* target, const void* precis,
                                            const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                            void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- the same entries for WIDER systems: nd = nx + na + nu <= 16 (1 <= nu <= 4) ---------------------------------------------
+ * Signatures, operands, tape (mm_pathwise_tape_bytes_nd: it has no bound on nd), results and error codes of the _nd entries; one
+ * implementation serves both, so for nd <= 8 the results are bit-equal.  The cart-double-pendulum (nx 6, two angles, one force)
+ * has nd 9, a three-link arm nd 13.  Refused with MM_E_DIM: nd > 16, nu outside 1..4, policy_M > 256, and -- the reverse sweep
+ * only -- a shape outside the LDS bound above (with ne up to 15): every shape with M <= 64 fits; the tightest case, nu 4 on
+ * ne 12, stops at M = 77.  mm_pathwise_backward_scratch_bytes_wide returns 0 for what the backward entry refuses. */
+int mm_pathwise_policy_rollout_wide(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                    int nu, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                                    const double* x_scale, const double* prior_scale, const double* variance,
+                                    const double* mean_c, const void* wb,
+                                    const void* policy_packed, size_t policy_bytes, int policy_M,
+                                    const double* head_scale, const double* head_shift,
+                                    const void* target, const void* precis, const void* x0, void* cost,
+                                    void* tape, size_t tape_bytes, int with_jacobians, void* stream);
+size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, int ne, int nu);
+int mm_pathwise_policy_rollout_backward_wide(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                             int nu, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                             const double* head_scale, const double* head_shift,
+                                             const void* target, const void* precis,
+                                             const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
+                                             void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,10 @@ M = 2000, K = 1024 bases, policy M = 30, S = 8192 paths, H = 30), f32 and f64 pa
   two actions (nx = 4, two angles, nd = 8): native forward and native loss + gradient (native_actions=2), and the torch
     composition's forward and loss + gradient (native=False) on the same paths (float64 paths only: the torch composition
     evaluates the float64 policy models);
-  one action (cartpole: nx = 4, one angle, nd = 6) through the existing entries, same four figures, same process: the yardstick.
+  one action (cartpole: nx = 4, one angle, nd = 6) through the existing entries, same four figures, same process: the yardstick;
+  the cart-double-pendulum (nx = 6, angles (2, 4), one action, nd = 9) through ``native_inputs=16``: the wide entries and the
+    Jacobian pass over half sample groups, same four figures (its torch composition differentiates through the same pass).
+``--rows one_action,two_actions`` picks rows (the first two exist in earlier checkouts: run from the root of one for its numbers).
 The variants of one shape are timed in alternation (window r of every variant before window r + 1 of any).  ``--samples`` /
 ``--drift-M`` shrink the shape for a dry run; ``--native-only`` leaves the torch composition out (the run to put under
 ``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv).
@@ -190,7 +193,7 @@ def main_grad(args):
   print(json.dumps(res))
 
 
-def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True):
+def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True, native_inputs=8):
   from gpflowpilco_amd.loops import pathwise_policy_loss_closure
   from gpflowpilco_amd.pathwise import PathwiseSVGP
   na = len(active); ne = nx + na; nd = ne + nu
@@ -215,7 +218,8 @@ def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repe
   params = [pol.q_mu] + [iv.Z for iv in pol.inducing_variable.inducing_variables] + [k.lengthscales for k in ks] + [k.variance for k in ks]
   for t in params:
     t.requires_grad_(True)
-  native = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=True, native_actions=nu)
+  wide = {"native_inputs": native_inputs} if native_inputs > 8 else {}
+  native = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=True, native_actions=nu, **wide)
   composed = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=False)
 
   def forward(closure):
@@ -252,13 +256,14 @@ def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repe
 def main_pathwise(args):
   device = "cuda"
   res = {"tool": "bench_multiaction --pathwise", "label": args.label, "unit": "ms per step, eager"}
+  rows = {"two_actions": (4, (0, 1), 2, 40, 8), "one_action": (4, (1,), 1, 3, 8), "cart_double_pendulum": (6, (2, 4), 1, 70, 16)}
   for nm, dtype in (("f32", torch.float32), ("f64", F64)):
-    res[nm] = {
-        "two_actions": pathwise_shape(4, (0, 1), 2, args.drift_M, 1024, args.samples, args.steps, dtype, 40, device, args.inner,
-                                      args.repeats, not args.native_only),
-        "one_action": pathwise_shape(4, (1,), 1, args.drift_M, 1024, args.samples, args.steps, dtype, 3, device, args.inner,
-                                     args.repeats, not args.native_only)}
-    torch.cuda.empty_cache()
+    res[nm] = {}
+    for row in args.rows.split(","):
+      nx, active, nu, seed, native_inputs = rows[row]
+      res[nm][row] = pathwise_shape(nx, active, nu, args.drift_M, 1024, args.samples, args.steps, dtype, seed, device, args.inner,
+                                    args.repeats, not args.native_only, native_inputs)
+      torch.cuda.empty_cache()
   print(json.dumps(res))
 
 
@@ -271,6 +276,7 @@ def main():
   ap.add_argument("--label", default="")
   ap.add_argument("--pathwise", action="store_true")
   ap.add_argument("--native-only", action="store_true", help="--pathwise without the torch composition (for a kernel trace)")
+  ap.add_argument("--rows", default="two_actions,one_action,cart_double_pendulum", help="--pathwise: which shapes")
   ap.add_argument("--samples", type=int, default=8192)
   ap.add_argument("--drift-M", type=int, default=2000)
   ap.add_argument("--grad", action="store_true", help="moment-matched loss + gradient, native vs torch composition (see the docstring)")
