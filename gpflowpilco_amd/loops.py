@@ -386,7 +386,7 @@ class GraphedPolicyLoss:
 def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable, num_steps: int,
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
                                  generator: Optional[torch.Generator] = None, native_actions: int = 1,
-                                 native_inputs: int = 8) -> Callable:
+                                 native_inputs: int = 8, native_sampler: bool = False) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -413,9 +413,17 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   nd 9) runs in the wide entries (``PolicyRollout(wide=True)``: the Jacobian pass of the weight stream over half sample groups),
   forward and gradient, for any number of actions ``native_actions`` admits; nd > 16 or a gradient outside the reverse sweep's
   LDS bound falls back once, naming the bound (the forward stays native in the latter case).  Values above 16 behave as 16.
-  The torch composition itself is differentiable for nd <= 16 (``Paths.__call__``)."""
+  The torch composition itself is differentiable for nd <= 16 (``Paths.__call__``).
+
+  ``native_sampler``: with ``paths=None``, where the new paths of each call come from.  The default False calls
+  ``drift.generate_paths`` (torch, from nothing each time: Kuu and its factor included, every tensor newly allocated, one host
+  synchronisation).  True keeps one ``pathwise.PathSampler`` per (S, dtype, device) and draws from it -- on the native and on the
+  torch-composition route alike: the drift's factor is cached per version of its parameters, a draw allocates and synchronises
+  nothing, so a ``GraphedPolicyLoss`` of the closure captures, and each replay draws new paths (from the default generator:
+  ``generator`` must be None for that).  The paths of a call live in the sampler's static buffers until the next call.  With
+  ``paths`` given the option changes nothing."""
   from . import ops
-  from .pathwise import PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
+  from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
   drift = system.drift
   if not isinstance(drift, PathwiseSVGP):
     raise TypeError("pathwise_policy_loss_closure needs a PathwiseSVGP drift (gpflow_pilco/loops/pilco.py:230-236)")
@@ -450,10 +458,19 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
                        callbacks_and_initializers=((_accumulate_loss, loss0),), iterator="foldl")
     return loss
 
+  samplers = {}
+
+  def _new_paths(x0):
+    if not native_sampler:
+      return drift.generate_paths(x0.shape[0], num_bases, dtype=x0.dtype, device=x0.device, generator=generator)
+    key = (x0.shape[0], x0.dtype, str(x0.device))
+    if key not in samplers:
+      samplers[key] = PathSampler(drift, x0.shape[0], num_bases, dtype=x0.dtype, device=x0.device)
+    return samplers[key].draw(generator=generator)
+
   def _closure():
     x0 = state_initializer()
-    pth = paths if paths is not None else drift.generate_paths(x0.shape[0], num_bases, dtype=x0.dtype, device=x0.device,
-                                                                generator=generator)
+    pth = paths if paths is not None else _new_paths(x0)
     if parts is None or not x0.is_cuda or x0.ndim != 2:
       if x0.is_cuda and native is not False:
         _fallback(why_not[0] if why_not else f"state of rank {x0.ndim}")

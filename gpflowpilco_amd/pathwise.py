@@ -4,10 +4,15 @@ Mirrors the surface the reference uses from ``gpflow_sampling`` (un-vendored thi
 ``PathwiseSVGP.generate_paths(num_samples, num_bases, sample_axis=0)``,
 ``set_temporary_paths`` and ``predict_f_samples`` / ``__call__``
 (``gpflow_pilco/models/svgp.py:124-130``, ``loops/pilco.py:263-303``).  Path *generation*
-(sampling weights, one Cholesky solve per latent) is torch plumbing done once per rollout
-closure; path *evaluation* -- the per-step hot loop -- runs in ``mm_pathwise_eval`` /
-``mm_pathwise_rollout`` (``csrc/mm_pathwise.hip``).  Parity with gpflow_sampling is unpinned
-(see ``oracle/pathwise_oracle.py``).
+(sampling weights, one Cholesky solve per latent) runs on EVERY call of a rollout closure that
+is not handed paths (``loops/pilco.py:281-284``: new paths per optimiser step).
+``generate_paths`` is torch plumbing that starts from nothing each time (Kuu and its factor
+included); ``PathSampler`` keeps what does not change between draws, draws into preallocated
+buffers and does the reformatting in two kernels (``csrc/mm_pathwise_sample.hip``), so that a
+draw neither allocates nor synchronises and can be captured in a HIP graph.  Path *evaluation*
+-- the per-step hot loop -- runs in ``mm_pathwise_eval`` / ``mm_pathwise_rollout``
+(``csrc/mm_pathwise.hip``).  Parity with gpflow_sampling is unpinned (see
+``oracle/pathwise_oracle.py``).
 """
 from __future__ import annotations
 
@@ -214,6 +219,120 @@ def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=t
   return paths_from_arrays(omega, phase, w, v, Z, ls, var, mean_c, dtype=dtype, device=device)
 
 
+class PathSampler:
+  """Draws sample paths of ONE model over and over (``PathwisePILCO``: new paths on every optimiser step) without redoing what
+  does not depend on the draw.
+
+  Cached per version of the model's parameters (keyed on the tensors' ``_version`` like ``models._PackCache``; rebuilt lazily by the
+  next ``draw`` after an in-place update): the stacked Z, lengthscales and variances, ``Luu = chol(Kuu + jitter)`` (one
+  ``linalg.cholesky`` with its check), ``q(u)``'s mean and factor -- mapped through ``Luu`` for a whitened model, so that
+  u = c + T eps is one batched GEMM -- and the model-constant operands of ``Paths`` (``zs``, ``hz``, ``lengthscales``, ``prior_scale``,
+  ``variance``, ``mean_c``: the torch expressions of ``paths_from_arrays``).  Preallocated once: the float64 draw buffers
+  ``n [L,K,d]``, ``b [L,K]``, ``w [S,L,K]``, ``eps [S,L,M]``, ``Phi_Z [L,M,K]``, the right-hand side ``[L,M,S]`` the two triangular
+  solves run in place on, and the outputs ``omega``, ``phase``, ``wb`` in the stream dtype.
+
+  ``draw()``: RNG fills in ``generate_paths``'s order (the same generator state gives the same numbers) -> ``mm_pathwise_basis`` ->
+  u and u - Phi_Z w as two batched GEMMs into ``[L,M,S]`` -> two triangular solves with the cached factor ->
+  ``mm_pathwise_pack_stream``, all on the current stream.  After the first call a draw performs no host synchronisation and keeps
+  no new memory, and it can be captured in a HIP graph (``generator=None`` only; draw once eagerly first: a stale cache cannot be
+  rebuilt under capture, its factorisation check reads the device)."""
+
+  def __init__(self, model: SVGP, num_samples: int, num_bases: int = 1024, dtype=torch.float32, device="cuda"):
+    self.model, self.S, self.K = model, int(num_samples), int(num_bases)
+    self.dtype, self.device = dtype, torch.device(device)
+    self._code = _dtype_code(dtype)
+    if self.S <= 0 or self.K <= 0:
+      raise ValueError("PathSampler needs num_samples >= 1 and num_bases >= 1")
+    if not self.device.type == "cuda":
+      raise RuntimeError("gpflowpilco_amd kernels run on the GPU only (no CPU fallback): PathSampler on " + str(self.device))
+    self._key = None
+    self._bufs = None
+
+  # -- what depends on the model alone ------------------------------------------------------------------------------------------
+  def _refresh(self):
+    model, dev = self.model, self.device
+    key = tuple((id(t), t._version, t.device) for t in model._parameters())
+    if key == self._key:
+      return
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError("PathSampler: the model changed since the last draw (or nothing was drawn yet); draw() once outside the "
+                         "graph capture first")
+    with torch.no_grad():
+      kernels, Zs = unpack_multioutput(model.kernel, model.inducing_variable, model.num_latent_gps)
+      Z, ls, var = _stack_kernel_params(kernels, Zs, dev)
+      L, M, d = Z.shape
+      if d > _lib.MM_DMAX:
+        raise ValueError(f"PathSampler: input dimension {d} exceeds MM_DMAX = {_lib.MM_DMAX}")
+      A = Z / ls[:, None, :]
+      d2 = (A * A).sum(-1)[:, :, None] + (A * A).sum(-1)[:, None, :] - 2.0 * A @ A.transpose(1, 2)
+      Kuu = var[:, None, None] * torch.exp(-0.5 * d2.clamp_min(0.0)) + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=dev)
+      Luu = cholesky(Kuu)
+      q_mu = model.q_mu.to(device=dev, dtype=DEFAULT_FLOAT).T                        # [L, M]
+      q_sqrt = torch.tril(model.q_sqrt.to(device=dev, dtype=DEFAULT_FLOAT))           # [L, M, M]
+      c, T = q_mu.unsqueeze(-1), q_sqrt
+      if model.whiten:                                                                # u = Luu (q_mu + q_sqrt eps)
+        c, T = Luu @ c, Luu @ T
+      mean_c = None
+      if isinstance(model.mean_function, Constant):
+        mean_c = model.mean_function.c.to(device=dev, dtype=DEFAULT_FLOAT).expand(L).contiguous()
+      elif not isinstance(model.mean_function, Zero):
+        raise NotImplementedError
+      # the model-constant operands of Paths, by the expressions of paths_from_arrays
+      mult = 128 if self.dtype == torch.float64 else 256
+      tt = lambda a: a.to(self.dtype).contiguous()
+      xscale = math.sqrt(math.log2(math.e)) / ls
+      zs = Z * xscale[:, None, :]
+      hz = 0.5 * (zs * zs).sum(-1)
+      self._const = dict(zs=tt(_pad_last(zs.transpose(1, 2), mult)), hz=tt(_pad_last(hz, mult)), lengthscales=xscale.contiguous(),
+                         prior_scale=torch.sqrt(2.0 * var / self.K).contiguous(), variance=var.contiguous(), mean_c=mean_c)
+      self._Z, self._ls, self._var = Z.contiguous(), ls.contiguous(), var.contiguous()
+      self._Luu, self._LuuT = Luu.contiguous(), Luu.transpose(1, 2)
+      self._c, self._T = c.contiguous(), T.contiguous()
+    if self._bufs is None or self._dims != (L, M, d):
+      self._dims = (L, M, d)
+      S, K = self.S, self.K
+      f64 = lambda *shape: torch.empty(*shape, dtype=DEFAULT_FLOAT, device=dev)
+      Kp, Mp, G = K + (-K) % mult, M + (-M) % mult, (S + 3) // 4
+      out = lambda *shape: torch.empty(*shape, dtype=self.dtype, device=dev)
+      self._bufs = dict(n=f64(L, K, d), b=f64(L, K), w=f64(S, L, K), eps=f64(S, L, M), phiZ=f64(L, M, K), rhs=f64(L, M, S),
+                        omega=out(L, d, Kp), phase=out(L, Kp), wb=out(G, L, (Kp + Mp) // mult, 4, mult))
+    self._key = key
+
+  @property
+  def buffers(self):
+    """The static buffers of the last draw (``n``, ``b``, ``w``, ``eps``, ``phiZ``, ``rhs`` = the update weights v as [L,M,S],
+    ``omega``, ``phase``, ``wb``); the next ``draw`` overwrites them."""
+    return self._bufs
+
+  def draw(self, generator: Optional[torch.Generator] = None, clone: bool = False) -> Paths:
+    """New sample paths.  The returned ``Paths`` holds the sampler's STATIC buffers: the next ``draw`` (or the replay of a graph
+    that captured one) overwrites them; ``clone=True`` returns an independent copy."""
+    if generator is not None and torch.cuda.is_current_stream_capturing():
+      raise RuntimeError("PathSampler.draw: under graph capture only generator=None (the default generator, which the capture "
+                         "registers) is supported")
+    self._refresh()
+    B, (L, M, d), S, K = self._bufs, self._dims, self.S, self.K
+    with torch.no_grad():
+      B["n"].normal_(generator=generator)
+      B["b"].uniform_(generator=generator).mul_(2.0 * math.pi)
+      B["w"].normal_(generator=generator)
+      B["eps"].normal_(generator=generator)
+      lib, stream = _lib.lib(), _stream(self.device)
+      check(lib.mm_pathwise_basis(L, K, M, d, self._code, B["n"].data_ptr(), B["b"].data_ptr(), self._Z.data_ptr(),
+                                  self._ls.data_ptr(), self._var.data_ptr(), B["omega"].data_ptr(), B["phase"].data_ptr(),
+                                  B["phiZ"].data_ptr(), stream), "mm_pathwise_basis")
+      rhs = B["rhs"]
+      torch.baddbmm(self._c.expand(L, M, S), self._T, B["eps"].permute(1, 2, 0), out=rhs)        # u = c + T eps      [L, M, S]
+      rhs.baddbmm_(B["phiZ"], B["w"].permute(1, 2, 0), alpha=-1.0)                               # u - Phi_Z w
+      torch.linalg.solve_triangular(self._Luu, rhs, upper=False, out=rhs)
+      torch.linalg.solve_triangular(self._LuuT, rhs, upper=True, out=rhs)                        # v = Kuu^-1 (u - Phi_Z w)
+      check(lib.mm_pathwise_pack_stream(S, L, K, M, self._code, B["w"].data_ptr(), rhs.data_ptr(), B["wb"].data_ptr(), stream),
+            "mm_pathwise_pack_stream")
+      cp = (lambda t: None if t is None else t.clone()) if clone else (lambda t: t)
+      return Paths(omega=cp(B["omega"]), phase=cp(B["phase"]), wb=cp(B["wb"]), num_samples=S,
+                   **{k: cp(v) for k, v in self._const.items()})
+
+
 class PathwiseSVGP(SVGP):
   """``gpflow_pilco.models.PathwiseSVGP`` (models/svgp.py:124-130): an SVGP whose ``__call__``
   evaluates the currently attached sample paths."""
@@ -224,6 +343,10 @@ class PathwiseSVGP(SVGP):
                      dtype=torch.float32, device="cuda", generator=None) -> Paths:
     assert sample_axis == 0
     return generate_paths(self, num_samples, num_bases, dtype=dtype, device=device, generator=generator)
+
+  def path_sampler(self, num_samples: int, num_bases: int = 1024, dtype=torch.float32, device="cuda") -> PathSampler:
+    """A ``PathSampler`` of this model: ``.draw()`` is ``generate_paths`` for repeated use."""
+    return PathSampler(self, num_samples, num_bases, dtype=dtype, device=device)
 
   @contextlib.contextmanager
   def set_temporary_paths(self, paths: Paths):

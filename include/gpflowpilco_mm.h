@@ -477,6 +477,29 @@ int mm_pathwise_policy_rollout_backward_wide(int S, int dtype, int H, double dt,
                                              const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                              void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- path GENERATION: the two reformatting steps of a draw (csrc/mm_pathwise_sample.hip) -----------------------------------
+ * PathwisePILCO draws new paths on every optimiser step (loops/pilco.py:281-284).  Between the random draws, two GEMMs and two
+ * triangular solves (the caller's: pathwise.PathSampler keeps them on torch's BLAS with a cached Kuu factor) a draw is
+ * reformatting; these two entries do it in one launch resp. one pass each, into buffers the caller reuses across draws.
+ *
+ * mm_pathwise_basis: from the draws n [L,K,d] (standard normal) and b [L,K] (uniform on [0, 2 pi)), f64, and the model's
+ * Z [L,M,d], ls [L,d], var [L], f64:
+ *   omega_out [L,d,Kp] T = (n[l][k][j] / ls[l][j]) / 2 pi,  phase_out [L,Kp] T = b[l][k] / 2 pi   (mm_pathwise_eval's omega_t, phase;
+ *                          Kp = K rounded up to BT; zero for k >= K; the division by 2 pi is a multiplication by the f64
+ *                          reciprocal, as torch evaluates a division by a host scalar on the device: bit-equal to it)
+ *   phiZ_out [L,M,K] f64 = sqrt(2 var_l / K) cos(sum_j Z[l][m][j] (n[l][k][j] / ls[l][j]) + b[l][k])
+ * BT = 128 (MM_F64) or 256 (MM_F32).  MM_E_DIM: d > MM_DMAX or a non-positive size.
+ *
+ * mm_pathwise_pack_stream: the blocked weight stream of mm_pathwise_eval from the prior weights w [S,L,K] f64 and the update
+ * weights v [L,M,S] f64 (sample index fastest: the layout a solve with the right-hand side [L,M,S] leaves):
+ *   wb_out [G][L][NB][4][BT] T, G = ceil(S / 4), NB = (Kp + Mp) / BT:  [g][l][nb][sl][t] = (T) w[4g+sl][l][nb BT + t] for
+ *   nb < Kp / BT, else (T) v[l][(nb - Kp/BT) BT + t][4g+sl]; zero where k >= K, m >= M or 4g+sl >= S.
+ * Every element of wb_out is written exactly once (no memset needed between draws).  MM_E_DIM: a non-positive size. */
+int mm_pathwise_basis(int L, int K, int M, int d, int dtype, const double* n, const double* b, const double* Z,
+                      const double* ls, const double* var, void* omega_out, void* phase_out, double* phiZ_out, void* stream);
+int mm_pathwise_pack_stream(int S, int L, int K, int M, int dtype, const double* w, const double* v, void* wb_out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
