@@ -97,6 +97,14 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p]),
+    "mm_rollout_composed_backward_seeded": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                      C.c_void_p, C.c_void_p]),
     "mm_compose_tape_bytes_nd": (C.c_size_t, [C.c_int] * 7),
     "mm_rollout_composed_taped_nd": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                C.c_void_p, C.c_size_t, C.c_int, C.c_int,
@@ -115,6 +123,14 @@ SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.c_void_p]),
+    "mm_rollout_composed_backward_nd_seeded": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                         C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                         C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p]),
     "mm_bwd_f32_supported": (C.c_int, [C.c_int]),
     "mm_backward_pair_aggregates_bytes": (C.c_size_t, [C.c_int] * 5),
     "mm_backward_pair_aggregates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -489,3 +489,46 @@ class ComposedRolloutNDFunction(torch.autograd.Function):
     gvar = g[:, M * d + M + d].reshape(vs)
     gmean = g[:, M * d + M + d + 1].reshape(ms)
     return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
+
+
+class ComposedTrajectoryFunction(torch.autograd.Function):
+  """The moment-matched policy rollout with its TRAJECTORY as a differentiable output, for one action and for several: the taped
+  forward of ``ComposedRolloutFunction`` / ``ComposedRolloutNDFunction`` (by ``roll.nu``), and the same reverse sweep seeded per step
+  with d loss / d (m_t, S_t) (``mm_rollout_composed_backward_seeded`` / ``_nd_seeded``).  Any torch objective of the states then
+  sits on the native policy -> drift -> Euler chain, and the gradient of its own parameters comes from that torch part.
+
+  Inputs: those of ``ComposedRolloutFunction`` (a leading latent axis on the packed coordinates for nu > 1).  Outputs:
+  (cost [B, H] of the rollout's built-in Gaussian cost, xm [B, H, nx], xS [B, H, nx, nx]) -- the states x_1 .. x_H read off the
+  tape.  Only the symmetric part of a seed on the symmetric S_t is determined: the backward uses (G + G^T) / 2."""
+
+  @staticmethod
+  def forward(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
+    f64 = torch.float64
+    det = lambda t: t.detach().to(f64)
+    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
+    taped = roll.taped if roll.nu == 1 else roll.taped_nd
+    m_H, S_H, cost, tape = taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
+    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
+    ctx.save_for_backward(ls)
+    ctx.need_state = mx.requires_grad or Sxx.requires_grad
+    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+    xm, xS = roll.tape_states(tape, ctx.B, ctx.H)
+    return cost.T.contiguous(), xm.transpose(0, 1).contiguous(), xS.transpose(0, 1).contiguous()
+
+  @staticmethod
+  def backward(ctx, g_cost, g_xm, g_xS):
+    (ls,) = ctx.saved_tensors
+    g_xS = 0.5 * (g_xS + g_xS.transpose(-1, -2))
+    seeds = (g_xm.transpose(0, 1).contiguous(), g_xS.transpose(0, 1).contiguous())
+    sweep = ctx.roll.backward if ctx.roll.nu == 1 else ctx.roll.backward_nd
+    g_pol, g_m, g_S = sweep(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
+                            want_state_grad=ctx.need_state, g_traj=seeds)
+    nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
+    g = g_pol.sum(0).reshape(nu, -1)                                                        # [nu, M d + M + d + 2]
+    zs, lss, vs, bs, ms = ctx.shapes
+    gZ = g[:, :M * d].reshape(zs)
+    gbeta = g[:, M * d:M * d + M].reshape(bs)
+    gls = (2.0 * ls.detach().reshape(nu, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)   # d/d ls = 2 ls d/d ls^2
+    gvar = g[:, M * d + M + d].reshape(vs)
+    gmean = g[:, M * d + M + d + 1].reshape(ms)
+    return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None

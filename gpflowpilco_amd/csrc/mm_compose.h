@@ -47,7 +47,7 @@ static inline MMComposeLayout mm_compose_layout(int B, int nx, int na, int dtype
 }
 
 static inline int mm_compose_dims(int nx, int na, const int32_t* active_dims, MMComposeDims& D) {
-  if (nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || !active_dims) return MM_E_DIM;
+  if (nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || (na > 0 && !active_dims)) return MM_E_DIM;
   D.nx = nx; D.na = na; D.nb = nx - na; D.ne = 2 * na + D.nb; D.nd = D.ne + 1;
   if (D.nd > MMC_ND) return MM_E_DIM;
   bool used[MMC_NX] = {false};

@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256) void k_policy_match_small(const double* __rest
 // host side
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t mm_compose_workspace_bytes(int B, int nx, int na, int dtype) {
-  if (B <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx) return 0;
+  if (B <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx) return 0;
   if (2 * na + (nx - na) + 1 > MMC_ND) return 0;
   return mm_compose_layout(B, nx, na, dtype).total;
 }
@@ -571,7 +571,7 @@ extern "C" int mm_rollout_composed(const void* drift_packed, size_t drift_bytes,
 }
 
 extern "C" size_t mm_compose_tape_bytes(int B, int H, int nx, int na, int drift_M, int dtype) {
-  if (B <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
+  if (B <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
   if (2 * na + (nx - na) + 1 > MMC_ND) return 0;
   return mm_tape_layout(B, H, nx, na, drift_M, dtype).total;
 }

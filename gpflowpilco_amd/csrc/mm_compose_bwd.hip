@@ -491,7 +491,8 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd(MMComposeDims D, double
                                                          const double* __restrict__ Sxe, const double* __restrict__ cp,
                                                          const double* __restrict__ Sdd, const double* __restrict__ dcross,
                                                          double* cm, double* cS, double* cme, double* cSee, double* cSxe,
-                                                         double* ccp, double* cSdd, double* cdf1, double* cdSff, double* cdcross) {
+                                                         double* ccp, double* cSdd, double* cdf1, double* cdSff, double* cdcross,
+                                                           const double* __restrict__ sxm, const double* __restrict__ sxS) {
   extern __shared__ double sm[];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nx = D.nx, ne = D.ne, nd = D.nd;
@@ -504,6 +505,11 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd(MMComposeDims D, double
   for (int i = lane; i < nx * ne; i += 64) gSxe[i] = first ? 0.0 : cSxe[i];
   for (int i = lane; i < nx; i += 64) gm1[i] = first ? 0.0 : cm[i];
   for (int i = lane; i < nx * nx; i += 64) gS1[i] = first ? 0.0 : cS[i];
+  // the caller's own seeds d loss / d (m_{h+1}, S_{h+1}) (the seeded entries; the same lanes wrote the carry above)
+  if (sxm) {
+    for (int i = lane; i < nx; i += 64) gm1[i] += sxm[(size_t)b * nx + i];
+    for (int i = lane; i < nx * nx; i += 64) gS1[i] += sxS[(size_t)b * nx * nx + i];
+  }
   __syncthreads();
   // this step's cost statistic: the expected cost of the ENCODED new state (loops/pilco.py:199-205)
   mma_cost_bwd(c, ne, me1 + (size_t)b * ne, See1 + (size_t)b * ne * ne, target, precis, gcost[b], gme, gSee, wk);
@@ -618,7 +624,7 @@ static inline MMComposeBwdLayout mm_compose_bwd_layout(int B, int nx, int na, in
 }
 
 extern "C" size_t mm_compose_backward_workspace_bytes(int B, int nx, int na, int drift_M) {
-  if (B <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
+  if (B <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
   if (2 * na + (nx - na) + 1 > MMC_ND) return 0;
   return mm_compose_bwd_layout(B, nx, na, drift_M).total;
 }
@@ -636,14 +642,18 @@ extern "C" size_t mm_policy_grad_bytes(int B, int policy_M, int policy_d) {
 //   g_mx0 [B][nx], g_Sxx0 [B][nx][nx] (out, optional): gradient w.r.t. the initial state (symmetric)
 // The policy: M <= 256 centres on ne <= 8 encoded dims (k_policy_head_bwd_small: one workgroup per element, the M x M block
 // and the M-sized vectors in LDS -- mm_policy_bwd_lds: 120 KB at M = 256, ne = 8); else MM_E_DIM.
-extern "C" int mm_rollout_composed_backward(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
-                                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
-                                            int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
-                                            double head_scale, double head_shift, const void* target, const void* precis,
-                                            const void* tape, size_t tape_bytes, const void* g_cost,
-                                            void* g_policy, void* g_mx0, void* g_Sxx0,
-                                            void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
-                                            int32_t* status, void* stream) {
+// g_xm [H][B][nx], g_xS [H][B][nx][nx] (both or neither): the caller's seeds d loss / d (m_{h+1}, S_{h+1}) of step h, added to
+// the carried adjoint of x_{h+1} before the built-in cost's (mm_rollout_composed_backward_seeded; null: the plain entry)
+static int mm_rollout_composed_backward_impl(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                             const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                             int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                             double head_scale, double head_shift, const void* target, const void* precis,
+                                             const void* tape, size_t tape_bytes, const void* g_cost,
+                                             const void* g_xm, const void* g_xS,
+                                             void* g_policy, void* g_mx0, void* g_Sxx0,
+                                             void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                             int32_t* status, void* stream) {
+  if ((g_xm == nullptr) != (g_xS == nullptr)) return MM_E_ARG;
   if (!drift_packed || !policy_packed || !tape || !g_cost || !g_policy || !ws_drift || !ws_bwd || !target || !precis) return MM_E_ARG;
   if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
   if (dtype != MM_F64) return MM_E_DTYPE;
@@ -685,7 +695,9 @@ extern "C" int mm_rollout_composed_backward(const void* drift_packed, size_t dri
                        (const double*)(sn + cl.See), (const double*)target, (const double*)precis,
                        (const double*)g_cost + (size_t)h * B, (const double*)(sl + cl.Sxe), (const double*)(sl + cl.cpol),
                        (const double*)(sl + cl.Sdd), (const double*)(sl + cl.dcross), cr(kl.cm), cr(kl.cS), cr(kl.cme),
-                       cr(kl.cSee), cr(kl.cSxe), cr(kl.ccp), cr(kl.cSdd), cr(kl.cdf1), cr(kl.cdSff), cr(kl.cdcross));
+                       cr(kl.cSee), cr(kl.cSxe), cr(kl.ccp), cr(kl.cSdd), cr(kl.cdf1), cr(kl.cdSff), cr(kl.cdcross),
+                       g_xm ? (const double*)g_xm + (size_t)h * B * nx : (const double*)nullptr,
+                       g_xS ? (const double*)g_xS + (size_t)h * B * nx * nx : (const double*)nullptr);
     MMB_CHECK();
     // the drift's match: (g df1, g dSff, g dcross) -> g md (assigned), g Sdd (accumulated onto the bookkeeping's part)
     const bool kept = tl.ws_stride != 0;                   // the tape holds this step's q-stage workspace
@@ -712,4 +724,35 @@ extern "C" int mm_rollout_composed_backward(const void* drift_packed, size_t dri
     MMB_CHECK();
   }
   return 0;
+}
+
+extern "C" int mm_rollout_composed_backward(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                            int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                            double head_scale, double head_shift, const void* target, const void* precis,
+                                            const void* tape, size_t tape_bytes, const void* g_cost,
+                                            void* g_policy, void* g_mx0, void* g_Sxx0,
+                                            void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                            int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes, policy_M,
+                                           policy_d, dtype, B, H, dt, nx, na, active_dims, head_scale, head_shift, target, precis, tape,
+                                           tape_bytes, g_cost, nullptr, nullptr, g_policy, g_mx0, g_Sxx0, ws_drift, ws_drift_bytes,
+                                           ws_bwd, ws_bwd_bytes, status, stream);
+}
+
+// The same sweep with per-step seeds on the trajectory: the states x_1 .. x_H of the tape become differentiable outputs, so any
+// objective evaluated on them outside (autodiff.ComposedTrajectoryFunction) sits on the native policy -> drift -> Euler chain.
+extern "C" int mm_rollout_composed_backward_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                                   const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                                   int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                   double head_scale, double head_shift, const void* target, const void* precis,
+                                                   const void* tape, size_t tape_bytes, const void* g_cost,
+                                                   const void* g_xm, const void* g_xS,
+                                                   void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                   void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                   int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes, policy_M,
+                                           policy_d, dtype, B, H, dt, nx, na, active_dims, head_scale, head_shift, target, precis, tape,
+                                           tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0, ws_drift, ws_drift_bytes,
+                                           ws_bwd, ws_bwd_bytes, status, stream);
 }

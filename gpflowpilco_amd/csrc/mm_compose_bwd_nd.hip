@@ -66,7 +66,8 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd_nd(MMComposeDims D, dou
                                                             const double* __restrict__ Sxe, const double* __restrict__ cp,
                                                             const double* __restrict__ Sdd, const double* __restrict__ dcross,
                                                             double* cm, double* cS, double* cme, double* cSee, double* cSxe,
-                                                            double* ccp, double* cSdd, double* cdf1, double* cdSff, double* cdcross) {
+                                                            double* ccp, double* cSdd, double* cdf1, double* cdSff, double* cdcross,
+                                                              const double* __restrict__ sxm, const double* __restrict__ sxS) {
   extern __shared__ double sm[];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nx = D.nx, ne = D.ne, nd = D.nd, nu = nd - ne;
@@ -79,6 +80,11 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd_nd(MMComposeDims D, dou
   for (int i = lane; i < nx * ne; i += 64) gSxe[i] = first ? 0.0 : cSxe[i];
   for (int i = lane; i < nx; i += 64) gm1[i] = first ? 0.0 : cm[i];
   for (int i = lane; i < nx * nx; i += 64) gS1[i] = first ? 0.0 : cS[i];
+  // the caller's own seeds d loss / d (m_{h+1}, S_{h+1}) (the seeded entries; the same lanes wrote the carry above)
+  if (sxm) {
+    for (int i = lane; i < nx; i += 64) gm1[i] += sxm[(size_t)b * nx + i];
+    for (int i = lane; i < nx * nx; i += 64) gS1[i] += sxS[(size_t)b * nx * nx + i];
+  }
   __syncthreads();
   mma_cost_bwd(c, ne, me1 + (size_t)b * ne, See1 + (size_t)b * ne * ne, target, precis, gcost[b], gme, gSee, wk);
   mma_encode_bwd(c, D, x1m + (size_t)b * nx, x1S + (size_t)b * nx * nx, gme, gSee, gSxe, gm1, gS1, wk);
@@ -154,7 +160,7 @@ static inline size_t mm_policy_bwd_nd_lds(int M, int ne, int nu) {
 
 // shapes the sweep takes (see the header comment)
 static inline bool mm_compose_bwd_nd_takes(int nx, int na, int nu, int policy_M) {
-  if (nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU || policy_M <= 0) return false;
+  if (nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU || policy_M <= 0) return false;
   const int ne = nx + na;
   if (ne + nu > MMC_ND || ne > 8 || policy_M > MM_SORT_MIN_M) return false;
   return mm_policy_bwd_nd_lds(policy_M, ne, nu) <= MMB_ND_LDS_MAX;
@@ -186,14 +192,17 @@ extern "C" size_t mm_policy_grad_bytes_nd(int B, int nu, int policy_M, int polic
 //   g_policy [B][nu][M d + M + d + 2] (out, overwritten): per batch element and latent, in latent order, the gradient w.r.t. the
 //            PACKED policy -- Z [M][d], beta [M], ls2 = lengthscales^2 [d], variance, mean_c
 //   g_mx0 [B][nx], g_Sxx0 [B][nx][nx] (out, optional): gradient w.r.t. the initial state (symmetric)
-extern "C" int mm_rollout_composed_backward_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
-                                               const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
-                                               int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
-                                               int nu, const double* head_scale, const double* head_shift,
-                                               const void* target, const void* precis, const void* tape, size_t tape_bytes,
-                                               const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
-                                               void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
-                                               int32_t* status, void* stream) {
+// g_xm [H][B][nx], g_xS [H][B][nx][nx] (both or neither): the caller's seeds on the trajectory, as in mm_compose_bwd.hip
+static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                                const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                                int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                int nu, const double* head_scale, const double* head_shift,
+                                                const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                                const void* g_cost, const void* g_xm, const void* g_xS,
+                                                void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                int32_t* status, void* stream) {
+  if ((g_xm == nullptr) != (g_xS == nullptr)) return MM_E_ARG;
   if (!drift_packed || !policy_packed || !tape || !g_cost || !g_policy || !ws_drift || !ws_bwd || !target || !precis) return MM_E_ARG;
   if (!head_scale || !head_shift) return MM_E_ARG;
   if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
@@ -239,7 +248,9 @@ extern "C" int mm_rollout_composed_backward_nd(const void* drift_packed, size_t 
                        (const double*)(sn + cl.See), (const double*)target, (const double*)precis,
                        (const double*)g_cost + (size_t)h * B, (const double*)(sl + cl.Sxe), (const double*)(sl + cl.cpol),
                        (const double*)(sl + cl.Sdd), (const double*)(sl + cl.dcross), cr(kl.cm), cr(kl.cS), cr(kl.cme),
-                       cr(kl.cSee), cr(kl.cSxe), cr(kl.ccp), cr(kl.cSdd), cr(kl.cdf1), cr(kl.cdSff), cr(kl.cdcross));
+                       cr(kl.cSee), cr(kl.cSxe), cr(kl.ccp), cr(kl.cSdd), cr(kl.cdf1), cr(kl.cdSff), cr(kl.cdcross),
+                       g_xm ? (const double*)g_xm + (size_t)h * B * nx : (const double*)nullptr,
+                       g_xS ? (const double*)g_xS + (size_t)h * B * nx * nx : (const double*)nullptr);
     MMB_CHECK();
     // the drift's match (its items are summed by the next kernel), as the one-action sweep runs it
     const bool kept = tl.ws_stride != 0;                   // the tape holds this step's q-stage workspace
@@ -266,4 +277,35 @@ extern "C" int mm_rollout_composed_backward_nd(const void* drift_packed, size_t 
     MMB_CHECK();
   }
   return 0;
+}
+
+extern "C" int mm_rollout_composed_backward_nd(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                               const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                               int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                               int nu, const double* head_scale, const double* head_shift,
+                                               const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                               const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
+                                               void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                               int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, nullptr, nullptr, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream);
+}
+
+// ... with per-step seeds d loss / d (m_{h+1}, S_{h+1}) on the trajectory (mm_rollout_composed_backward_seeded for 1 to 4 actions)
+extern "C" int mm_rollout_composed_backward_nd_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                      int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                      int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                      const int32_t* active_dims, int nu, const double* head_scale,
+                                                      const double* head_shift, const void* target, const void* precis,
+                                                      const void* tape, size_t tape_bytes, const void* g_cost,
+                                                      const void* g_xm, const void* g_xS,
+                                                      void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                      void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                      int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream);
 }

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(64) void k_compose_tail_nd(MMComposeDims D, double 
 // host side
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t mm_compose_nd_workspace_bytes(int B, int nx, int na, int nu, int dtype) {
-  if (B <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return 0;
+  if (B <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return 0;
   if (2 * na + (nx - na) + nu > MMC_ND) return 0;
   if (dtype != MM_F32 && dtype != MM_F64) return 0;
   return mm_compose_layout_nd(B, nx, na, nu, dtype).total;
@@ -314,7 +314,7 @@ extern "C" int mm_rollout_composed_nd(const void* drift_packed, size_t drift_byt
 // ---- the same rollout, recorded (f64 only, as the reverse sweep) -------------------------------------------------------------
 // 0: dims out of range or a dtype other than MM_F64
 extern "C" size_t mm_compose_tape_bytes_nd(int B, int H, int nx, int na, int nu, int drift_M, int dtype) {
-  if (B <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
+  if (B <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || drift_M <= 0) return 0;
   if (nu < 1 || nu > MMC_NU || 2 * na + (nx - na) + nu > MMC_ND) return 0;
   if (dtype != MM_F64) return 0;
   return mm_tape_layout_nd(B, H, nx, na, nu, drift_M, dtype).total;

@@ -174,7 +174,7 @@ static int mmp_check(int S, int M, int K, int dtype, int H, int nx, int na, cons
 static inline size_t mmp_head_lds(int pM, int ne) { return (size_t)(pM * ne + pM + ne + ne + ne * ne + 8) * sizeof(double); }
 
 extern "C" size_t mm_pathwise_tape_bytes(int S, int H, int nx, int na, int dtype, int with_jacobians) {
-  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx) return 0;
+  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx) return 0;
   return mm_pw_tape_layout(S, H, nx, na, 1, dtype, with_jacobians).total;
 }
 

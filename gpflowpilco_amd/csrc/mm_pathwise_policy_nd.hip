@@ -186,7 +186,7 @@ static inline size_t mmp_nd_bwd_lds(int pM, int ne, int nu) {
 // everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions
 static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, int nu, const int32_t* active_dims, int policy_M,
                         int nd_max, MMComposeDims& D) {
-  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || !active_dims) return MM_E_ARG;
+  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || (na > 0 && !active_dims)) return MM_E_ARG;
   if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
   const int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
   if (rc) return rc;
@@ -196,7 +196,7 @@ static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, i
 }
 
 extern "C" size_t mm_pathwise_tape_bytes_nd(int S, int H, int nx, int na, int nu, int dtype, int with_jacobians) {
-  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na <= 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return 0;
+  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return 0;
   return mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians).total;
 }
 

@@ -34,9 +34,11 @@ def forward_sde(x, drift, noise=None, policy=None, encoder=None):
     match_policy = moment_matching(x, policy)
     match_drift = moment_matching(match_policy.joint(), drift)
     if match_drift.cross[1]:
-      preinv = match_policy.cross[1]
-      cross = (match_policy.cross_covariance(preinv=preinv)
-               @ match_drift.cross_covariance(preinv=True), preinv)
+      # Cov(x, f) ~ Cov(x, d) Cov(d, d)^-1 Cov(d, f), d = (x, u): Cov(x, d) = the first nx rows of Cov(d, d), as the branch with
+      # an encoder takes the rows of its inactive dims.  (The reference multiplies Cov(x, u) [nx, nu] by the pre-inverted
+      # Cov(d, f) [nd, nx] here, which does not compose for a GP drift: that form raised for every such system.)
+      Sdd = match_drift.x.covariance(dense=True)
+      cross = Sdd[..., :x.mean().shape[-1], :] @ match_drift.cross_covariance(preinv=True), False
     else:
       cross = match_drift.cross_covariance()[..., :x.mean().shape[-1], :], False
     chain = GaussianMatch(x=x, y=match_drift.y, cross=cross)

@@ -22,12 +22,17 @@ def get_state_initializer(mean: torch.Tensor, covariance: torch.Tensor) -> Calla
   return lambda: (mx, Sxx)
 
 
-def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[list], moment_solver: bool):
+def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[list], moment_solver: bool,
+                  no_encoder: bool = False, any_objective: bool = False):
   """The pieces the native rollouts are written for -- TrigonometricEncoder, policy = InverseLinkWrapper(KernelRegressor(SVGP with
   one latent per action, up to 4), Chain[Scale, Shift, NormalCDF]) with scale and shift a scalar or one value per action, SVGP
   drift, no diffusion, GaussianObjective (the cartpole wiring of ``examples/cartpole_swingup/swingup_loops.py:41-91``; two
   actions: the double pendulum) -- or None, with the reason appended to ``why``.  ``head_constants()`` returns two floats for
-  one action and two tuples of nu floats for nu > 1."""
+  one action and two tuples of nu floats for nu > 1.
+
+  ``no_encoder``: also take ``encoder=None`` and ``TrigonometricEncoder(active_dims=())``, treated alike (the native entries with
+  na = 0: the encoding is the identity); the encoder returned is then one without active dims.  ``any_objective``: also take an
+  objective that is no ``GaussianObjective`` (the caller evaluates it on the native rollout's trajectory)."""
   from . import bijectors as tfb
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
@@ -42,9 +47,14 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
     return no("a diffusion term")
   if moment_solver and not isinstance(system.solver, MomentMatchingEuler):
     return no("a solver other than MomentMatchingEuler")
+  if enc is None or (isinstance(enc, TrigonometricEncoder) and len(enc.active_dims) == 0):
+    if not no_encoder:
+      return no(f"encoder {type(enc).__name__} (the native rollout implements TrigonometricEncoder)" if enc is None else
+                "a TrigonometricEncoder without active dims (native_no_encoder=True runs it natively)")
+    enc = TrigonometricEncoder(active_dims=())
   if not isinstance(enc, TrigonometricEncoder):
     return no(f"encoder {type(enc).__name__} (the native rollout implements TrigonometricEncoder)")
-  if not isinstance(objective, GaussianObjective):
+  if not isinstance(objective, GaussianObjective) and not any_objective:
     return no(f"objective {type(objective).__name__} (the native rollout implements GaussianObjective)")
   if not isinstance(pol, InverseLinkWrapper) or not isinstance(pol.model, KernelRegressor):
     return no("the policy is not InverseLinkWrapper(KernelRegressor(SVGP))")
@@ -95,7 +105,8 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
 
 
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
-                       why: Optional[list] = None, native_actions: int = 1):
+                       why: Optional[list] = None, native_actions: int = 1, native_no_encoder: bool = False,
+                       native_objective: bool = False):
   """``f(mx, Sxx) -> loss [B]`` running the whole rollout in ``mm_rollout_composed`` (csrc/mm_compose.hip), or None
   when the system is not the shape that entry point implements: TrigonometricEncoder, policy =
   InverseLinkWrapper(KernelRegressor(SVGP with one latent per action), Chain[Scale, Shift, NormalCDF]), SVGP drift, no
@@ -108,40 +119,87 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
   ``native_actions``: the largest number of actions ``with_grad`` may differentiate natively.  The default 1 keeps a policy with
   several actions forward only (``grad_obstacle`` names ``nu > 1``); with ``native_actions >= nu`` its gradient runs through the
   multi-action tape and reverse sweep (csrc/mm_compose_bwd_nd.hip, ``autodiff.ComposedRolloutNDFunction``) where
-  ``ComposedRollout.backward_nd_refusal`` has no objection."""
+  ``ComposedRollout.backward_nd_refusal`` has no objection.
+
+  ``native_no_encoder``: take a system with ``encoder=None`` (or a ``TrigonometricEncoder`` without active dims) too: the native
+  entries with na = 0; the cost is the objective of the raw state (``GaussianObjective.target`` is [nx]).
+
+  ``native_objective``: take any objective.  One that is no ``GaussianObjective``, or a ``GaussianObjective`` whose target /
+  precision require a gradient, is evaluated in torch on the trajectory of the native rollout (``f.uses_trajectory(mx)``):
+  ``autodiff.ComposedTrajectoryFunction`` returns the H states as differentiable outputs, the loss is the reference's accumulation
+  ``objective(x = encoder match of x_t, t = t)`` over them, and the seeded reverse sweep carries its gradient back to the policy
+  and the initial state; the objective's own parameters get theirs from the torch part."""
   from . import ops
-  parts = _native_parts(system, objective, why, moment_solver=True)
+  from .cost import GaussianObjective
+  parts = _native_parts(system, objective, why, moment_solver=True, no_encoder=bool(native_no_encoder),
+                        any_objective=bool(native_objective))
   if parts is None:
     return None
   enc, pm_, drift, bj, head_constants = parts
   max_native = int(native_actions)
   cache = {}
+  gaussian = isinstance(objective, GaussianObjective)
+  zero_cost = {}
 
-  def current_roll(mx: torch.Tensor, fresh_policy: bool = True):
+  def cost_constants(mx, zero):
+    """(target, precis) of the rollout's built-in cost: the objective's, or zeros where the trajectory route ignores that cost."""
+    if not zero:
+      return objective.target, objective.precis
+    key = (mx.dtype, str(mx.device))
+    if key not in zero_cost:
+      ne = mx.shape[-1] + len(enc.active_dims)
+      zero_cost[key] = (torch.zeros(ne, dtype=mx.dtype, device=mx.device), torch.zeros(ne, ne, dtype=mx.dtype, device=mx.device))
+    return zero_cost[key]
+
+  def uses_trajectory(mx=None) -> bool:
+    """The objective is evaluated in torch on the native trajectory (``native_objective``)."""
+    if not native_objective:
+      return False
+    if not gaussian:
+      return True
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for t in (objective.target, objective.precis))
+
+  def current_roll(mx: torch.Tensor, fresh_policy: bool = True, zero: bool = False):
     # (fresh_policy=False: the caller brings its own pack of the policy's current parameters -- the differentiable
     # path -- and the rollout object only has to have the right shapes: no re-pack of the policy here)
     # Everything the rollout reads is looked up on EVERY call: ``packed()`` re-packs a model whose parameters were
     # updated in place (optimiser step, refit between episodes: _PackCache keys on the tensors' versions), and the
     # head / objective constants are read from their owners.  Only the compose workspace is kept across calls.
-    key = (mx.dtype, str(mx.device))
+    # (zero: the rollout of the trajectory route, built with a zero target / precision -- its cost output is ignored)
+    key = (mx.dtype, str(mx.device), bool(zero))
     ent = cache.get(key)
     roll = None if ent is None else ent[0]
     pd = drift.packed(mx.dtype, True, mx.device)
     pp = roll.policy if (roll is not None and not fresh_policy) else pm_.packed(mx.dtype, False, mx.device)
     scale, shift = head_constants()
+    target, precis = cost_constants(mx, zero)
     if (roll is None or roll.drift is not pd or roll.policy is not pp or roll.scale != scale or roll.shift != shift
-        or ent[1] is not objective.target or ent[2] is not objective.precis
-        or ent[3] != (objective.target._version, objective.precis._version)):
+        or ent[1] is not target or ent[2] is not precis or ent[3] != (target._version, precis._version)):
       new = ops.ComposedRollout(pd, pp, nx=mx.shape[-1], active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
-                                target=objective.target, precis=objective.precis)
+                                target=target, precis=precis)
       if roll is not None:
         new._wsc = roll._wsc                               # same shapes: the workspace carries over
       roll = new
-      cache[key] = (roll, objective.target, objective.precis, (objective.target._version, objective.precis._version))
+      cache[key] = (roll, target, precis, (target._version, precis._version))
     return roll
 
-  def run(mx: torch.Tensor, Sxx: torch.Tensor):
-    _, _, cost = current_roll(mx)(mx, Sxx, num_steps, dt=dt)
+  def objective_of_trajectory(xm: torch.Tensor, xS: torch.Tensor):
+    """pilco.py:199-205 over the states x_1 .. x_H (xm [B, H, nx], xS [B, H, nx, nx]) at the unit-spaced times 1 .. H."""
+    loss = torch.zeros(xm.shape[0], dtype=xm.dtype, device=xm.device)
+    for h in range(num_steps):
+      x = GaussianMoments(moments=(xm[:, h], xS[:, h]), centered=True)
+      if system.encoder is not None:
+        x = moment_matching(x, system.encoder).y
+      loss = loss + objective(x=x, t=dt * float(h + 1))
+    return loss
+
+  def run(mx: torch.Tensor, Sxx: torch.Tensor, policy=None):
+    if uses_trajectory(mx):
+      roll = current_roll(mx, fresh_policy=policy is None, zero=True)
+      _, _, _, tm, tS = roll(mx, Sxx, num_steps, dt=dt, keep_trajectory=True, policy=policy)
+      return objective_of_trajectory(tm.transpose(0, 1), tS.transpose(0, 1))
+    _, _, cost = current_roll(mx, fresh_policy=policy is None)(mx, Sxx, num_steps, dt=dt, policy=policy)
     return cost.sum(1)
 
   def run_with_grad(mx: torch.Tensor, Sxx: torch.Tensor):
@@ -149,14 +207,19 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     the taped native rollout, backward = the native reverse sweep (autodiff.ComposedRolloutFunction); the policy enters
     in packed coordinates computed from its parameters by differentiable torch ops (a 30 x 30 precompute).  The tape and
     the reverse sweep are float64; a float32 state is cast up on the way in and the loss back down (autograd carries both)."""
-    from .autodiff import ComposedRolloutFunction, ComposedRolloutNDFunction
+    from .autodiff import ComposedRolloutFunction, ComposedRolloutNDFunction, ComposedTrajectoryFunction
     out_dtype = mx.dtype
     if mx.dtype != torch.float64:
       mx, Sxx = mx.double(), Sxx.double()
-    roll = current_roll(mx, fresh_policy=False)
+    traj = uses_trajectory(mx)
+    roll = current_roll(mx, fresh_policy=False, zero=traj)
     Zp, lsp, varp, betap, _, mcp = pm_.precompute(mx.device)
     if mcp is None:
       mcp = torch.zeros(roll.nu, dtype=Zp.dtype, device=mx.device)
+    if traj:
+      # the objective in torch on the H returned states; the rollout's own (zero-precision) cost is not part of the loss
+      _, xm, xS = ComposedTrajectoryFunction.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
+      return objective_of_trajectory(xm, xS).to(out_dtype)
     fn = ComposedRolloutFunction if roll.nu == 1 else ComposedRolloutNDFunction      # (several actions: native_actions >= nu)
     cost = fn.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
     return cost.sum(1).to(out_dtype)
@@ -165,11 +228,9 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     """Forward only, the policy packed from its parameters on the stream (no snapshot from outside): what a HIP-graph
     capture of the loss of a trainable policy must record, so that replays follow the optimiser's in-place updates."""
     with torch.no_grad():
-      roll = current_roll(mx, fresh_policy=False)
       Zp, lsp, varp, betap, _, mcp = pm_.precompute(mx.device)
       pol = ops.pack_model(Zp, lsp, varp, betap, None, mcp, dtype=mx.dtype, sync=False)
-      _, _, cost = roll(mx, Sxx, num_steps, dt=dt, policy=pol)
-    return cost.sum(1)
+      return run(mx, Sxx, policy=pol)
   run.from_parameters = run_from_parameters
 
   def grad_obstacle(mx: torch.Tensor) -> Optional[str]:
@@ -184,15 +245,16 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       return f"the policy has nu = {nu} actions (nu > 1) and native_actions = {max_native}"
     # the native reverse sweep returns gradients for the policy SVGP's parameters and the initial state only: the head's
     # Scale / Shift and the objective's target / precision enter as constants (float() / raw pointers)
-    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
-               "objective.target": objective.target, "objective.precis": objective.precis}
+    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift}
+    if not native_objective:                  # (with it, the objective's own parameters are differentiated by the torch part)
+      outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
     for name, t in outside.items():
       if isinstance(t, torch.Tensor) and t.requires_grad:
         return f"{name} requires a gradient (the native reverse sweep covers the policy SVGP's parameters and the initial state)"
     if any(t.requires_grad for t in drift._parameters()):
       return "the drift is being trained (the native reverse sweep takes a frozen drift)"
     mx64 = mx if mx.dtype == torch.float64 else torch.empty(mx.shape, dtype=torch.float64, device=mx.device)
-    roll = current_roll(mx64, fresh_policy=False)
+    roll = current_roll(mx64, fresh_policy=False, zero=uses_trajectory(mx))
     if nu > 1:
       return roll.backward_nd_refusal()
     if not roll.supports_backward():
@@ -205,13 +267,15 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
   run.with_grad = run_with_grad
   run.supports_grad = supports_grad
   run.grad_obstacle = grad_obstacle
+  run.uses_trajectory = uses_trajectory
   return run
 
 
 def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable,
                         num_steps: int, initial_time: float = 0.0,
                         solution_times: Optional[Sequence[float]] = None, native: Optional[bool] = None,
-                        native_actions: int = 1, **kwargs) -> Callable:
+                        native_actions: int = 1, native_no_encoder: bool = False, native_objective: bool = False,
+                        **kwargs) -> Callable:
   """pilco.py:176-220.  Returns ``closure() -> loss [B]``; ``system.solver`` should be a
   ``MomentMatchingEuler`` (pilco.py:141-144).
 
@@ -227,7 +291,18 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   The default 1 is the routing described above.  With ``native_actions >= nu`` a gradient of the policy SVGP's parameters and / or
   the initial state of a policy with 2 to 4 actions runs as one differentiable op too (``autodiff.ComposedRolloutNDFunction``: the
   multi-action tape and reverse sweep, csrc/mm_compose_bwd_nd.hip) -- frozen drift, constant head and objective, float64 tape
-  (a float32 state is cast up), inside the sweep's LDS bound; every other case falls back once and names its reason."""
+  (a float32 state is cast up), inside the sweep's LDS bound; every other case falls back once and names its reason.
+
+  ``native_no_encoder``: with the default False a system without an encoder (``encoder=None``: mountain car,
+  forward_sde.py:49-68) takes the torch composition as before (``native=True`` raises); True runs it natively, forward and
+  gradient, through the entries' na = 0 form -- the cost is the objective of the raw state.  With an encoder present the option
+  changes nothing.
+
+  ``native_objective``: with the default False only a constant ``GaussianObjective`` runs natively.  True also takes any other
+  objective, and a ``GaussianObjective`` whose target / precision require a gradient: the rollout stays native, its trajectory
+  comes back as a differentiable output (``autodiff.ComposedTrajectoryFunction``), and the objective is accumulated over the H
+  states in torch, which also carries the gradient of the objective's own parameters.  Head scale / shift gradients and a
+  trainable drift keep falling back."""
   uniform = solution_times is None
   if solution_times is None:
     solution_times = np.arange(1, 1 + num_steps, dtype=np.float64)     # pilco.py:186
@@ -241,7 +316,8 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       shape_reason = f"solver options {sorted(kwargs)}"
     else:
       why_not = []
-      fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not, native_actions=native_actions)
+      fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not, native_actions=native_actions,
+                                native_no_encoder=native_no_encoder, native_objective=native_objective)
       if fast is None:
         shape_reason = why_not[0] if why_not else "the system is not the shape mm_rollout_composed implements"
   if native is True and fast is None:
@@ -269,7 +345,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       return False
     models = [system.drift, getattr(getattr(system.policy, "model", None), "model", None)]
     trainable = any(t.requires_grad for m in models if m is not None for t in m._parameters())
-    if torch.is_grad_enabled() and (trainable or mx.requires_grad or Sxx.requires_grad):
+    if torch.is_grad_enabled() and (trainable or mx.requires_grad or Sxx.requires_grad or fast.uses_trajectory(mx)):
       return False                       # someone differentiates: the torch composition carries the autograd graph
     if trainable and torch.cuda.is_current_stream_capturing():
       # a captured graph must evaluate a trainable model FROM its parameters, not from a packed snapshot that goes
@@ -386,7 +462,8 @@ class GraphedPolicyLoss:
 def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, state_initializer: Callable, num_steps: int,
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
                                  generator: Optional[torch.Generator] = None, native_actions: int = 1,
-                                 native_inputs: int = 8, native_sampler: bool = False) -> Callable:
+                                 native_inputs: int = 8, native_sampler: bool = False,
+                                 native_no_encoder: bool = False) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -421,7 +498,11 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   torch-composition route alike: the drift's factor is cached per version of its parameters, a draw allocates and synchronises
   nothing, so a ``GraphedPolicyLoss`` of the closure captures, and each replay draws new paths (from the default generator:
   ``generator`` must be None for that).  The paths of a call live in the sampler's static buffers until the next call.  With
-  ``paths`` given the option changes nothing."""
+  ``paths`` given the option changes nothing.
+
+  ``native_no_encoder``: with the default False a system without an encoder takes the torch composition (``native=True`` raises);
+  True runs it in the native rollouts with na = 0 (the drift's inputs are (x, u), the cost that of the raw state), under the same
+  ``native_actions`` / ``native_inputs`` rules."""
   from . import ops
   from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
   drift = system.drift
@@ -429,7 +510,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     raise TypeError("pathwise_policy_loss_closure needs a PathwiseSVGP drift (gpflow_pilco/loops/pilco.py:230-236)")
   H = int(num_steps)
   why_not: list = []
-  parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False)
+  parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False,
+                                                     no_encoder=bool(native_no_encoder))
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
   max_native = int(native_actions)

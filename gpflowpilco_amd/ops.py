@@ -544,10 +544,12 @@ class ComposedRollout:
     return mx, Sxx, cost, tape
 
   def backward(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
-               policy: Optional[PackedModel] = None, want_state_grad: bool = True):
+               policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
     """``mm_rollout_composed_backward``: g_cost [H, B] -> (g_policy [B, M d + M + d + 2], g_mx0 [B,nx] | None,
     g_Sxx0 [B,nx,nx] | None): the gradient w.r.t. the packed policy (Z, beta, lengthscales^2, variance, mean) per batch
-    element and w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with (``taped(policy=...)``)."""
+    element and w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with (``taped(policy=...)``).
+    ``g_traj = (g_xm [H,B,nx], g_xS [H,B,nx,nx])``: seeds d loss / d (m_{h+1}, S_{h+1}) on the taped states, added to the sweep's
+    carry beside the built-in cost's adjoint (``mm_rollout_composed_backward_seeded``)."""
     pol = self._policy_pack(policy)
     dev = tape.device
     H = int(num_steps)
@@ -555,6 +557,7 @@ class ComposedRollout:
     g_cost = g_cost.to(f64).contiguous()
     if g_cost.shape != (H, B):
       raise ValueError(f"g_cost must be [H={H}, B={B}]")
+    g_xm, g_xS = self._seeds(g_traj, H, B)
     npar = pol.M * pol.d + pol.M + pol.d + 2
     g_pol = torch.empty(B, npar, dtype=f64, device=dev)
     g_m = torch.empty(B, self.nx, dtype=f64, device=dev) if want_state_grad else None
@@ -568,15 +571,52 @@ class ComposedRollout:
         raise ValueError("mm_compose_backward_workspace_bytes rejected the shape")
       wb = torch.empty(n, dtype=torch.uint8, device=dev)
       self._wsc[key] = wb
-    rc = lib().mm_rollout_composed_backward(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
-                                            float(dt), self.nx, self.na, self._act, self.scale, self.shift,
-                                            self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
-                                            g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_m), _ptr(g_S),
-                                            wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
-                                            self.drift.status().data_ptr(), _stream(dev))
+    head = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
+            float(dt), self.nx, self.na, self._act, self.scale, self.shift,
+            self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), g_cost.data_ptr())
+    tail = (g_pol.data_ptr(), _ptr(g_m), _ptr(g_S), wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
+            self.drift.status().data_ptr(), _stream(dev))
+    if g_traj is None:
+      rc = lib().mm_rollout_composed_backward(*head, *tail)
+    else:
+      rc = lib().mm_rollout_composed_backward_seeded(*head, _ptr(g_xm), _ptr(g_xS), *tail)
     check(rc, "mm_rollout_composed_backward")
     return g_pol, g_m, g_S
+
+  def _seeds(self, g_traj, H, B):
+    """``g_traj`` of ``backward`` / ``backward_nd`` as contiguous f64 tensors of the tape's shapes (``(None, None)`` passes the
+    seeded entry null seeds)."""
+    if g_traj is None:
+      return None, None
+    g_xm, g_xS = g_traj
+    if (g_xm is None) != (g_xS is None):
+      raise ValueError("g_traj: both seeds or neither")
+    if g_xm is None:
+      return None, None
+    g_xm, g_xS = g_xm.to(torch.float64).contiguous(), g_xS.to(torch.float64).contiguous()
+    if g_xm.shape != (H, B, self.nx) or g_xS.shape != (H, B, self.nx, self.nx):
+      raise ValueError(f"g_traj must be (g_xm [H={H}, B={B}, {self.nx}], g_xS [H, B, {self.nx}, {self.nx}])")
+    return g_xm, g_xS
+
+  def tape_states(self, tape: torch.Tensor, B: int, num_steps: int):
+    """The states x_1 .. x_H a taped rollout left on its tape: -> (xm [H, B, nx], xS [H, B, nx, nx]), float64 copies."""
+    H = int(num_steps)
+    if self.nu == 1:
+      n = lib().mm_compose_tape_bytes(B, H, self.nx, self.na, self.drift.M, MM_F64)
+      slot = lib().mm_compose_workspace_bytes(B, self.nx, self.na, MM_F64)
+    else:
+      n = lib().mm_compose_tape_bytes_nd(B, H, self.nx, self.na, self.nu, self.drift.M, MM_F64)
+      slot = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, MM_F64)
+    if n == 0 or tape.numel() < n or tape.dtype != torch.uint8:
+      raise ValueError("not a tape of this rollout")
+    # MMTapeLayout (csrc/mm_compose.h): H + 1 slots, then x_0 .. x_H means and covariances, each block aligned to 256 bytes
+    nx, align = self.nx, lambda v: (v + 255) // 256 * 256
+    off_m = (H + 1) * slot
+    off_S = align(off_m + (H + 1) * B * nx * 8)
+    xm = tape[off_m:off_m + (H + 1) * B * nx * 8].view(torch.float64).view(H + 1, B, nx)
+    xS = tape[off_S:off_S + (H + 1) * B * nx * nx * 8].view(torch.float64).view(H + 1, B, nx, nx)
+    return xm[1:].clone(), xS[1:].clone()
 
   # ---- the same for 1 to 4 actions (csrc/mm_compose_nd.hip, csrc/mm_compose_bwd_nd.hip) -----------------------------------
   def _head_arrays(self):
@@ -624,10 +664,11 @@ class ComposedRollout:
     return mx, Sxx, cost, tape
 
   def backward_nd(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
-                  policy: Optional[PackedModel] = None, want_state_grad: bool = True):
+                  policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
     """``mm_rollout_composed_backward_nd``: g_cost [H, B] -> (g_policy [B, nu, M d + M + d + 2], g_mx0 [B,nx] | None,
     g_Sxx0 [B,nx,nx] | None): per batch element and latent the gradient w.r.t. the packed policy (Z, beta, lengthscales^2,
-    variance, mean), and the gradient w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with."""
+    variance, mean), and the gradient w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with.
+    ``g_traj``: seeds on the taped states as in ``backward`` (``mm_rollout_composed_backward_nd_seeded``)."""
     pol = self._policy_pack(policy)
     dev = tape.device
     H = int(num_steps)
@@ -635,6 +676,7 @@ class ComposedRollout:
     g_cost = g_cost.to(f64).contiguous()
     if g_cost.shape != (H, B):
       raise ValueError(f"g_cost must be [H={H}, B={B}]")
+    g_xm, g_xS = self._seeds(g_traj, H, B)
     npar = pol.M * pol.d + pol.M + pol.d + 2
     g_pol = torch.empty(B, self.nu, npar, dtype=f64, device=dev)
     g_m = torch.empty(B, self.nx, dtype=f64, device=dev) if want_state_grad else None
@@ -649,13 +691,16 @@ class ComposedRollout:
       wb = torch.empty(n, dtype=torch.uint8, device=dev)
       self._wsc[key] = wb
     scale, shift = self._head_arrays()
-    rc = lib().mm_rollout_composed_backward_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                               pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
-                                               float(dt), self.nx, self.na, self._act, self.nu, scale, shift,
-                                               self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
-                                               g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_m), _ptr(g_S),
-                                               wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
-                                               self.drift.status().data_ptr(), _stream(dev))
+    head = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
+            float(dt), self.nx, self.na, self._act, self.nu, scale, shift,
+            self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), g_cost.data_ptr())
+    tail = (g_pol.data_ptr(), _ptr(g_m), _ptr(g_S), wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
+            self.drift.status().data_ptr(), _stream(dev))
+    if g_traj is None:
+      rc = lib().mm_rollout_composed_backward_nd(*head, *tail)
+    else:
+      rc = lib().mm_rollout_composed_backward_nd_seeded(*head, _ptr(g_xm), _ptr(g_xS), *tail)
     check(rc, "mm_rollout_composed_backward_nd")
     return g_pol, g_m, g_S
 

@@ -200,7 +200,11 @@ int mm_route_estimates(const void* packed, size_t packed_bytes, int L, int M, in
  * mx [B,nx] / Sxx [B,nx,nx] are updated in place; cost [H,B] (optional, needs target [ne], precis [ne,ne]) receives
  * the per-step statistic (the loss of pilco.py:199-205 is its sum over H); traj_* [H,B,..] optional.
  * active_dims: HOST array of na distinct state indices.  One action (Owen's T branch, bijectors.py:57-58); several
- * actions: mm_rollout_composed_nd below. */
+ * actions: mm_rollout_composed_nd below.
+ * na == 0 (a system without a periodic coordinate, forward_sde.py:49-68: mountain car) is taken by every rollout entry and
+ * size query of this header -- moment-matched and pathwise, one action, _nd and _wide: the encoding is the identity (e = x,
+ * ne = nx, nd = nx + nu, Cov(x, e) = Sxx), active_dims may be NULL, target / precis are those of the raw state, and every
+ * other bound stays as stated.  na < 0 is MM_E_DIM (0 from a size query). */
 size_t mm_compose_workspace_bytes(int B, int nx, int na, int dtype);
 int mm_rollout_composed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
                         const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
@@ -262,6 +266,22 @@ int mm_rollout_composed_backward(const void* drift_packed, size_t drift_bytes, i
                                  void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                  int32_t* status, void* stream);
 
+/* The same reverse sweep SEEDED on the trajectory: g_xm [H][B][nx] = d loss / d m_{h+1} and g_xS [H][B][nx][nx] =
+ * d loss / d S_{h+1} (both or neither, else MM_E_ARG; f64) are added to the carried adjoint of x_{h+1} in step h, before the
+ * built-in cost's adjoint, so g_cost keeps working beside them (all zeros: the seeds alone).  The taped states x_1 .. x_H thereby
+ * become differentiable outputs and any objective evaluated on them by the caller sits on the native chain.  Only the symmetric
+ * part of a seed on the symmetric S is determined: pass (G + G^T) / 2.  With null seeds the result is bit-equal to
+ * mm_rollout_composed_backward (one sweep serves both entries). */
+int mm_rollout_composed_backward_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                        const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                        int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                        double head_scale, double head_shift, const void* target, const void* precis,
+                                        const void* tape, size_t tape_bytes, const void* g_cost,
+                                        const void* g_xm, const void* g_xS,
+                                        void* g_policy, void* g_mx0, void* g_Sxx0,
+                                        void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                        int32_t* status, void* stream);
+
 /* ---- the same for a policy with nu actions (csrc/mm_compose_nd.hip, csrc/mm_compose_bwd_nd.hip; f64 only, else MM_E_DTYPE) ----
  * mm_rollout_composed_taped_nd is mm_rollout_composed_nd writing into a tape: H + 1 slots of the multi-action compose workspace,
  * the states x_0 .. x_H, and -- where H of them fit in 512 MB, by the rules of mm_compose_tape_bytes -- per step the drift match's
@@ -296,6 +316,16 @@ int mm_rollout_composed_backward_nd(const void* drift_packed, size_t drift_bytes
                                     const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
                                     void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                     int32_t* status, void* stream);
+/* ... seeded on the trajectory exactly as mm_rollout_composed_backward_seeded (g_xm [H][B][nx], g_xS [H][B][nx][nx]) */
+int mm_rollout_composed_backward_nd_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                           const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                           int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                           int nu, const double* head_scale, const double* head_shift,
+                                           const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                           const void* g_cost, const void* g_xm, const void* g_xS,
+                                           void* g_policy, void* g_mx0, void* g_Sxx0,
+                                           void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                           int32_t* status, void* stream);
 
 /* ---- backward w.r.t. the input moments, stage A (f64 mode) ---------------------
  * The M x M part of d(f1, Sff, cross)/d(mu, Sigma) reduced to M-sized sums (see csrc/mm_backward.hip);
