@@ -61,14 +61,18 @@ __global__ __launch_bounds__(256) void k_pw_head(MMComposeDims D, int S, int h, 
 // k_pw_policy_bwd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][npar] (ASSIGNED): per wave the
 // sum over its 64 samples and all steps of the packed policy's gradient (dZ [M][ne], dbeta [M], dls2 [ne], dvar, dmean);
 // g_x0 [S][nx] (optional).  g_cost [H][S] f64.
-template <typename T>
+// SEEDED (the _seeded entry with a seed on the states, or without the built-in cost): g_x [H][S][nx] f64, block h = d loss /
+// d x_{h+1}, one more term in the adjoint of x_{h+1} (NULL: none); g_cost NULL: the built-in cost is not part of the loss, its
+// term is skipped.  SEEDED = false is the sweep of the built-in cost alone (g_x is not read).
+template <typename T, bool SEEDED>
 __global__ __launch_bounds__(256) void k_pw_policy_bwd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
                                                        const T* __restrict__ dins, const T* __restrict__ jacs,
-                                                       const double* __restrict__ g_cost, const T* __restrict__ target,
-                                                       const T* __restrict__ precis, const double* __restrict__ pZ,
-                                                       const double* __restrict__ pbeta, const double* __restrict__ pls2,
-                                                       const double* __restrict__ pvar, const double* __restrict__ pmean, int pM,
-                                                       double scale, double shift, double* __restrict__ gpart,
+                                                       const double* __restrict__ g_cost, const double* __restrict__ g_x,
+                                                       const T* __restrict__ target, const T* __restrict__ precis,
+                                                       const double* __restrict__ pZ, const double* __restrict__ pbeta,
+                                                       const double* __restrict__ pls2, const double* __restrict__ pvar,
+                                                       const double* __restrict__ pmean, int pM, double scale, double shift,
+                                                       double* __restrict__ gpart,
                                                        double* __restrict__ g_x0) {
   extern __shared__ double sm[];
   const int nx = D.nx, ne = D.ne, nd = D.nd, npar = pM * ne + pM + ne + 2;
@@ -92,11 +96,17 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd(MMComposeDims D, int S, i
     double x1[MMC_NX], e1[MMP_NE], ge[MMP_NE];
     // adjoint of x_{h+1}: what later steps left in gx, plus this step's cost of its encoding
     for (int i = 0; i < nx; ++i) x1[i] = (double)xs[((size_t)(h + 1) * S + sr) * nx + i];
-    mmp_encode(D, x1, e1);
-    mmp_cost(ne, e1, tg, W, ge);
-    const double gc = live ? g_cost[(size_t)h * S + sr] : 0.0;
-    for (int i = 0; i < ne; ++i) ge[i] *= gc;
-    mmp_encode_bwd(D, x1, ge, gx);
+    if (SEEDED && g_x) {                                     // seed block h belongs to x_{h+1}; idle lanes read a zero seed
+      const double* sx = g_x + ((size_t)h * S + sr) * nx;
+      for (int i = 0; i < nx; ++i) gx[i] += live ? sx[i] : 0.0;
+    }
+    if (!SEEDED || g_cost) {
+      mmp_encode(D, x1, e1);
+      mmp_cost(ne, e1, tg, W, ge);
+      const double gc = live ? g_cost[(size_t)h * S + sr] : 0.0;
+      for (int i = 0; i < ne; ++i) ge[i] *= gc;
+      mmp_encode_bwd(D, x1, ge, gx);
+    }
     // x_{h+1} = x_h + dt f(d_h):  g d = dt J^T g x_{h+1}
     double gd[MMP_NE + 1], e[MMP_NE];
     const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
@@ -238,15 +248,16 @@ extern "C" size_t mm_pathwise_backward_scratch_bytes(int S, int policy_M, int ne
   return (size_t)((S + 255) / 256) * 4 * (size_t)(policy_M * ne + policy_M + ne + 2) * sizeof(double);
 }
 
-extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
-                                                   const void* policy_packed, size_t policy_bytes, int policy_M,
-                                                   double head_scale, double head_shift, const void* target, const void* precis,
-                                                   const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
-                                                   void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+// the backward entries: the unseeded one (g_cost required, g_x = nullptr) and the _seeded one (either seed may be NULL, not both)
+static int mmp_backward(bool seeded_entry, int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                        const void* policy_packed, size_t policy_bytes, int policy_M, double head_scale, double head_shift,
+                        const void* target, const void* precis, const void* tape, size_t tape_bytes, const void* g_cost,
+                        const void* g_x, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
   MMComposeDims D;
   int rc = mmp_check(S, 1, 1, dtype, H, nx, na, active_dims, policy_M, D);
   if (rc) return rc;
-  if (!policy_packed || !target || !precis || !tape || !g_cost || !g_policy || !scratch) return MM_E_ARG;
+  if (!policy_packed || !target || !precis || !tape || (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch)
+    return MM_E_ARG;
   const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, 1, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   const int ne = D.ne, npar = policy_M * ne + policy_M + ne + 2;
@@ -258,19 +269,23 @@ extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, doub
   const size_t lds = mmp_head_lds(policy_M, ne) + (size_t)4 * npar * sizeof(double);
   if (lds > 160 * 1024) return MM_E_DIM;
   const dim3 grid((S + 255) / 256);
-#define MMP_BWD(T_)                                                                                                              \
+  // (the built-in cost alone: the unseeded instantiation, whichever entry was called -- same arithmetic, bit-equal outputs)
+  const bool seeded = g_x != nullptr || g_cost == nullptr;
+#define MMP_BWD(T_, SEEDED_)                                                                                                     \
   do {                                                                                                                          \
     if (lds > 64 * 1024) {                                                                                                      \
-      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd<T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd<T_, SEEDED_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                          (int)lds);                                                                            \
       if (ea != hipSuccess) return (int)ea;                                                                                     \
     }                                                                                                                           \
-    hipLaunchKernelGGL((k_pw_policy_bwd<T_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x), (const T_*)(tp + tl.din), \
-                       (const T_*)(tp + tl.jac), (const double*)g_cost, (const T_*)target, (const T_*)precis,                    \
-                       (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2),              \
-                       (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M, head_scale, head_shift,           \
-                       (double*)scratch, (double*)g_x0);                                                                        \
+    hipLaunchKernelGGL((k_pw_policy_bwd<T_, SEEDED_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),             \
+                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const double*)g_x,            \
+                       (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),      \
+                       (const double*)(pp + pl.ls2), (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M,     \
+                       head_scale, head_shift, (double*)scratch, (double*)g_x0);                                                \
   } while (0)
-  if (dtype == MM_F64) MMP_BWD(double); else MMP_BWD(float);
+  if (dtype == MM_F64) { if (seeded) MMP_BWD(double, true); else MMP_BWD(double, false); }
+  else { if (seeded) MMP_BWD(float, true); else MMP_BWD(float, false); }
 #undef MMP_BWD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -278,4 +293,23 @@ extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, doub
                      (double*)g_policy);
   e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
+}
+
+extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                   const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                   double head_scale, double head_shift, const void* target, const void* precis,
+                                                   const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
+                                                   void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+  return mmp_backward(false, S, dtype, H, dt, nx, na, active_dims, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
+                      target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int H, double dt, int nx, int na,
+                                                          const int32_t* active_dims, const void* policy_packed,
+                                                          size_t policy_bytes, int policy_M, double head_scale, double head_shift,
+                                                          const void* target, const void* precis, const void* tape,
+                                                          size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
+                                                          void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+  return mmp_backward(true, S, dtype, H, dt, nx, na, active_dims, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
+                      target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch, scratch_bytes, stream);
 }

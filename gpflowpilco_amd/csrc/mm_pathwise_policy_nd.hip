@@ -78,14 +78,17 @@ __global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int 
 // k_pw_policy_bwd_nd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][NU][npar1] (ASSIGNED): per
 // wave the sum over its 64 samples and all steps of the packed policy's gradient, per latent dZ [M][ne], dbeta [M], dls2 [ne],
 // dvar, dmean (npar1 = M ne + M + ne + 2);  g_x0 [S][nx] (optional).  g_cost [H][S] f64.
-template <typename T, int NU>
+// SEEDED (the _seeded entries with a seed on the states, or without the built-in cost): g_x [H][S][nx] f64, block h = d loss /
+// d x_{h+1} (NULL: none); g_cost NULL: the built-in cost's term is skipped.  SEEDED = false: the built-in cost alone.
+template <typename T, int NU, bool SEEDED>
 __global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
                                                           const T* __restrict__ dins, const T* __restrict__ jacs,
-                                                          const double* __restrict__ g_cost, const T* __restrict__ target,
-                                                          const T* __restrict__ precis, const double* __restrict__ pZ,
-                                                          const double* __restrict__ pbeta, const double* __restrict__ pls2,
-                                                          const double* __restrict__ pvar, const double* __restrict__ pmean,
-                                                          int pM, MMHeadND hd, double* __restrict__ gpart,
+                                                          const double* __restrict__ g_cost, const double* __restrict__ g_x,
+                                                          const T* __restrict__ target, const T* __restrict__ precis,
+                                                          const double* __restrict__ pZ, const double* __restrict__ pbeta,
+                                                          const double* __restrict__ pls2, const double* __restrict__ pvar,
+                                                          const double* __restrict__ pmean, int pM, MMHeadND hd,
+                                                          double* __restrict__ gpart,
                                                           double* __restrict__ g_x0) {
   extern __shared__ double sm[];
   const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne, npar1 = blk + 2, npar = NU * npar1;
@@ -112,11 +115,17 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S
     double x1[MMC_NX], e1[MMP_NE], ge[MMP_NE];
     // adjoint of x_{h+1}: what later steps left in gx, plus this step's cost of its encoding
     for (int i = 0; i < nx; ++i) x1[i] = (double)xs[((size_t)(h + 1) * S + sr) * nx + i];
-    mmp_encode(D, x1, e1);
-    mmp_cost(ne, e1, tg, W, ge);
-    const double gc = live ? g_cost[(size_t)h * S + sr] : 0.0;
-    for (int i = 0; i < ne; ++i) ge[i] *= gc;
-    mmp_encode_bwd(D, x1, ge, gx);
+    if (SEEDED && g_x) {                                     // seed block h belongs to x_{h+1}; idle lanes read a zero seed
+      const double* sx = g_x + ((size_t)h * S + sr) * nx;
+      for (int i = 0; i < nx; ++i) gx[i] += live ? sx[i] : 0.0;
+    }
+    if (!SEEDED || g_cost) {
+      mmp_encode(D, x1, e1);
+      mmp_cost(ne, e1, tg, W, ge);
+      const double gc = live ? g_cost[(size_t)h * S + sr] : 0.0;
+      for (int i = 0; i < ne; ++i) ge[i] *= gc;
+      mmp_encode_bwd(D, x1, ge, gx);
+    }
     // x_{h+1} = x_h + dt f(d_h):  g d = dt J^T g x_{h+1}
     double gd[MMP_NE + MMC_NU], e[MMP_NE];
     const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
@@ -304,17 +313,19 @@ extern "C" size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, i
   return mmp_nd_scratch_bytes(16, S, policy_M, ne, nu);
 }
 
-// the backward entries: _nd (nd_max = 8) and _wide (nd_max = 16) are this function
-static int mmp_nd_backward(int nd_max, int S, int dtype, int H, double dt, int nx, int na,
+// the backward entries: _nd (nd_max = 8) and _wide (nd_max = 16), unseeded (g_cost required, g_x = nullptr) and _seeded (either
+// seed may be NULL, not both), are this function
+static int mmp_nd_backward(int nd_max, bool seeded_entry, int S, int dtype, int H, double dt, int nx, int na,
                            const int32_t* active_dims, int nu, const void* policy_packed,
                            size_t policy_bytes, int policy_M, const double* head_scale,
                            const double* head_shift, const void* target, const void* precis,
-                           const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
+                           const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
                            void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
   MMComposeDims D;
   int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
-  if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape || !g_cost || !g_policy || !scratch)
+  if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape ||
+      (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch)
     return MM_E_ARG;
   const int ne = D.ne, npar = nu * (policy_M * ne + policy_M + ne + 2);
   const size_t lds = mmp_nd_bwd_lds(policy_M, ne, nu);
@@ -329,21 +340,23 @@ static int mmp_nd_backward(int nd_max, int S, int dtype, int H, double dt, int n
   const char* pp = (const char*)policy_packed; const char* tp = (const char*)tape;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((S + 255) / 256);
-#define MMP_BWD(T_, NU_)                                                                                                          \
+  // (the built-in cost alone: the unseeded instantiation, whichever entry was called -- same arithmetic, bit-equal outputs)
+  const bool seeded = g_x != nullptr || g_cost == nullptr;
+#define MMP_BWD(T_, NU_, SEEDED_)                                                                                                 \
   do {                                                                                                                          \
     if (lds > 64 * 1024) {                                                                                                      \
-      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                          (int)lds);                                                                            \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_, SEEDED_>,                                     \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
       if (ea != hipSuccess) return (int)ea;                                                                                     \
     }                                                                                                                           \
-    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),              \
-                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const T_*)target,            \
-                       (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),                        \
+    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_, SEEDED_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),     \
+                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const double*)g_x,           \
+                       (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),     \
                        (const double*)(pp + pl.ls2), (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M, hd, \
                        (double*)scratch, (double*)g_x0);                                                                        \
   } while (0)
-#define MMP_BWD_F64(NU_) MMP_BWD(double, NU_)
-#define MMP_BWD_F32(NU_) MMP_BWD(float, NU_)
+#define MMP_BWD_F64(NU_) if (seeded) MMP_BWD(double, NU_, true); else MMP_BWD(double, NU_, false)
+#define MMP_BWD_F32(NU_) if (seeded) MMP_BWD(float, NU_, true); else MMP_BWD(float, NU_, false)
   if (dtype == MM_F64) { MMP_ND_DISPATCH(nu, MMP_BWD_F64) } else { MMP_ND_DISPATCH(nu, MMP_BWD_F32) }
 #undef MMP_BWD_F64
 #undef MMP_BWD_F32
@@ -358,8 +371,18 @@ static int mmp_nd_backward(int nd_max, int S, int dtype, int H, double dt, int n
                        const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
                        const double* head_shift, const void* target, const void* precis, const void* tape, size_t tape_bytes,    \
                        const void* g_cost, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {      \
-    return mmp_nd_backward(nd_max_, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M, head_scale,  \
-                           head_shift, target, precis, tape, tape_bytes, g_cost, g_policy, g_x0, scratch, scratch_bytes, stream); \
+    return mmp_nd_backward(nd_max_, false, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M,       \
+                           head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch,   \
+                           scratch_bytes, stream);                                                                              \
+  }                                                                                                                             \
+  extern "C" int name_##_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,          \
+                                const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,          \
+                                const double* head_shift, const void* target, const void* precis, const void* tape,              \
+                                size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy, void* g_x0,              \
+                                void* scratch, size_t scratch_bytes, void* stream) {                                            \
+    return mmp_nd_backward(nd_max_, true, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M,        \
+                           head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch,       \
+                           scratch_bytes, stream);                                                                              \
   }
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_nd, 8)
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_wide, 16)

@@ -463,7 +463,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
                                  generator: Optional[torch.Generator] = None, native_actions: int = 1,
                                  native_inputs: int = 8, native_sampler: bool = False,
-                                 native_no_encoder: bool = False) -> Callable:
+                                 native_no_encoder: bool = False, native_objective: bool = False) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -502,16 +502,32 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
 
   ``native_no_encoder``: with the default False a system without an encoder takes the torch composition (``native=True`` raises);
   True runs it in the native rollouts with na = 0 (the drift's inputs are (x, u), the cost that of the raw state), under the same
-  ``native_actions`` / ``native_inputs`` rules."""
+  ``native_actions`` / ``native_inputs`` rules.
+
+  ``native_objective``: with the default False only a constant ``GaussianObjective`` runs natively (its cost is computed in the
+  rollout's kernels).  True also takes any other objective of a tensor of states, and a ``GaussianObjective`` whose target /
+  precision require a gradient: the rollout stays native with a zero built-in cost, its states x_1 .. x_H come back as a
+  differentiable output (``pathwise.PolicyTrajectoryFunction``; forward only under ``no_grad`` when neither the policy nor the
+  initial states require a gradient), and the loss is the reference's accumulation (pilco.py:272-275) in torch on them: the whole
+  [H, S, nx] block encoded in one call, then ``objective(x=encoder(x_h), t=h dt)`` per step.  The seeded reverse sweep
+  (``mm_pathwise_policy_rollout_backward[_nd|_wide]_seeded``) carries d loss / d x_h back to the policy and the initial states; the
+  objective's own parameters get their gradients from the torch part.  A constant ``GaussianObjective`` keeps the in-kernel cost.
+  The option composes with ``native_actions``, ``native_inputs``, ``native_no_encoder``, ``native_sampler`` and ``paths`` under their
+  rules; head scale / shift gradients keep falling back."""
   from . import ops
-  from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction
+  from .components import TrigonometricEncoder
+  from .cost import GaussianObjective
+  from .linalg import index_tensor
+  from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction, PolicyTrajectoryFunction
   drift = system.drift
   if not isinstance(drift, PathwiseSVGP):
     raise TypeError("pathwise_policy_loss_closure needs a PathwiseSVGP drift (gpflow_pilco/loops/pilco.py:230-236)")
   H = int(num_steps)
   why_not: list = []
   parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False,
-                                                     no_encoder=bool(native_no_encoder))
+                                                     no_encoder=bool(native_no_encoder),
+                                                     any_objective=bool(native_objective))
+  gaussian = isinstance(objective, GaussianObjective)
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
   max_native = int(native_actions)
@@ -550,6 +566,38 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       samplers[key] = PathSampler(drift, x0.shape[0], num_bases, dtype=x0.dtype, device=x0.device)
     return samplers[key].draw(generator=generator)
 
+  def _uses_trajectory() -> bool:
+    """The objective is evaluated in torch on the native rollout's states (``native_objective``)."""
+    if not native_objective:
+      return False
+    if not gaussian:
+      return True
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for t in (objective.target, objective.precis))
+
+  def _encode(xs):
+    """``system.encoder(xs)``.  A plain ``TrigonometricEncoder`` is evaluated by its own transform on columns selected with cached
+    device index tensors (``linalg.index_tensor``): ``Encoder.__call__`` indexes with a Python list, which uploads the indices on
+    every call -- a copy a HIP-graph capture of the closure refuses.  A subclass keeps its own ``__call__``."""
+    enc = system.encoder
+    if enc is None:
+      return xs
+    if type(enc) is not TrigonometricEncoder:
+      return enc(xs)
+    active, inactive = enc.get_partition_indices(ndims=xs.shape[-1])
+    if not active:
+      return xs
+    ret = enc.transform(xs.index_select(-1, index_tensor(active, xs.device)))
+    return torch.cat([ret, xs.index_select(-1, index_tensor(inactive, xs.device))], dim=-1) if inactive else ret
+
+  def _objective_of_states(xs):
+    """pilco.py:272-275 over the states x_1 .. x_H (xs [H, S, nx]) at the times dt, 2 dt, ..: one encoder call for the block."""
+    e = _encode(xs)
+    loss = torch.zeros(xs.shape[1], dtype=xs.dtype, device=xs.device)
+    for h in range(H):
+      loss = loss + objective(x=e[h], t=dt * float(h + 1))
+    return loss
+
   def _closure():
     x0 = state_initializer()
     pth = paths if paths is not None else _new_paths(x0)
@@ -577,8 +625,13 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     elif nd > 8 or pol_M > 256:
       _fallback(f"drift inputs of dimension nx + na + nu = {nd} > 8 or a policy of more than 256 centres ({pol_M})")
       return _torch_loss(x0, pth)
-    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift,
-               "objective.target": objective.target, "objective.precis": objective.precis}
+    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift}
+    # (with native_objective the objective's own parameters are differentiated by the torch part.  Without it ``parts`` is only
+    # non-None for a GaussianObjective -- ``_native_parts`` refused every other one above -- so .target / .precis exist here; an
+    # objective of the caller's own has neither and must not be asked for them)
+    if not native_objective:
+      outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
+    traj = _uses_trajectory()
     grad = torch.is_grad_enabled()
     if grad:
       for name, t in outside.items():
@@ -587,19 +640,33 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
           return _torch_loss(x0, pth)
     scale, shift = head_constants()
     pol_pack = pm_.packed(torch.float64, False, x0.device)
+    # (the trajectory route: a zero built-in cost, its output ignored)
     roll = PolicyRollout(pth, pol_pack, nx=nx, active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
-                         target=objective.target, precis=objective.precis, wide=nd > 8)
+                         target=None if traj else objective.target, precis=None if traj else objective.precis, wide=nd > 8)
     needs = grad and (x0.requires_grad or any(t.requires_grad for t in pm_._parameters()))
     if needs and not roll.supports_backward():
       _fallback(f"the native reverse sweep does not take nu = {nu} actions with {pol_M} centres on {nx + na} inputs (its LDS bound)")
       return _torch_loss(x0, pth)
     if not needs:
       with torch.no_grad():
-        cost, _ = roll(x0, H, dt=dt)
-      return cost.sum(0)
+        pol = None
+        if traj and torch.cuda.is_current_stream_capturing() and any(t.requires_grad for t in pm_._parameters()):
+          # a captured forward of a trainable policy packs it FROM its parameters inside the graph, so that replays follow the
+          # optimiser's in-place updates (the cached pack is a snapshot: native_policy_loss's run.from_parameters).  Only on
+          # the trajectory route, which is new: the built-in-cost branch below is deliberately left as it was -- a captured
+          # forward-only graph of it keeps reading the snapshot taken at capture (its loss_and_grad graph packs from the
+          # parameters already) -- so that nothing changes with the option off; treating both alike is a change of its own
+          Zp, lsp, varp, betap, _, mcp = pm_.precompute(x0.device)
+          pol = ops.pack_model(Zp, lsp, varp, betap, None, mcp, dtype=torch.float64, sync=False)
+        cost, tape = roll(x0, H, dt=dt, policy=pol)
+      # (the trajectory route: the states are constants here; an objective parameter that requires a gradient still gets it)
+      return _objective_of_states(roll.trajectory(tape, H)) if traj else cost.sum(0)
     Zp, lsp, varp, betap, _, mcp = pm_.precompute(x0.device)
     if mcp is None:
       mcp = torch.zeros(nu, dtype=Zp.dtype, device=x0.device)
+    if traj:
+      _, xs = PolicyTrajectoryFunction.apply(x0, Zp, lsp, varp, betap, mcp, roll, H, dt)
+      return _objective_of_states(xs).to(x0.dtype)
     return PolicyRolloutFunction.apply(x0, Zp, lsp, varp, betap, mcp, roll, H, dt).sum(1).to(x0.dtype)
 
   return _closure

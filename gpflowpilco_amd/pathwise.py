@@ -379,10 +379,16 @@ class PolicyRollout:
   ``__call__(x0, H)`` -> ``(cost [H, S], tape)``; ``backward(tape, g_cost)`` -> ``(g_policy, g_x0 [S, nx] | None)`` with
   g_policy [M ne + M + ne + 2] from the one-action entries and [nu, M ne + M + ne + 2] from the ``_nd`` ones (per latent dZ,
   dbeta, d ls^2, dvar, dmean).  ``supports_backward()``: whether the reverse sweep takes this shape (its LDS bound:
-  include/gpflowpilco_mm.h)."""
+  include/gpflowpilco_mm.h).
+
+  ``target`` / ``precis`` None: a zero target and a zero precision of the right size (the entries need the pointers); the cost
+  output is then meaningless -- the rollout of a caller whose loss is its own function of the states: ``trajectory(tape, H)`` gives
+  x_1 .. x_H, and ``backward(..., g_states=...)`` (the ``_seeded`` entries) carries d loss / d x_1 .. x_H back to the policy and
+  to x_0, with or without a ``g_cost`` of the built-in cost beside it."""
 
   def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
-               target: torch.Tensor, precis: torch.Tensor, nd_entries: Optional[bool] = None, wide: bool = False):
+               target: Optional[torch.Tensor] = None, precis: Optional[torch.Tensor] = None, nd_entries: Optional[bool] = None,
+               wide: bool = False):
     S, L, Mp, Kp, d = paths._dims()
     self.paths, self.policy = paths, policy
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
@@ -419,8 +425,11 @@ class PolicyRollout:
       self._scale_c, self._shift_c = (_lib.C.c_double * self.nu)(*scales), (_lib.C.c_double * self.nu)(*shifts)
     else:
       self.scale, self.shift = scales[0], shifts[0]
-    self.target = target.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
-    self.precis = precis.to(dtype=paths.dtype, device=paths.wb.device).contiguous()
+    dev = paths.wb.device
+    self.target = (torch.zeros(self.ne, dtype=paths.dtype, device=dev) if target is None else
+                   target.to(dtype=paths.dtype, device=dev).contiguous())
+    self.precis = (torch.zeros(self.ne, self.ne, dtype=paths.dtype, device=dev) if precis is None else
+                   precis.to(dtype=paths.dtype, device=dev).contiguous())
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
     self._sfx = "wide" if self.wide else "nd"                  # which set of entries with the _nd signatures
 
@@ -481,16 +490,38 @@ class PolicyRollout:
     n = (num_steps + 1) * S * self.nx
     return tape[:n * es].view(self.paths.dtype).view(num_steps + 1, S, self.nx)
 
-  def backward(self, tape: torch.Tensor, g_cost: torch.Tensor, num_steps: int, dt: float = 1.0, policy=None,
-               want_state_grad: bool = False):
+  def trajectory(self, tape: torch.Tensor, num_steps: int) -> torch.Tensor:
+    """x_1 .. x_H [H, S, nx] (a view of the tape): the states the per-step objective is evaluated on."""
+    return self.states(tape, num_steps)[1:]
+
+  def backward(self, tape: torch.Tensor, g_cost: Optional[torch.Tensor], num_steps: int, dt: float = 1.0, policy=None,
+               want_state_grad: bool = False, g_states: Optional[torch.Tensor] = None):
+    """``g_states`` [H, S, nx] (any float dtype): block h = d loss / d x_{h+1}, the gradient w.r.t. ``trajectory(tape, H)`` -- the
+    ``_seeded`` entries; ``g_cost`` may then be None (the built-in cost is not part of the loss).  Without ``g_states``: the
+    unseeded entries."""
     pol = self._policy(policy)
-    S, H, code = self.paths.num_samples, int(num_steps), _dtype_code(self.paths.dtype)
-    dev = tape.device
-    g_cost = g_cost.to(torch.float64).contiguous()
-    if g_cost.shape != (H, S):
-      raise ValueError(f"g_cost must be [H={H}, S={S}]")
+    S, H = self.paths.num_samples, int(num_steps)
+    if g_cost is None and g_states is None:
+      raise ValueError("g_cost may be None only when g_states is given")
+    if g_cost is not None:
+      g_cost = g_cost.to(torch.float64).contiguous()
+      if g_cost.shape != (H, S):
+        raise ValueError(f"g_cost must be [H={H}, S={S}]")
+    if g_states is not None:
+      g_states = g_states.to(torch.float64).contiguous()
+      if g_states.shape != (H, S, self.nx):
+        raise ValueError(f"g_states must be [H={H}, S={S}, nx={self.nx}]")
+      _require_device(g_states, tape)
+    return self._sweep(pol, tape, g_cost, g_states, H, float(dt), want_state_grad, seeded=g_states is not None)
+
+  def _sweep(self, pol, tape, g_cost, g_states, H, dt, want_state_grad, seeded):
+    """One reverse sweep: the unseeded entry of this rollout's family (one action, ``_nd``, ``_wide``), or -- ``seeded`` -- its
+    ``_seeded`` sibling, which takes ``g_x`` after ``g_cost`` (either may be None -> NULL).  g_cost [H, S], g_states [H, S, nx]:
+    contiguous f64."""
+    S, code, dev = self.paths.num_samples, _dtype_code(self.paths.dtype), tape.device
     npar = pol.M * self.ne + pol.M + self.ne + 2
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
+    seeds = (_ptr(g_cost), _ptr(g_states)) if seeded else (g_cost.data_ptr(),)
     lib = _lib.lib()
     if self.nd_entries:
       ns = getattr(lib, f"mm_pathwise_backward_scratch_bytes_{self._sfx}")(S, pol.M, self.ne, self.nu)
@@ -498,25 +529,51 @@ class PolicyRollout:
         raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
                          "slabs exceed 160 KiB of LDS (see supports_backward)")
       g_pol = torch.empty(self.nu, npar, dtype=torch.float64, device=dev)
-      scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
-      entry = f"mm_pathwise_policy_rollout_backward_{self._sfx}"
-      rc = getattr(lib, entry)(S, code, H, float(dt), self.nx, self.na, self._act, self.nu,
-                               pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c,
-                               self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(),
-                               tape.numel(), g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0),
-                               scratch.data_ptr(), scratch.numel(), _stream(dev))
-      check(rc, entry)
-      return g_pol, g_x0
-    g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
-    ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
+      entry = f"mm_pathwise_policy_rollout_backward_{self._sfx}" + ("_seeded" if seeded else "")
+      head = (self.nu, pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c)
+    else:
+      ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
+      g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
+      entry = "mm_pathwise_policy_rollout_backward" + ("_seeded" if seeded else "")
+      head = (pol.buf.data_ptr(), pol.nbytes, pol.M, self.scale, self.shift)
     scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
-    rc = lib.mm_pathwise_policy_rollout_backward(S, code, H, float(dt), self.nx, self.na, self._act, pol.buf.data_ptr(),
-                                                 pol.nbytes, pol.M, self.scale, self.shift, self.target.data_ptr(),
-                                                 self.precis.data_ptr(), tape.data_ptr(), tape.numel(),
-                                                 g_cost.data_ptr(), g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
-                                                 scratch.numel(), _stream(dev))
-    check(rc, "mm_pathwise_policy_rollout_backward")
+    rc = getattr(lib, entry)(S, code, H, dt, self.nx, self.na, self._act, *head, self.target.data_ptr(), self.precis.data_ptr(),
+                             tape.data_ptr(), tape.numel(), *seeds, g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
+                             scratch.numel(), _stream(dev))
+    check(rc, entry)
     return g_pol, g_x0
+
+
+def _taped_policy_rollout(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt):
+  """The forward of the two autograd functions below: pack the policy from its packed coordinates, run the taped rollout, keep what
+  the backward needs on ``ctx``.  -> (cost [H, S], tape)."""
+  from . import ops
+  f64 = torch.float64
+  det = lambda t: t.detach().to(f64)
+  pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
+  cost, tape = roll(x0.detach(), num_steps, dt=dt, with_jacobians=True, policy=pol)
+  ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt = roll, pol, tape, int(num_steps), float(dt)
+  ctx.save_for_backward(ls)
+  ctx.need_state = x0.requires_grad
+  ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+  ctx.x_dtype = x0.dtype
+  return cost, tape
+
+
+def _policy_rollout_gradients(ctx, g_cost, g_states=None):
+  """The backward of the two autograd functions below: one reverse sweep, its packed gradient split per input."""
+  (ls,) = ctx.saved_tensors
+  g, g_x0 = ctx.roll.backward(ctx.tape, None if g_cost is None else g_cost.T.contiguous(), ctx.H, dt=ctx.dt, policy=ctx.pol,
+                              want_state_grad=ctx.need_state, g_states=g_states)
+  M, d = ctx.pol.M, ctx.pol.d
+  zs, lss, vs, bs, ms = ctx.shapes
+  g = g.reshape(ctx.pol.L, -1)                                                           # per latent: dZ, dbeta, d ls^2, dvar, dmean
+  gZ = g[:, :M * d].reshape(zs)
+  gbeta = g[:, M * d:M * d + M].reshape(bs)
+  gls = (2.0 * ls.detach().reshape(-1, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)  # d/d ls = 2 ls d/d ls^2
+  gvar = g[:, M * d + M + d].reshape(vs)
+  gmean = g[:, M * d + M + d + 1].reshape(ms)
+  return (None if g_x0 is None else g_x0.to(ctx.x_dtype)), gZ, gls, gvar, gbeta, gmean, None, None, None
 
 
 class PolicyRolloutFunction(torch.autograd.Function):
@@ -527,28 +584,30 @@ class PolicyRolloutFunction(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt):
-    from . import ops
-    f64 = torch.float64
-    det = lambda t: t.detach().to(f64)
-    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-    cost, tape = roll(x0.detach(), num_steps, dt=dt, with_jacobians=True, policy=pol)
-    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt = roll, pol, tape, int(num_steps), float(dt)
-    ctx.save_for_backward(ls)
-    ctx.need_state = x0.requires_grad
-    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
-    ctx.x_dtype = x0.dtype
+    cost, _ = _taped_policy_rollout(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt)
     return cost.T.contiguous()
 
   @staticmethod
   def backward(ctx, g_cost):
-    (ls,) = ctx.saved_tensors
-    g, g_x0 = ctx.roll.backward(ctx.tape, g_cost.T.contiguous(), ctx.H, dt=ctx.dt, policy=ctx.pol, want_state_grad=ctx.need_state)
-    M, d = ctx.pol.M, ctx.pol.d
-    zs, lss, vs, bs, ms = ctx.shapes
-    g = g.reshape(ctx.pol.L, -1)                                                           # per latent: dZ, dbeta, d ls^2, dvar, dmean
-    gZ = g[:, :M * d].reshape(zs)
-    gbeta = g[:, M * d:M * d + M].reshape(bs)
-    gls = (2.0 * ls.detach().reshape(-1, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)  # d/d ls = 2 ls d/d ls^2
-    gvar = g[:, M * d + M + d].reshape(vs)
-    gmean = g[:, M * d + M + d + 1].reshape(ms)
-    return (None if g_x0 is None else g_x0.to(ctx.x_dtype)), gZ, gls, gvar, gbeta, gmean, None, None, None
+    return _policy_rollout_gradients(ctx, g_cost)
+
+
+class PolicyTrajectoryFunction(torch.autograd.Function):
+  """``PolicyRolloutFunction`` with the STATES as a second differentiable output, for a loss the caller evaluates on the sample
+  trajectory (a caller-defined objective: ``loops.pathwise_policy_loss_closure(native_objective=True)``) -- the pathwise analogue
+  of ``autodiff.ComposedTrajectoryFunction``.  Same inputs; outputs ``(cost [S, H], states [H, S, nx])``: the built-in cost (of
+  ``roll``'s target / precision; meaningless when those are zero) and x_1 .. x_H, a copy of the tape's block (the caller may edit
+  it in place; the backward reads the tape).  Backward: whichever of the two output gradients arrived goes into the seeded reverse
+  sweep (``mm_pathwise_policy_rollout_backward[_nd|_wide]_seeded``), NULL for the one autograd did not produce."""
+
+  @staticmethod
+  def forward(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt):
+    cost, tape = _taped_policy_rollout(ctx, x0, Z, ls, var, beta, mean_c, roll, num_steps, dt)
+    ctx.set_materialize_grads(False)                       # an output the loss does not use arrives as None, not as zeros
+    return cost.T.contiguous(), roll.trajectory(tape, num_steps).clone()
+
+  @staticmethod
+  def backward(ctx, g_cost, g_states):
+    if g_cost is None and g_states is None:
+      return (None,) * 9
+    return _policy_rollout_gradients(ctx, g_cost, g_states)    # (g_states None: the built-in cost alone, the unseeded sweep)

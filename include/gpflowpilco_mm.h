@@ -452,6 +452,19 @@ int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, double dt, int 
                                         double head_scale, double head_shift, const void* target, const void* precis,
                                         const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                         void* scratch, size_t scratch_bytes, void* stream);
+/* The reverse sweep with a seed on the STATES, for a loss the caller evaluates on the taped trajectory (a caller-defined objective
+ * on sample paths: loops/pilco.py:272-275 calls self.objective(x = encoder(state), t = t) per step).  The argument list of
+ * mm_pathwise_policy_rollout_backward with g_x after g_cost:  g_x [H][S][nx] f64, block h = d loss / d x_{h+1} -- the state the
+ * tape stores at index h + 1, the convention of g_xm in mm_rollout_composed_backward_seeded -- read in f64 whatever the tape's
+ * element type.  g_x may be NULL (then the entry is the unseeded one, bit for bit); g_cost may be NULL: the built-in cost is not
+ * part of the loss and its term is skipped (target / precis must still be valid device buffers of ne and ne x ne elements: the
+ * kernels stage them as always, only their values are ignored).  Both NULL: MM_E_ARG.  Every other
+ * refusal, the scratch size, the LDS bound and the outputs are the unseeded entry's. */
+int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                               const void* policy_packed, size_t policy_bytes, int policy_M,
+                                               double head_scale, double head_shift, const void* target, const void* precis,
+                                               const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                               void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the same for policies with SEVERAL actions (csrc/mm_pathwise_policy_nd.hip): 1 <= nu <= 4 ------------------------------
  * On sample paths the policy is evaluated pointwise, so its nu actions are nu independent heads appended to the encoding in
@@ -484,6 +497,13 @@ int mm_pathwise_policy_rollout_backward_nd(int S, int dtype, int H, double dt, i
                                            const void* target, const void* precis,
                                            const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                            void* scratch, size_t scratch_bytes, void* stream);
+/* ... with a seed on the states: g_x [H][S][nx] f64 after g_cost, as in mm_pathwise_policy_rollout_backward_seeded above. */
+int mm_pathwise_policy_rollout_backward_nd_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                  int nu, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                  const double* head_scale, const double* head_shift,
+                                                  const void* target, const void* precis,
+                                                  const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                                  void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the same entries for WIDER systems: nd = nx + na + nu <= 16 (1 <= nu <= 4) ---------------------------------------------
  * Signatures, operands, tape (mm_pathwise_tape_bytes_nd: it has no bound on nd), results and error codes of the _nd entries; one
@@ -506,6 +526,12 @@ int mm_pathwise_policy_rollout_backward_wide(int S, int dtype, int H, double dt,
                                              const void* target, const void* precis,
                                              const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy, void* g_x0,
                                              void* scratch, size_t scratch_bytes, void* stream);
+int mm_pathwise_policy_rollout_backward_wide_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                    int nu, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                    const double* head_scale, const double* head_shift,
+                                                    const void* target, const void* precis,
+                                                    const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                                    void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- path GENERATION: the two reformatting steps of a draw (csrc/mm_pathwise_sample.hip) -----------------------------------
  * PathwisePILCO draws new paths on every optimiser step (loops/pilco.py:281-284).  Between the random draws, two GEMMs and two

@@ -21,7 +21,11 @@ M = 2000, K = 1024 bases, policy M = 30, S = 8192 paths, H = 30), f32 and f64 pa
 ``--rows one_action,two_actions`` picks rows (the first two exist in earlier checkouts: run from the root of one for its numbers).
 The variants of one shape are timed in alternation (window r of every variant before window r + 1 of any).  ``--samples`` /
 ``--drift-M`` shrink the shape for a dry run; ``--native-only`` leaves the torch composition out (the run to put under
-``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv).
+``rocprofv3 --kernel-trace --stats``: profiles/pathwise_multiaction_kernel_stats.csv).  ``--objective custom``: the same rows with a
+caller-defined objective -- the time-weighted quadratic (1 + 0.1 t / dt) (e - tau)^T W (e - tau) on tensors -- instead of the
+GaussianObjective: "native" is then ``native_objective=True`` (the native rollout with its states as a differentiable output, the
+objective in torch on them, the seeded reverse sweep), "torch" the torch composition with the same objective on the same paths;
+``--dtypes f64`` picks the paths' element types.
 
 ``--grad``: the moment-matched policy LOSS + GRADIENT (loops.policy_loss_closure; every policy parameter trainable), f64, H = 30, ms
 per step, for system A at B = 1, 64 and 256:
@@ -193,7 +197,19 @@ def main_grad(args):
   print(json.dumps(res))
 
 
-def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True, native_inputs=8):
+class TimeWeightedQuadratic:
+  """(1 + 0.1 t / dt) (e - tau)^T W (e - tau) of a tensor of encoded states."""
+
+  def __init__(self, W, tau, dt):
+    self.W, self.tau, self.dt = W, tau, dt
+
+  def __call__(self, x, t=None):
+    e = x - self.tau
+    return (1.0 + 0.1 * t / self.dt) * (e * (e @ self.W)).sum(-1)
+
+
+def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repeats, with_torch=True, native_inputs=8,
+                   custom=False):
   from gpflowpilco_amd.loops import pathwise_policy_loss_closure
   from gpflowpilco_amd.pathwise import PathwiseSVGP
   na = len(active); ne = nx + na; nd = ne + nu
@@ -211,6 +227,11 @@ def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repe
                                     encoder=TrigonometricEncoder(active_dims=active), solver=dynamics.Euler())
   target = np.zeros(ne); target[na:2 * na] = 1.0
   objective = GaussianObjective(target=to_dev(target, device, dtype), precis=to_dev(np.eye(ne), device, dtype))
+  extra = {}
+  if custom:
+    A = np.random.default_rng(seed + 3).standard_normal((ne, ne))
+    objective = TimeWeightedQuadratic(to_dev(A @ A.T / ne + 0.5 * np.eye(ne), device, dtype), to_dev(target, device, dtype), 0.1)
+    extra = {"native_objective": True}
   g = torch.Generator(device=device).manual_seed(seed + 2)
   x0 = 0.2 + 0.6 * torch.rand(S, nx, dtype=dtype, device=device, generator=g)
   paths = drift.generate_paths(S, K, dtype=dtype, device=device, generator=g)
@@ -219,7 +240,8 @@ def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repe
   for t in params:
     t.requires_grad_(True)
   wide = {"native_inputs": native_inputs} if native_inputs > 8 else {}
-  native = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=True, native_actions=nu, **wide)
+  native = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=True, native_actions=nu, **wide,
+                                        **extra)
   composed = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.1, paths=paths, native=False)
 
   def forward(closure):
@@ -245,6 +267,7 @@ def pathwise_shape(nx, active, nu, Md, K, S, H, dtype, seed, device, inner, repe
   res = alternating(fns, H, inner, repeats, 1)
   res["mean_loss"] = losses
   res["shape"] = {"nx": nx, "na": na, "nu": nu, "nd": nd, "drift_M": Md, "K": K, "policy_M": 30, "S": S, "H": H}
+  res["objective"] = "custom" if custom else "gaussian"
   for k in kinds:
     res[f"{k}_loss_and_grad_over_forward"] = res[f"{k}_loss_and_grad"]["median"] / res[f"{k}_forward"]["median"]
   if "torch" in kinds:
@@ -257,12 +280,15 @@ def main_pathwise(args):
   device = "cuda"
   res = {"tool": "bench_multiaction --pathwise", "label": args.label, "unit": "ms per step, eager"}
   rows = {"two_actions": (4, (0, 1), 2, 40, 8), "one_action": (4, (1,), 1, 3, 8), "cart_double_pendulum": (6, (2, 4), 1, 70, 16)}
+  res["objective"] = args.objective
   for nm, dtype in (("f32", torch.float32), ("f64", F64)):
+    if nm not in args.dtypes.split(","):
+      continue
     res[nm] = {}
     for row in args.rows.split(","):
       nx, active, nu, seed, native_inputs = rows[row]
       res[nm][row] = pathwise_shape(nx, active, nu, args.drift_M, 1024, args.samples, args.steps, dtype, seed, device, args.inner,
-                                    args.repeats, not args.native_only, native_inputs)
+                                    args.repeats, not args.native_only, native_inputs, args.objective == "custom")
       torch.cuda.empty_cache()
   print(json.dumps(res))
 
@@ -277,6 +303,9 @@ def main():
   ap.add_argument("--pathwise", action="store_true")
   ap.add_argument("--native-only", action="store_true", help="--pathwise without the torch composition (for a kernel trace)")
   ap.add_argument("--rows", default="two_actions,one_action,cart_double_pendulum", help="--pathwise: which shapes")
+  ap.add_argument("--objective", choices=("gaussian", "custom"), default="gaussian",
+                  help="--pathwise: the GaussianObjective, or a quadratic objective through native_objective=True")
+  ap.add_argument("--dtypes", default="f32,f64", help="--pathwise: the paths' element types")
   ap.add_argument("--samples", type=int, default=8192)
   ap.add_argument("--drift-M", type=int, default=2000)
   ap.add_argument("--grad", action="store_true", help="moment-matched loss + gradient, native vs torch composition (see the docstring)")
