@@ -131,6 +131,31 @@ SIGNATURES = {
                                                          C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                          C.c_void_p, C.c_void_p]),
+    "mm_compose_nd_mixed_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "mm_rollout_composed_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                               C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm_compose_tape_bytes_nd_mixed": (C.c_size_t, [C.c_int] * 8),
+    "mm_rollout_composed_taped_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                     C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm_compose_backward_workspace_bytes_nd_mixed": (C.c_size_t, [C.c_int] * 7),
+    "mm_rollout_composed_backward_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                        C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm_bwd_f32_supported": (C.c_int, [C.c_int]),
     "mm_backward_pair_aggregates_bytes": (C.c_size_t, [C.c_int] * 5),
     "mm_backward_pair_aggregates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

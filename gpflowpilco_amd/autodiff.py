@@ -493,7 +493,7 @@ class ComposedRolloutNDFunction(torch.autograd.Function):
 
 class ComposedTrajectoryFunction(torch.autograd.Function):
   """The moment-matched policy rollout with its TRAJECTORY as a differentiable output, for one action and for several: the taped
-  forward of ``ComposedRolloutFunction`` / ``ComposedRolloutNDFunction`` (by ``roll.nu``), and the same reverse sweep seeded per step
+  forward of ``ComposedRolloutFunction`` / ``ComposedRolloutNDFunction`` (by ``roll.uses_nd``), and the same reverse sweep seeded per step
   with d loss / d (m_t, S_t) (``mm_rollout_composed_backward_seeded`` / ``_nd_seeded``).  Any torch objective of the states then
   sits on the native policy -> drift -> Euler chain, and the gradient of its own parameters comes from that torch part.
 
@@ -506,7 +506,7 @@ class ComposedTrajectoryFunction(torch.autograd.Function):
     f64 = torch.float64
     det = lambda t: t.detach().to(f64)
     pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-    taped = roll.taped if roll.nu == 1 else roll.taped_nd
+    taped = roll.taped_nd if roll.uses_nd else roll.taped
     m_H, S_H, cost, tape = taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
     ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
     ctx.save_for_backward(ls)
@@ -520,7 +520,7 @@ class ComposedTrajectoryFunction(torch.autograd.Function):
     (ls,) = ctx.saved_tensors
     g_xS = 0.5 * (g_xS + g_xS.transpose(-1, -2))
     seeds = (g_xm.transpose(0, 1).contiguous(), g_xS.transpose(0, 1).contiguous())
-    sweep = ctx.roll.backward if ctx.roll.nu == 1 else ctx.roll.backward_nd
+    sweep = ctx.roll.backward_nd if ctx.roll.uses_nd else ctx.roll.backward
     g_pol, g_m, g_S = sweep(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
                             want_state_grad=ctx.need_state, g_traj=seeds)
     nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d

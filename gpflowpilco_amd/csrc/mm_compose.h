@@ -125,15 +125,17 @@ struct MMTapeLayout {
 // element).  Larger models re-run the q stage from the taped (md, Sdd).
 #define MM_TAPE_WS_LIMIT ((size_t)512 << 20)
 
-// slot_bytes: one compose-workspace slot; nd: the drift's input dimension (ne + number of actions)
-static inline MMTapeLayout mm_tape_layout_slots(int B, int H, int nx, int nd, size_t slot_bytes, int drift_M, int dtype) {
+// slot_bytes: one compose-workspace slot; nd: the drift's input dimension (ne + number of actions); drift_L: the drift's number of
+// latents (= nx unless its outputs are mixed, mm_tape_layout_nd_mixed), which sizes the kept workspace and the kept sums
+static inline MMTapeLayout mm_tape_layout_slots_l(int B, int H, int nx, int drift_L, int nd, size_t slot_bytes, int drift_M,
+                                                  int dtype) {
   MMTapeLayout o;
   const size_t es = mm_elem_size(dtype), A = 256;
   o.slot_bytes = slot_bytes;
   size_t off = (size_t)(H + 1) * o.slot_bytes;
   o.xm = off; off = mm_align_up(off + (size_t)(H + 1) * B * nx * es, A);
   o.xS = off; off = mm_align_up(off + (size_t)(H + 1) * B * nx * nx * es, A);
-  const size_t wsb = mm_align_up(mm_workspace_layout(B, nx, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY).total, A);
+  const size_t wsb = mm_align_up(mm_workspace_layout(B, drift_L, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY).total, A);
   o.ws = off; o.ws_stride = 0;
   if (wsb * (size_t)H <= MM_TAPE_WS_LIMIT) { o.ws_stride = wsb; off += wsb * (size_t)H; }
   // ... and, where they fit too, the sums of the drift match's backward sweeps: nothing in them depends on the incoming
@@ -141,12 +143,16 @@ static inline MMTapeLayout mm_tape_layout_slots(int B, int H, int nx, int nd, si
   // (mm_moment_match_with_sums) and the reverse step is the chain rule alone -- two launches less per step and direction
   o.gp = off; o.gp_stride = 0;
   if (o.ws_stride) {
-    const size_t gpb = mm_align_up(mm_moment_match_backward_bytes_dtype(B, nx, drift_M, nd, dtype,
+    const size_t gpb = mm_align_up(mm_moment_match_backward_bytes_dtype(B, drift_L, drift_M, nd, dtype,
                                                                         MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY), A);
     if (gpb && (wsb + gpb) * (size_t)H <= MM_TAPE_WS_LIMIT) { o.gp_stride = gpb; off += gpb * (size_t)H; }
   }
   o.total = off;
   return o;
+}
+
+static inline MMTapeLayout mm_tape_layout_slots(int B, int H, int nx, int nd, size_t slot_bytes, int drift_M, int dtype) {
+  return mm_tape_layout_slots_l(B, H, nx, nx, nd, slot_bytes, drift_M, dtype);
 }
 
 static inline MMTapeLayout mm_tape_layout(int B, int H, int nx, int na, int drift_M, int dtype) {
@@ -156,6 +162,38 @@ static inline MMTapeLayout mm_tape_layout(int B, int H, int nx, int na, int drif
 // several actions (mm_compose_nd.hip, mm_compose_bwd_nd.hip): slots of mm_compose_layout_nd, the drift on nd = ne + nu dims
 static inline MMTapeLayout mm_tape_layout_nd(int B, int H, int nx, int na, int nu, int drift_M, int dtype) {
   return mm_tape_layout_slots(B, H, nx, nx + na + nu, mm_compose_layout_nd(B, nx, na, nu, dtype).total, drift_M, dtype);
+}
+
+// ---- a coregionalised drift (mm_mix.h): Lg latents mixed to nx outputs by W [nx][Lg] -------------------------------------------
+// The drift's match writes its latent moments g1 [B][Lg], Sgg [B][Lg][Lg], cross_g [B][nd][Lg] to a staging block, and the mixing
+// launch writes the slot's df1 / dSff / dcross from it.  (The packed [B][Lg] blocks of different batch elements overlap the
+// [B][nx] ones, so one workgroup per batch element cannot mix in place.)  The staging block follows the nd layout: at the end of
+// the compose workspace, and ONCE at the end of the tape -- the map is linear, the reverse sweep never reads the latent moments.
+struct MMMixStage { size_t g1, Sgg, cg, total; };        // offsets inside the staging block
+static inline MMMixStage mm_mix_stage(int B, int Lg, int nd, size_t es) {
+  MMMixStage o;
+  const size_t A = 256;
+  size_t off = 0;
+  o.g1 = off;  off = mm_align_up(off + (size_t)B * Lg * es, A);
+  o.Sgg = off; off = mm_align_up(off + (size_t)B * Lg * Lg * es, A);
+  o.cg = off;  off = mm_align_up(off + (size_t)B * nd * Lg * es, A);
+  o.total = off;
+  return o;
+}
+// the tape of mm_rollout_composed_taped_nd_mixed: mm_tape_layout_nd with the kept workspace / sums sized by Lg; the staging block
+// starts at .total (mm_compose_tape_bytes_nd_mixed adds it)
+static inline MMTapeLayout mm_tape_layout_nd_mixed(int B, int H, int nx, int na, int nu, int Lg, int drift_M, int dtype) {
+  return mm_tape_layout_slots_l(B, H, nx, Lg, nx + na + nu, mm_compose_layout_nd(B, nx, na, nu, dtype).total, drift_M, dtype);
+}
+
+// Where the tape does not keep the sums of the drift's backward sweeps per step, the mixed taped forward still reads the drift's value
+// off those sums (mm_moment_match_with_sums, into ONE scratch buffer behind the staging block) instead of running the forward's own
+// reduces: the two routines sum in different orders, and on an ill-conditioned drift (|beta| ~ 1e2 .. 1e3) their Sff differ by
+// ~1e-10 of its scale.  So the value of a taped rollout, and with it the gradient, does not depend on the regime the tape's size
+// puts it in: element b of a large batch reproduces the same element of a small one.  0: the sums are kept per step, no scratch.
+static inline size_t mm_tape_nd_mixed_scratch(const MMTapeLayout& tl, int B, int Lg, int drift_M, int nd, int dtype) {
+  if (tl.gp_stride) return 0;
+  return mm_align_up(mm_moment_match_backward_bytes_dtype(B, Lg, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY), 256);
 }
 
 // mm_compose_bwd.hip: the adjoint of one GP moment match (general in d), shared by the two reverse sweeps.

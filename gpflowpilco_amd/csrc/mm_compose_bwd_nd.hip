@@ -9,6 +9,8 @@
 //                            match with L = nu latents w.r.t. its input moments AND every latent's packed parameters
 //                            (mma_policy_nd_bwd: nu latent items + nu (nu - 1) / 2 pair items)
 // and k_compose_encode_bwd0 (mm_compose_bwd.hip) at x_0.  All adjoints are f64; f64 packs only.
+// mm_rollout_composed_backward_nd_mixed (a coregionalised drift, mm_mix.h): k_compose_mix_bwd_nd, the adjoint of the output mixing,
+// runs between k_compose_tail_bwd_nd and the drift's adjoint, which then has L = Lg latents and Lg + Lg (Lg + 1) / 2 items.
 //
 // Work split: ONE 256-thread workgroup per batch element runs the nu + nu (nu - 1) / 2 policy items in turn and adds them in that
 // fixed order -- no floating-point atomics, two sweeps over one tape are bit-equal.
@@ -23,6 +25,7 @@
 #include "mm_common.h"
 #include "mm_compose.h"
 #include "mm_adjoint_nd.h"
+#include "mm_mix.h"
 
 #define MMB_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 #define MMB_ND_LDS_MAX ((size_t)160 * 1024)
@@ -177,6 +180,30 @@ static inline MMComposeBwdLayoutND mm_compose_bwd_layout_nd(int B, int nx, int n
   return o;
 }
 
+// a coregionalised drift (mm_mix.h, the _mixed entries): the adjoints of the latent moments (mm_mix_stage, f64) sit between the carry
+// and the drift match's backward buffer, which is sized by the Lg latents
+struct MMComposeBwdLayoutNDMixed { size_t carry, stage, gp, gp_bytes, total; };
+static inline MMComposeBwdLayoutNDMixed mm_compose_bwd_layout_nd_mixed(int B, int nx, int na, int nu, int Lg, int Md) {
+  MMComposeBwdLayoutNDMixed o;
+  o.carry = 0;
+  o.stage = mm_align_up(mm_carry_layout_nd(B, nx, na, nu).total, 256);
+  o.gp = o.stage + mm_mix_stage(B, Lg, nx + na + nu, 8).total;
+  o.gp_bytes = mm_moment_match_backward_bytes_dtype(B, Lg, Md, nx + na + nu, MM_F64, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY);
+  o.total = o.gp + o.gp_bytes;
+  return o;
+}
+
+// the adjoint of the mixing, between k_compose_tail_bwd_nd and the drift match's adjoint: grid B, 64 threads
+__global__ __launch_bounds__(64) void k_compose_mix_bwd_nd(int nx, int Lg, int nd, const double* __restrict__ W,
+                                                           const double* __restrict__ cdf1, const double* __restrict__ cdSff,
+                                                           const double* __restrict__ cdcross, double* __restrict__ cg1,
+                                                           double* __restrict__ cSgg, double* __restrict__ ccg) {
+  __shared__ double sm[MMC_NX * MMC_NX];
+  const size_t b = blockIdx.x;
+  mma_mix_bwd(MMADevCtx(), nx, Lg, nd, W, cdf1 + b * nx, cdSff + b * nx * nx, cdcross + b * nd * nx, cg1 + b * Lg,
+              cSgg + b * Lg * Lg, ccg + b * nd * Lg, sm);
+}
+
 extern "C" size_t mm_compose_backward_workspace_bytes_nd(int B, int nx, int na, int nu, int drift_M, int policy_M) {
   if (B <= 0 || drift_M <= 0 || !mm_compose_bwd_nd_takes(nx, na, nu, policy_M)) return 0;
   return mm_compose_bwd_layout_nd(B, nx, na, nu, drift_M).total;
@@ -193,6 +220,7 @@ extern "C" size_t mm_policy_grad_bytes_nd(int B, int nu, int policy_M, int polic
 //            PACKED policy -- Z [M][d], beta [M], ls2 = lengthscales^2 [d], variance, mean_c
 //   g_mx0 [B][nx], g_Sxx0 [B][nx][nx] (out, optional): gradient w.r.t. the initial state (symmetric)
 // g_xm [H][B][nx], g_xS [H][B][nx][nx] (both or neither): the caller's seeds on the trajectory, as in mm_compose_bwd.hip
+// mixed (the _mixed entry): the drift has drift_L <= nx latents mixed by mix_W; else drift_L == nx and mix_W is not read
 static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
                                                 const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
                                                 int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
@@ -201,8 +229,10 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
                                                 const void* g_cost, const void* g_xm, const void* g_xS,
                                                 void* g_policy, void* g_mx0, void* g_Sxx0,
                                                 void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
-                                                int32_t* status, void* stream) {
+                                                int32_t* status, void* stream, bool mixed = false,
+                                                const double* mix_W = nullptr) {
   if ((g_xm == nullptr) != (g_xS == nullptr)) return MM_E_ARG;
+  if (mixed && !mix_W) return MM_E_ARG;
   if (!drift_packed || !policy_packed || !tape || !g_cost || !g_policy || !ws_drift || !ws_bwd || !target || !precis) return MM_E_ARG;
   if (!head_scale || !head_shift) return MM_E_ARG;
   if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
@@ -212,17 +242,27 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
   int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
   if (rc) return rc;
   const int ne = D.ne, nd = D.nd;
-  if (drift_L != nx || drift_d != nd || policy_d != ne) return MM_E_STATE;
+  if (mixed && (drift_L < 1 || drift_L > nx)) return MM_E_DIM;
+  if ((!mixed && drift_L != nx) || drift_d != nd || policy_d != ne) return MM_E_STATE;
   if (!mm_compose_bwd_nd_takes(nx, na, nu, policy_M)) return MM_E_DIM;
-  const MMTapeLayout tl = mm_tape_layout_nd(B, H, nx, na, nu, drift_M, dtype);
-  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  const int Lg = drift_L;
+  const MMMixStage ms = mm_mix_stage(B, Lg, nd, 8);
+  const MMTapeLayout tl = mixed ? mm_tape_layout_nd_mixed(B, H, nx, na, nu, Lg, drift_M, dtype)
+                                : mm_tape_layout_nd(B, H, nx, na, nu, drift_M, dtype);
+  if (tape_bytes < tl.total + (mixed ? ms.total + mm_tape_nd_mixed_scratch(tl, B, Lg, drift_M, nd, dtype) : 0)) return MM_E_WORKSPACE;
   const MMCarryLayoutND kl = mm_carry_layout_nd(B, nx, na, nu);
-  const MMComposeBwdLayoutND bl = mm_compose_bwd_layout_nd(B, nx, na, nu, drift_M);
+  MMComposeBwdLayoutND bl = mm_compose_bwd_layout_nd(B, nx, na, nu, drift_M);
+  size_t stage_off = 0;
+  if (mixed) {
+    const MMComposeBwdLayoutNDMixed blm = mm_compose_bwd_layout_nd_mixed(B, nx, na, nu, Lg, drift_M);
+    bl.carry = blm.carry; bl.gp = blm.gp; bl.gp_bytes = blm.gp_bytes; bl.total = blm.total;
+    stage_off = blm.stage;
+  }
   if (ws_bwd_bytes < bl.total) return MM_E_WORKSPACE;
-  if (ws_drift_bytes < mm_workspace_bytes(B, nx, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)) return MM_E_WORKSPACE;
+  if (ws_drift_bytes < mm_workspace_bytes(B, Lg, drift_M, nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, dtype, 1);
   if (policy_bytes < pl.Cm) return MM_E_WORKSPACE;
-  if (drift_bytes < mm_packed_model_bytes(nx, drift_M, nd, dtype, 1)) return MM_E_WORKSPACE;
+  if (drift_bytes < mm_packed_model_bytes(Lg, drift_M, nd, dtype, 1)) return MM_E_WORKSPACE;
   MMHeadND hd = {};
   for (int j = 0; j < nu; ++j) { hd.scale[j] = head_scale[j]; hd.shift[j] = head_shift[j]; }
   const MMComposeLayout cl = mm_compose_layout_nd(B, nx, na, nu, dtype);
@@ -240,7 +280,12 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
   hipLaunchKernelGGL(k_zero_f64, dim3((unsigned)((npar + 255) / 256)), dim3(256), 0, s, (double*)g_policy, npar);
   MMB_CHECK();
   const int dflags = MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY;
-  const size_t items_off = mm_gp_bwd_items_offset(B, nx, drift_M, nd, MM_F64, dflags);
+  const size_t items_off = mm_gp_bwd_items_offset(B, Lg, drift_M, nd, MM_F64, dflags);
+  // the adjoints the drift match's backward reads: the carry's own, or (mixed) those of the latent moments
+  char* sg = (char*)ws_bwd + stage_off;
+  const double* gdf1 = mixed ? (const double*)(sg + ms.g1) : cr(kl.cdf1);
+  const double* gdSff = mixed ? (const double*)(sg + ms.Sgg) : cr(kl.cdSff);
+  const double* gdcross = mixed ? (const double*)(sg + ms.cg) : cr(kl.cdcross);
   for (int h = H - 1; h >= 0; --h) {
     const char* sl = tp + (size_t)h * tl.slot_bytes; const char* sn = tp + (size_t)(h + 1) * tl.slot_bytes;
     hipLaunchKernelGGL(k_compose_tail_bwd_nd, dim3(B), dim3(64), lds_tail, s, D, dt, h == H - 1 ? 1 : 0,
@@ -252,13 +297,19 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
                        g_xm ? (const double*)g_xm + (size_t)h * B * nx : (const double*)nullptr,
                        g_xS ? (const double*)g_xS + (size_t)h * B * nx * nx : (const double*)nullptr);
     MMB_CHECK();
+    if (mixed) {
+      hipLaunchKernelGGL(k_compose_mix_bwd_nd, dim3(B), dim3(64), 0, s, nx, Lg, nd, mix_W, (const double*)cr(kl.cdf1),
+                         (const double*)cr(kl.cdSff), (const double*)cr(kl.cdcross), (double*)(sg + ms.g1), (double*)(sg + ms.Sgg),
+                         (double*)(sg + ms.cg));
+      MMB_CHECK();
+    }
     // the drift's match (its items are summed by the next kernel), as the one-action sweep runs it
     const bool kept = tl.ws_stride != 0;                   // the tape holds this step's q-stage workspace
     const bool sums = tl.gp_stride != 0;                   // ... and the sums of its backward sweeps: chain rule alone
     void* wsd = kept ? (void*)(const_cast<char*>(tp) + tl.ws + (size_t)h * tl.ws_stride) : ws_drift;
     char* gslot = sums ? const_cast<char*>(tp) + tl.gp + (size_t)h * tl.gp_stride : gw;
-    rc = mm_moment_match_backward_impl(drift_packed, drift_bytes, nx, drift_M, nd, dtype, B, sl + cl.md, sl + cl.Sdd, dflags,
-                                       cr(kl.cdf1), cr(kl.cdSff), cr(kl.cdcross), cr(kl.cmd), cr(kl.cSdd), 1, wsd,
+    rc = mm_moment_match_backward_impl(drift_packed, drift_bytes, Lg, drift_M, nd, dtype, B, sl + cl.md, sl + cl.Sdd, dflags,
+                                       gdf1, gdSff, gdcross, cr(kl.cmd), cr(kl.cSdd), 1, wsd,
                                        kept ? tl.ws_stride : ws_drift_bytes, gslot, sums ? tl.gp_stride : bl.gp_bytes, status, stream,
                                        kept, true, sums ? MMB_MODE_CHAIN : MMB_MODE_ALL, false /* the tape is this rollout's own */);
     if (rc) return rc;
@@ -267,7 +318,7 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
                        (const double*)(sl + cl.me), (const double*)(sl + cl.See), (const double*)(sl + cl.pf1),
                        (const double*)(sl + cl.pSff), (const double*)(sl + cl.pcross), (const double*)cr(kl.cSdd),
                        (const double*)cr(kl.ccp), cr(kl.cme), cr(kl.cSee), (double*)g_policy, status,
-                       (const double*)(gslot + items_off), nx + nx * (nx + 1) / 2);
+                       (const double*)(gslot + items_off), Lg + Lg * (Lg + 1) / 2);
     MMB_CHECK();
   }
   if (g_mx0) {
@@ -308,4 +359,30 @@ extern "C" int mm_rollout_composed_backward_nd_seeded(const void* drift_packed, 
                                               policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
                                               target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
                                               ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream);
+}
+
+// ---- a coregionalised drift: the sweep over the tape of mm_rollout_composed_taped_nd_mixed (mm_compose_nd.hip) -----------------
+// 0: the shapes mm_compose_backward_workspace_bytes_nd refuses, or drift_L outside 1 .. nx
+extern "C" size_t mm_compose_backward_workspace_bytes_nd_mixed(int B, int nx, int na, int nu, int drift_L, int drift_M,
+                                                               int policy_M) {
+  if (B <= 0 || drift_M <= 0 || !mm_compose_bwd_nd_takes(nx, na, nu, policy_M) || drift_L < 1 || drift_L > nx) return 0;
+  return mm_compose_bwd_layout_nd_mixed(B, nx, na, nu, drift_L, drift_M).total;
+}
+
+// mm_rollout_composed_backward_nd_seeded with the adjoint of the mixing in front of the drift's adjoint (g_xm / g_xS NULL: the plain
+// sweep).  mix_W [nx][drift_L] as the forward's; no gradient w.r.t. W, c or the drift.
+extern "C" int mm_rollout_composed_backward_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                     int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                     int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                     const int32_t* active_dims, int nu, const double* head_scale,
+                                                     const double* head_shift, const void* target, const void* precis,
+                                                     const void* tape, size_t tape_bytes, const void* g_cost,
+                                                     const void* g_xm, const void* g_xS,
+                                                     void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                     void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                     int32_t* status, void* stream, const double* mix_W) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, true, mix_W);
 }

@@ -17,12 +17,16 @@
 // mm_tape_layout_slots (mm_compose.h), as for one action -- the drift match runs in the tape's own workspace of the step where H of
 // them fit, and leaves the sums of its backward sweeps there too (mm_moment_match_with_sums_impl) where those fit as well.
 // The policy match's workspace is not kept: the reverse sweep recomputes the policy from (me, See).
+// The _mixed entries at the end of the file run the same rollout for a COREGIONALISED drift (Lg <= nx latents, f = W g + c): the
+// drift's match with L = Lg writes to a staging block and k_compose_mix_nd (mm_mix.h), one more launch per step, fills the slot's
+// df1 / dSff / dcross; everything else is shared, and without mixing operands nothing differs from before.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "mm_common.h"
 #include "mm_cost.h"
 #include "mm_compose.h"
 #include "mm_compose_dev.h"
+#include "mm_mix.h"
 
 #define MMC_BVN_PANELS 4
 
@@ -203,6 +207,19 @@ __global__ __launch_bounds__(64) void k_compose_tail_nd(MMComposeDims D, double 
   }
 }
 
+// the mixing of a coregionalised drift (mm_mix.h): staged latent moments of the drift's match -> the slot's df1 / dSff / dcross, which
+// the tail then reads as those of an ordinary drift with nx outputs.  One workgroup per batch element, a launch of its own.
+template <typename T>
+__global__ __launch_bounds__(64) void k_compose_mix_nd(int nx, int Lg, int nd, const double* __restrict__ W,
+                                                       const double* __restrict__ mc, const T* __restrict__ g1,
+                                                       const T* __restrict__ Sgg, const T* __restrict__ cg, T* __restrict__ df1,
+                                                       T* __restrict__ dSff, T* __restrict__ dcross) {
+  __shared__ double sm[MMC_NX * MMC_NX];
+  const size_t b = blockIdx.x;
+  mma_mix_fwd<MMADevCtx, T>(MMADevCtx(), nx, Lg, nd, W, mc, g1 + b * Lg, Sgg + b * Lg * Lg, cg + b * nd * Lg, df1 + b * nx,
+                            dSff + b * nx * nx, dcross + b * nd * nx, sm);
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -214,14 +231,18 @@ extern "C" size_t mm_compose_nd_workspace_bytes(int B, int nx, int na, int nu, i
 }
 
 // tape == nullptr: every step reuses the one compose workspace `w`; else step h works in tape slot h (see the header comment)
+// mixW != nullptr (the _mixed entries): the drift has Lg <= nx latents; its match writes to the staging block `stage`
+// (mm_mix_stage) and k_compose_mix_nd fills df1 / dSff / dcross.  mixW == nullptr: Lg == nx, no staging, as ever.
 template <typename T>
 static int mm_rollout_composed_nd_t(const void* drift, size_t drift_bytes, int Md, const void* policy, size_t policy_bytes,
                                     int Mpol, int dtype, int B, int H, double dt, const MMComposeDims& D, const MMHeadND& hd,
                                     const T* target, const T* precis, T* mx, T* Sxx, T* cost, T* traj_mu, T* traj_S,
                                     void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
                                     char* w, const MMComposeLayout& cl, char* tape, const MMTapeLayout& tl, int32_t* status,
-                                    hipStream_t s) {
+                                    hipStream_t s, int Lg, const double* mixW = nullptr, const double* mixc = nullptr,
+                                    char* stage = nullptr, char* gp_scratch = nullptr, size_t gp_scratch_bytes = 0) {
   const int nx = D.nx, ne = D.ne, nd = D.nd, nu = nd - ne;
+  const MMMixStage ms = mm_mix_stage(B, Lg, nd, sizeof(T));
   auto slot = [&](int h) { return tape ? tape + (size_t)h * tl.slot_bytes : w; };
   T* xm = tape ? (T*)(tape + tl.xm) : nullptr;
   T* xS = tape ? (T*)(tape + tl.xS) : nullptr;
@@ -243,6 +264,8 @@ static int mm_rollout_composed_nd_t(const void* drift, size_t drift_bytes, int M
     T *me = (T*)(c + cl.me), *See = (T*)(c + cl.See), *pf1 = (T*)(c + cl.pf1), *pSff = (T*)(c + cl.pSff);
     T *pcross = (T*)(c + cl.pcross), *md = (T*)(c + cl.md), *Sdd = (T*)(c + cl.Sdd), *df1 = (T*)(c + cl.df1);
     T *dSff = (T*)(c + cl.dSff), *dcross = (T*)(c + cl.dcross);
+    // where the drift's match writes: the slot itself, or the staging block of the mixing
+    T *mf1 = mixW ? (T*)(stage + ms.g1) : df1, *mSff = mixW ? (T*)(stage + ms.Sgg) : dSff, *mcross = mixW ? (T*)(stage + ms.cg) : dcross;
     double *Sxe = (double*)(c + cl.Sxe), *cpol = (double*)(c + cl.cpol);
     // policy: mean-only regressor (models.py:34-41: model_uncertainty = False), nu latents, full covariance between them
     int rc = mm_moment_match(policy, policy_bytes, nu, Mpol, ne, dtype, B, me, See, MM_FULL_OUTPUT_COV, 0.0, pf1, pSff, pcross,
@@ -255,13 +278,22 @@ static int mm_rollout_composed_nd_t(const void* drift, size_t drift_bytes, int M
     void* wsd = (tape && tl.ws_stride) ? (void*)(tape + tl.ws + (size_t)h * tl.ws_stride) : ws_drift;
     const size_t wsd_bytes = (tape && tl.ws_stride) ? tl.ws_stride : ws_drift_bytes;
     if (tape && tl.gp_stride)     // the sums of the backward's sweeps stay on the tape and give this step's value too (mm_compose.h)
-      rc = mm_moment_match_with_sums_impl(drift, drift_bytes, nx, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY,
-                                          0.0, df1, dSff, dcross, wsd, wsd_bytes, tape + tl.gp + (size_t)h * tl.gp_stride,
+      rc = mm_moment_match_with_sums_impl(drift, drift_bytes, Lg, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY,
+                                          0.0, mf1, mSff, mcross, wsd, wsd_bytes, tape + tl.gp + (size_t)h * tl.gp_stride,
                                           tl.gp_stride, status, (void*)s, false);
+    else if (tape && gp_scratch)  // (mixed: the same routine on one scratch buffer, so that the value is that of the kept regime)
+      rc = mm_moment_match_with_sums_impl(drift, drift_bytes, Lg, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY,
+                                          0.0, mf1, mSff, mcross, wsd, wsd_bytes, gp_scratch, gp_scratch_bytes, status, (void*)s,
+                                          false);
     else
-      rc = mm_moment_match(drift, drift_bytes, nx, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY, 0.0,
-                           df1, dSff, dcross, wsd, wsd_bytes, status, (void*)s);
+      rc = mm_moment_match(drift, drift_bytes, Lg, Md, nd, dtype, B, md, Sdd, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY, 0.0,
+                           mf1, mSff, mcross, wsd, wsd_bytes, status, (void*)s);
     if (rc) return rc;
+    if (mixW) {
+      hipLaunchKernelGGL((k_compose_mix_nd<T>), dim3(B), dim3(64), 0, s, nx, Lg, nd, mixW, mixc, (const T*)mf1, (const T*)mSff,
+                         (const T*)mcross, df1, dSff, dcross);
+      MMC_CHECK();
+    }
     T* tm = tape ? xm + (size_t)(h + 1) * B * nx : (traj_mu ? traj_mu + (size_t)h * B * nx : (T*)nullptr);
     T* tS = tape ? xS + (size_t)(h + 1) * B * nx * nx : (traj_S ? traj_S + (size_t)h * B * nx * nx : (T*)nullptr);
     hipLaunchKernelGGL((k_compose_tail_nd<T>), dim3(B), dim3(64), mm_cost_lds_bytes(ne), s, D, dt, (const double*)cpol,
@@ -304,11 +336,11 @@ extern "C" int mm_rollout_composed_nd(const void* drift_packed, size_t drift_byt
     return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
                                             dt, D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
                                             (double*)cost, (double*)traj_mu, (double*)traj_Sigma, ws_drift, ws_drift_bytes,
-                                            ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s);
+                                            ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s, nx);
   return mm_rollout_composed_nd_t<float>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
                                          dt, D, hd, (const float*)target, (const float*)precis, (float*)mx, (float*)Sxx,
                                          (float*)cost, (float*)traj_mu, (float*)traj_Sigma, ws_drift, ws_drift_bytes,
-                                         ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s);
+                                         ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s, nx);
 }
 
 // ---- the same rollout, recorded (f64 only, as the reverse sweep) -------------------------------------------------------------
@@ -348,5 +380,108 @@ extern "C" int mm_rollout_composed_taped_nd(const void* drift_packed, size_t dri
   return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H, dt,
                                           D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
                                           (double*)cost, nullptr, nullptr, ws_drift, ws_drift_bytes, ws_policy, ws_policy_bytes, nullptr, cl,
-                                          (char*)tape, tl, status, (hipStream_t)stream);
+                                          (char*)tape, tl, status, (hipStream_t)stream, nx);
+}
+
+// ---- a coregionalised drift: Lg = drift_L <= nx latents, f = W g + c (mm_mix.h) ------------------------------------------------
+// mix_W [nx][drift_L] row-major, mix_c [nx] or NULL, both f64 on the device.  Everything else as the entries above with drift_L in
+// place of nx for the drift's own pack and workspace.
+static inline bool mm_mixed_dims_ok(int B, int nx, int na, int nu, int Lg) {
+  if (B <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU) return false;
+  if (2 * na + (nx - na) + nu > MMC_ND) return false;
+  return Lg >= 1 && Lg <= nx;
+}
+
+// the compose workspace of mm_rollout_composed_nd_mixed: that of mm_rollout_composed_nd, then the staging block.  0: out of range
+extern "C" size_t mm_compose_nd_mixed_workspace_bytes(int B, int nx, int na, int nu, int drift_L, int dtype) {
+  if (!mm_mixed_dims_ok(B, nx, na, nu, drift_L)) return 0;
+  if (dtype != MM_F32 && dtype != MM_F64) return 0;
+  return mm_compose_layout_nd(B, nx, na, nu, dtype).total + mm_mix_stage(B, drift_L, nx + na + nu, mm_elem_size(dtype)).total;
+}
+
+extern "C" int mm_rollout_composed_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                            int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                            int nu, const double* head_scale, const double* head_shift,
+                                            const void* target, const void* precis,
+                                            void* mx, void* Sxx, void* cost, void* traj_mu, void* traj_Sigma,
+                                            void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                                            void* ws_compose, size_t ws_compose_bytes, int32_t* status, void* stream,
+                                            const double* mix_W, const double* mix_c) {
+  if (!drift_packed || !policy_packed || !mx || !Sxx || !head_scale || !head_shift || !mix_W) return MM_E_ARG;
+  if (!ws_drift || !ws_policy || !ws_compose) return MM_E_ARG;
+  if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
+  if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
+  if (cost && (!target || !precis)) return MM_E_ARG;
+  MMComposeDims D;
+  int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
+  if (rc) return rc;
+  if (drift_L < 1 || drift_L > nx) return MM_E_DIM;
+  if (drift_d != D.nd || policy_d != D.ne) return MM_E_STATE;
+  const MMComposeLayout cl = mm_compose_layout_nd(B, nx, na, nu, dtype);
+  if (ws_compose_bytes < cl.total + mm_mix_stage(B, drift_L, D.nd, mm_elem_size(dtype)).total) return MM_E_WORKSPACE;
+  if (ws_policy_bytes < mm_workspace_bytes(B, nu, policy_M, D.ne, dtype, MM_FULL_OUTPUT_COV)) return MM_E_WORKSPACE;
+  if (ws_drift_bytes < mm_workspace_bytes(B, drift_L, drift_M, D.nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)) return MM_E_WORKSPACE;
+  if (policy_bytes < mm_packed_model_bytes(nu, policy_M, D.ne, dtype, 0)) return MM_E_WORKSPACE;
+  if (drift_bytes < mm_packed_model_bytes(drift_L, drift_M, D.nd, dtype, 1)) return MM_E_WORKSPACE;
+  MMHeadND hd = {};
+  for (int j = 0; j < nu; ++j) { hd.scale[j] = head_scale[j]; hd.shift[j] = head_shift[j]; }
+  hipStream_t s = (hipStream_t)stream;
+  char* stage = (char*)ws_compose + cl.total;
+  if (dtype == MM_F64)
+    return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
+                                            dt, D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
+                                            (double*)cost, (double*)traj_mu, (double*)traj_Sigma, ws_drift, ws_drift_bytes,
+                                            ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s,
+                                            drift_L, mix_W, mix_c, stage);
+  return mm_rollout_composed_nd_t<float>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H,
+                                         dt, D, hd, (const float*)target, (const float*)precis, (float*)mx, (float*)Sxx,
+                                         (float*)cost, (float*)traj_mu, (float*)traj_Sigma, ws_drift, ws_drift_bytes,
+                                         ws_policy, ws_policy_bytes, (char*)ws_compose, cl, nullptr, MMTapeLayout(), status, s,
+                                         drift_L, mix_W, mix_c, stage);
+}
+
+// 0: dims out of range (drift_L outside 1 .. nx included) or a dtype other than MM_F64
+extern "C" size_t mm_compose_tape_bytes_nd_mixed(int B, int H, int nx, int na, int nu, int drift_L, int drift_M, int dtype) {
+  if (H <= 0 || drift_M <= 0 || !mm_mixed_dims_ok(B, nx, na, nu, drift_L)) return 0;
+  if (dtype != MM_F64) return 0;
+  const MMTapeLayout tl = mm_tape_layout_nd_mixed(B, H, nx, na, nu, drift_L, drift_M, dtype);
+  return tl.total + mm_mix_stage(B, drift_L, nx + na + nu, mm_elem_size(dtype)).total
+         + mm_tape_nd_mixed_scratch(tl, B, drift_L, drift_M, nx + na + nu, dtype);
+}
+
+extern "C" int mm_rollout_composed_taped_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                  int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                  int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                  const int32_t* active_dims, int nu, const double* head_scale,
+                                                  const double* head_shift, const void* target, const void* precis, void* mx,
+                                                  void* Sxx, void* cost, void* ws_drift, size_t ws_drift_bytes, void* ws_policy,
+                                                  size_t ws_policy_bytes, void* tape, size_t tape_bytes, int32_t* status,
+                                                  void* stream, const double* mix_W, const double* mix_c) {
+  if (!drift_packed || !policy_packed || !mx || !Sxx || !head_scale || !head_shift || !mix_W) return MM_E_ARG;
+  if (!ws_drift || !ws_policy || !tape) return MM_E_ARG;
+  if (B <= 0 || H <= 0 || drift_M <= 0 || policy_M <= 0) return MM_E_ARG;
+  if (dtype != MM_F64) return MM_E_DTYPE;
+  if (cost && (!target || !precis)) return MM_E_ARG;
+  MMComposeDims D;
+  int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
+  if (rc) return rc;
+  if (drift_L < 1 || drift_L > nx) return MM_E_DIM;
+  if (drift_d != D.nd || policy_d != D.ne) return MM_E_STATE;
+  const MMTapeLayout tl = mm_tape_layout_nd_mixed(B, H, nx, na, nu, drift_L, drift_M, dtype);
+  const size_t stage_bytes = mm_mix_stage(B, drift_L, D.nd, mm_elem_size(dtype)).total;
+  const size_t scratch_bytes = mm_tape_nd_mixed_scratch(tl, B, drift_L, drift_M, D.nd, dtype);
+  if (tape_bytes < tl.total + stage_bytes + scratch_bytes) return MM_E_WORKSPACE;
+  if (ws_policy_bytes < mm_workspace_bytes(B, nu, policy_M, D.ne, dtype, MM_FULL_OUTPUT_COV)) return MM_E_WORKSPACE;
+  if (ws_drift_bytes < mm_workspace_bytes(B, drift_L, drift_M, D.nd, dtype, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)) return MM_E_WORKSPACE;
+  if (policy_bytes < mm_packed_model_bytes(nu, policy_M, D.ne, dtype, 0)) return MM_E_WORKSPACE;
+  if (drift_bytes < mm_packed_model_bytes(drift_L, drift_M, D.nd, dtype, 1)) return MM_E_WORKSPACE;
+  MMHeadND hd = {};
+  for (int j = 0; j < nu; ++j) { hd.scale[j] = head_scale[j]; hd.shift[j] = head_shift[j]; }
+  const MMComposeLayout cl = mm_compose_layout_nd(B, nx, na, nu, dtype);
+  return mm_rollout_composed_nd_t<double>(drift_packed, drift_bytes, drift_M, policy_packed, policy_bytes, policy_M, dtype, B, H, dt,
+                                          D, hd, (const double*)target, (const double*)precis, (double*)mx, (double*)Sxx,
+                                          (double*)cost, nullptr, nullptr, ws_drift, ws_drift_bytes, ws_policy, ws_policy_bytes, nullptr, cl,
+                                          (char*)tape, tl, status, (hipStream_t)stream, drift_L, mix_W, mix_c, (char*)tape + tl.total,
+                                          scratch_bytes ? (char*)tape + tl.total + stage_bytes : nullptr, scratch_bytes);
 }

@@ -23,7 +23,7 @@ def get_state_initializer(mean: torch.Tensor, covariance: torch.Tensor) -> Calla
 
 
 def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[list], moment_solver: bool,
-                  no_encoder: bool = False, any_objective: bool = False):
+                  no_encoder: bool = False, any_objective: bool = False, coregionalized: bool = False):
   """The pieces the native rollouts are written for -- TrigonometricEncoder, policy = InverseLinkWrapper(KernelRegressor(SVGP with
   one latent per action, up to 4), Chain[Scale, Shift, NormalCDF]) with scale and shift a scalar or one value per action, SVGP
   drift, no diffusion, GaussianObjective (the cartpole wiring of ``examples/cartpole_swingup/swingup_loops.py:41-91``; two
@@ -32,7 +32,9 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
 
   ``no_encoder``: also take ``encoder=None`` and ``TrigonometricEncoder(active_dims=())``, treated alike (the native entries with
   na = 0: the encoding is the identity); the encoder returned is then one without active dims.  ``any_objective``: also take an
-  objective that is no ``GaussianObjective`` (the caller evaluates it on the native rollout's trajectory)."""
+  objective that is no ``GaussianObjective`` (the caller evaluates it on the native rollout's trajectory).  ``coregionalized``: also
+  take a drift with a ``LinearCoregionalization`` kernel of no more latents than outputs (the caller mixes: ``_drift_mixing``); a
+  coregionalised policy stays refused."""
   from . import bijectors as tfb
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
@@ -64,8 +66,18 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   nu = int(pm_.num_latent_gps)
   if nu < 1 or nu > 4:
     return no(f"a policy with {nu} latents (the native rollout takes 1 to 4 actions)")
-  if isinstance(pm_.kernel, LinearCoregionalization) or isinstance(drift.kernel, LinearCoregionalization):
-    return no("a LinearCoregionalization kernel (its mixing stays on the host)")
+  if not coregionalized:
+    if isinstance(pm_.kernel, LinearCoregionalization) or isinstance(drift.kernel, LinearCoregionalization):
+      return no("a LinearCoregionalization kernel (its mixing stays on the host)")
+  elif isinstance(pm_.kernel, LinearCoregionalization):
+    return no("a coregionalised policy (a LinearCoregionalization kernel on the policy: the native mixing covers the drift only)")
+  elif isinstance(drift.kernel, LinearCoregionalization):
+    W = drift.kernel.W
+    if W.ndim != 2 or W.shape[1] != int(drift.num_latent_gps):
+      return no(f"a LinearCoregionalization drift whose W {tuple(W.shape)} does not match its {drift.num_latent_gps} latents")
+    if W.shape[1] > W.shape[0]:
+      return no(f"a coregionalised drift with more latents than outputs (Lg = {W.shape[1]} > nx = {W.shape[0]}: the native "
+                "mixing takes Lg <= nx)")
   if any(k.active_dims is not None for k in pm_.latent_kernels + drift.latent_kernels):
     return no("a kernel with active_dims")
   bj = head.bijectors if isinstance(head, tfb.Chain) else None
@@ -104,9 +116,33 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   return enc, pm_, drift, bj, head_constants
 
 
+def _drift_mixing(drift):
+  """``mixing(device) -> (W [nx, Lg], c [nx] | None)`` of a coregionalised drift as float64 device tensors, or None for any other
+  drift.  The tensors are re-made when ``kernel.W`` or the Constant mean change in place (their ``_version``), as target / precision
+  are re-read: a new pair makes ``native_policy_loss`` rebuild its rollout object."""
+  from .models import Constant, LinearCoregionalization
+  if not isinstance(drift.kernel, LinearCoregionalization):
+    return None
+  memo = {}
+
+  def mixing(device):
+    W = drift.kernel.W
+    c = drift.mean_function.c if isinstance(drift.mean_function, Constant) else None
+    key = (id(W), W._version, None if c is None else (id(c), c._version))
+    hit = memo.get(str(device))
+    if hit is None or hit[0] != key or hit[1] is not W:
+      f64 = torch.float64
+      Wd = W.detach().to(device=device, dtype=f64).clone().contiguous()
+      cd = None if c is None else c.detach().to(device=device, dtype=f64).reshape(-1).clone().contiguous()
+      hit = (key, W, Wd, cd)
+      memo[str(device)] = hit
+    return hit[2], hit[3]
+  return mixing
+
+
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
                        why: Optional[list] = None, native_actions: int = 1, native_no_encoder: bool = False,
-                       native_objective: bool = False):
+                       native_objective: bool = False, native_coregionalized: bool = False):
   """``f(mx, Sxx) -> loss [B]`` running the whole rollout in ``mm_rollout_composed`` (csrc/mm_compose.hip), or None
   when the system is not the shape that entry point implements: TrigonometricEncoder, policy =
   InverseLinkWrapper(KernelRegressor(SVGP with one latent per action), Chain[Scale, Shift, NormalCDF]), SVGP drift, no
@@ -128,14 +164,20 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
   precision require a gradient, is evaluated in torch on the trajectory of the native rollout (``f.uses_trajectory(mx)``):
   ``autodiff.ComposedTrajectoryFunction`` returns the H states as differentiable outputs, the loss is the reference's accumulation
   ``objective(x = encoder match of x_t, t = t)`` over them, and the seeded reverse sweep carries its gradient back to the policy
-  and the initial state; the objective's own parameters get theirs from the torch part."""
+  and the initial state; the objective's own parameters get theirs from the torch part.
+
+  ``native_coregionalized``: take a drift with a ``LinearCoregionalization`` kernel of Lg <= nx latents too: its mixing f = W g + c
+  runs on the device after every drift match (csrc/mm_mix.h) and the rollout -- one action included -- goes through the
+  ``_nd_mixed`` entries, forward and gradient (``ComposedRolloutNDFunction`` / ``ComposedTrajectoryFunction``).  W and the Constant
+  mean are constants of the frozen drift, re-read when they change in place."""
   from . import ops
   from .cost import GaussianObjective
   parts = _native_parts(system, objective, why, moment_solver=True, no_encoder=bool(native_no_encoder),
-                        any_objective=bool(native_objective))
+                        any_objective=bool(native_objective), coregionalized=bool(native_coregionalized))
   if parts is None:
     return None
   enc, pm_, drift, bj, head_constants = parts
+  mixing = _drift_mixing(drift)
   max_native = int(native_actions)
   cache = {}
   gaussian = isinstance(objective, GaussianObjective)
@@ -174,10 +216,12 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     pp = roll.policy if (roll is not None and not fresh_policy) else pm_.packed(mx.dtype, False, mx.device)
     scale, shift = head_constants()
     target, precis = cost_constants(mx, zero)
+    mix_W, mix_c = mixing(mx.device) if mixing is not None else (None, None)
     if (roll is None or roll.drift is not pd or roll.policy is not pp or roll.scale != scale or roll.shift != shift
-        or ent[1] is not target or ent[2] is not precis or ent[3] != (target._version, precis._version)):
+        or ent[1] is not target or ent[2] is not precis or ent[3] != (target._version, precis._version)
+        or (mixing is not None and (roll.mix_W is not mix_W or roll.mix_c is not mix_c))):
       new = ops.ComposedRollout(pd, pp, nx=mx.shape[-1], active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
-                                target=target, precis=precis)
+                                target=target, precis=precis, mix_W=mix_W, mix_c=mix_c)
       if roll is not None:
         new._wsc = roll._wsc                               # same shapes: the workspace carries over
       roll = new
@@ -220,7 +264,8 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       # the objective in torch on the H returned states; the rollout's own (zero-precision) cost is not part of the loss
       _, xm, xS = ComposedTrajectoryFunction.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
       return objective_of_trajectory(xm, xS).to(out_dtype)
-    fn = ComposedRolloutFunction if roll.nu == 1 else ComposedRolloutNDFunction      # (several actions: native_actions >= nu)
+    # (several actions: native_actions >= nu; a coregionalised drift takes the _nd family with one action too)
+    fn = ComposedRolloutNDFunction if roll.uses_nd else ComposedRolloutFunction
     cost = fn.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
     return cost.sum(1).to(out_dtype)
 
@@ -251,11 +296,11 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     for name, t in outside.items():
       if isinstance(t, torch.Tensor) and t.requires_grad:
         return f"{name} requires a gradient (the native reverse sweep covers the policy SVGP's parameters and the initial state)"
-    if any(t.requires_grad for t in drift._parameters()):
+    if any(t.requires_grad for t in drift._parameters()) or (mixing is not None and drift.kernel.W.requires_grad):
       return "the drift is being trained (the native reverse sweep takes a frozen drift)"
     mx64 = mx if mx.dtype == torch.float64 else torch.empty(mx.shape, dtype=torch.float64, device=mx.device)
     roll = current_roll(mx64, fresh_policy=False, zero=uses_trajectory(mx))
-    if nu > 1:
+    if roll.uses_nd:
       return roll.backward_nd_refusal()
     if not roll.supports_backward():
       return (f"the policy has M = {roll.policy.M} centres on {roll.ne} encoded dims (the native reverse sweep takes "
@@ -275,7 +320,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
                         num_steps: int, initial_time: float = 0.0,
                         solution_times: Optional[Sequence[float]] = None, native: Optional[bool] = None,
                         native_actions: int = 1, native_no_encoder: bool = False, native_objective: bool = False,
-                        **kwargs) -> Callable:
+                        native_coregionalized: bool = False, **kwargs) -> Callable:
   """pilco.py:176-220.  Returns ``closure() -> loss [B]``; ``system.solver`` should be a
   ``MomentMatchingEuler`` (pilco.py:141-144).
 
@@ -302,7 +347,13 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   objective, and a ``GaussianObjective`` whose target / precision require a gradient: the rollout stays native, its trajectory
   comes back as a differentiable output (``autodiff.ComposedTrajectoryFunction``), and the objective is accumulated over the H
   states in torch, which also carries the gradient of the objective's own parameters.  Head scale / shift gradients and a
-  trainable drift keep falling back."""
+  trainable drift keep falling back.
+
+  ``native_coregionalized``: with the default False a drift (or policy) with a ``LinearCoregionalization`` kernel takes the torch
+  composition as before.  True runs a coregionalised DRIFT with Lg <= nx latents natively, forward and gradient, for 1 to 4 actions
+  (``native_actions`` still governs the gradient of nu > 1): the mixing f = W g + c is one small launch per step on the device
+  (``mm_rollout_composed_nd_mixed`` and its tape / reverse sweep).  A coregionalised policy, Lg > nx, a trainable drift (W and the
+  mean included) and head / objective constants that require a gradient each fall back once, with a named reason."""
   uniform = solution_times is None
   if solution_times is None:
     solution_times = np.arange(1, 1 + num_steps, dtype=np.float64)     # pilco.py:186
@@ -317,7 +368,8 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
     else:
       why_not = []
       fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not, native_actions=native_actions,
-                                native_no_encoder=native_no_encoder, native_objective=native_objective)
+                                native_no_encoder=native_no_encoder, native_objective=native_objective,
+                                native_coregionalized=native_coregionalized)
       if fast is None:
         shape_reason = why_not[0] if why_not else "the system is not the shape mm_rollout_composed implements"
   if native is True and fast is None:
@@ -345,6 +397,9 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       return False
     models = [system.drift, getattr(getattr(system.policy, "model", None), "model", None)]
     trainable = any(t.requires_grad for m in models if m is not None for t in m._parameters())
+    if native_coregionalized:              # (the mixing matrix of a coregionalised drift is one of its parameters here)
+      W = getattr(system.drift.kernel, "W", None)
+      trainable = trainable or (isinstance(W, torch.Tensor) and W.requires_grad)
     if torch.is_grad_enabled() and (trainable or mx.requires_grad or Sxx.requires_grad or fast.uses_trajectory(mx)):
       return False                       # someone differentiates: the torch composition carries the autograd graph
     if trainable and torch.cuda.is_current_stream_capturing():

@@ -380,11 +380,20 @@ class ComposedRollout:
   moments are bivariate normal CDFs); ``taped`` / ``backward`` are one-action, ``taped_nd`` / ``backward_nd`` the tape and reverse
   sweep for 1 to 4 actions (csrc/mm_compose_bwd_nd.hip).  ``head_scale`` / ``head_shift``: a float or one value per action.
   ``__call__(mx, Sxx, H)`` returns ``(mx_H, Sxx_H, cost [B, H])`` (and the trajectory if asked); the inputs are not modified.
+
+  ``mix_W`` [nx, Lg] (and optionally ``mix_c`` [nx]): the drift is coregionalised -- ``drift`` packs its Lg <= nx latents (with C, no
+  mean) and its outputs are f = W g + c, mixed on the device after every drift match (csrc/mm_mix.h).  Such a rollout (``mixed``)
+  takes the ``_nd_mixed`` entries for any nu, one action included: ``__call__``, ``taped_nd`` / ``backward_nd`` and the size queries;
+  ``taped`` / ``backward`` (the one-action entries) do not take it.
   """
 
   def __init__(self, drift: PackedModel, policy: PackedModel, nx: int, active_dims, head_scale, head_shift,
-               target: torch.Tensor, precis: torch.Tensor):
+               target: torch.Tensor, precis: torch.Tensor, mix_W: Optional[torch.Tensor] = None,
+               mix_c: Optional[torch.Tensor] = None):
     self.drift, self.policy = drift, policy
+    self.mixed = mix_W is not None
+    if mix_c is not None and mix_W is None:
+      raise ValueError("mix_c without mix_W")
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
     self.na = len(self.active)
     self.ne = self.nx + self.na
@@ -392,7 +401,16 @@ class ComposedRollout:
     self.nd = self.ne + self.nu
     if drift.dtype != policy.dtype:
       raise TypeError("drift and policy must be packed with the same dtype")
-    if drift.L != self.nx or drift.d != self.nd or policy.d != self.ne:
+    if self.mixed:
+      if mix_W.ndim != 2 or mix_W.shape[0] != self.nx or mix_W.shape[1] != drift.L:
+        raise ValueError(f"mix_W must be [nx = {self.nx}, Lg = {drift.L}] (the drift pack's latents), got {tuple(mix_W.shape)}")
+      if drift.L > self.nx:
+        raise ValueError(f"a coregionalised drift with more latents than outputs (Lg = {drift.L} > nx = {self.nx}) is not taken")
+      if mix_c is not None and mix_c.numel() != self.nx:
+        raise ValueError(f"mix_c must have nx = {self.nx} entries")
+      self.mix_W = mix_W.detach().to(dtype=torch.float64, device=drift.device).contiguous()
+      self.mix_c = None if mix_c is None else mix_c.detach().to(dtype=torch.float64, device=drift.device).reshape(-1).contiguous()
+    if (not self.mixed and drift.L != self.nx) or drift.d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: drift L={drift.L} d={drift.d} (want {self.nx}, {self.nd}), "
                        f"policy L={policy.L} d={policy.d} (want {self.nu}, {self.ne})")
     if not drift.with_C:
@@ -420,7 +438,9 @@ class ComposedRollout:
   def _compose_ws(self, B):
     ws = self._wsc.get(B)
     if ws is None:
-      if self.nu == 1:
+      if self.mixed:
+        n = lib().mm_compose_nd_mixed_workspace_bytes(B, self.nx, self.na, self.nu, self.drift.L, _dtype_code(self.drift.dtype))
+      elif self.nu == 1:
         n = lib().mm_compose_workspace_bytes(B, self.nx, self.na, _dtype_code(self.drift.dtype))
       else:
         n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(self.drift.dtype))
@@ -463,9 +483,10 @@ class ComposedRollout:
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
     wc = self._compose_ws(B)
-    if self.nu > 1:
-      rc = self._call_nd(pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc)
-      check(rc, "mm_rollout_composed_nd")
+    if self.uses_nd:
+      scale, shift = self._head_arrays()
+      rc = self._call_nd(pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, scale, shift)
+      check(rc, "mm_rollout_composed_nd_mixed" if self.mixed else "mm_rollout_composed_nd")
       out = (mx, Sxx, cost.T.contiguous())
       return out + (tmu, tS) if keep_trajectory else out
     rc = lib().mm_rollout_composed(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
@@ -481,8 +502,19 @@ class ComposedRollout:
 
 
   def _call_nd(self, pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, scale=None, shift=None):
-    """``mm_rollout_composed_nd`` on prepared buffers (``scale`` / ``shift``: ctypes arrays of nu doubles)."""
+    """``mm_rollout_composed_nd`` (``mixed``: ``mm_rollout_composed_nd_mixed``) on prepared buffers (``scale`` / ``shift``: ctypes
+    arrays of nu doubles)."""
     dt_ = self.drift.dtype
+    if self.mixed:
+      return lib().mm_rollout_composed_nd_mixed(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+                                                pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
+                                                _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act, self.nu,
+                                                self._scale_c if scale is None else scale, self._shift_c if shift is None else shift,
+                                                self.target.data_ptr(), self.precis.data_ptr(),
+                                                mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
+                                                wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
+                                                self.drift.status().data_ptr(), _stream(mx.device),
+                                                self.mix_W.data_ptr(), _ptr(self.mix_c))
     return lib().mm_rollout_composed_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
                                         pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
                                         _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act, self.nu,
@@ -491,6 +523,11 @@ class ComposedRollout:
                                         mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
                                         wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
                                         self.drift.status().data_ptr(), _stream(mx.device))
+
+  @property
+  def uses_nd(self) -> bool:
+    """The rollout runs in the ``_nd`` family (several actions, or a coregionalised drift with any number of actions)."""
+    return self.nu > 1 or self.mixed
 
   def call_nd_entry(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0):
     """The same rollout through ``mm_rollout_composed_nd`` whatever nu is (a one-action rollout normally takes
@@ -502,7 +539,10 @@ class ComposedRollout:
     cost = torch.empty(H, B, dtype=dt_, device=mx.device)
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = self.policy.workspace(B, MM_FULL_OUTPUT_COV)
-    n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(dt_))
+    if self.mixed:
+      n = lib().mm_compose_nd_mixed_workspace_bytes(B, self.nx, self.na, self.nu, self.drift.L, _dtype_code(dt_))
+    else:
+      n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(dt_))
     if n == 0:
       raise ValueError("mm_compose_nd_workspace_bytes rejected the shape")
     wc = torch.empty(n, dtype=torch.uint8, device=mx.device)
@@ -517,14 +557,16 @@ class ComposedRollout:
   def supports_backward(self) -> bool:
     """The native reverse sweep exists for one-action f64 rollouts whose policy has M <= 256 centres on ne <= 8 encoded
     dims (one workgroup per batch element sweeps the policy's M x M block from LDS: 120 KB at M = 256, ne = 8)."""
-    return (self.nu == 1 and self.drift.dtype == torch.float64 and self.policy.M <= self.BACKWARD_MAX_POLICY_M
-            and self.ne <= 8)
+    return (self.nu == 1 and not self.mixed and self.drift.dtype == torch.float64
+            and self.policy.M <= self.BACKWARD_MAX_POLICY_M and self.ne <= 8)
 
   def taped(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
     """``mm_rollout_composed_taped``: -> (mx_H, Sxx_H, cost [H, B], tape).  ``policy``: another pack of the same shape
     (the current parameters of a trainable policy)."""
     if self.nu != 1:
       raise NotImplementedError("the tape and the native reverse sweep are one-action (supports_backward() is False)")
+    if self.mixed:
+      raise NotImplementedError("a coregionalised drift takes taped_nd / backward_nd (the one-action entries do not mix)")
     pol = self._policy_pack(policy)
     dt_ = self.drift.dtype
     B, H = self._check_state(mx, Sxx), int(num_steps)
@@ -602,7 +644,10 @@ class ComposedRollout:
   def tape_states(self, tape: torch.Tensor, B: int, num_steps: int):
     """The states x_1 .. x_H a taped rollout left on its tape: -> (xm [H, B, nx], xS [H, B, nx, nx]), float64 copies."""
     H = int(num_steps)
-    if self.nu == 1:
+    if self.mixed:
+      n = lib().mm_compose_tape_bytes_nd_mixed(B, H, self.nx, self.na, self.nu, self.drift.L, self.drift.M, MM_F64)
+      slot = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, MM_F64)        # (the slots are the _nd ones)
+    elif self.nu == 1:
       n = lib().mm_compose_tape_bytes(B, H, self.nx, self.na, self.drift.M, MM_F64)
       slot = lib().mm_compose_workspace_bytes(B, self.nx, self.na, MM_F64)
     else:
@@ -629,7 +674,11 @@ class ComposedRollout:
     """Why ``taped_nd`` / ``backward_nd`` do not take this rollout (None: they do)."""
     if self.drift.dtype != torch.float64:
       return "the multi-action tape and reverse sweep are float64 only"
-    if lib().mm_compose_backward_workspace_bytes_nd(1, self.nx, self.na, self.nu, self.drift.M, self.policy.M) == 0:
+    if self.mixed:
+      n = lib().mm_compose_backward_workspace_bytes_nd_mixed(1, self.nx, self.na, self.nu, self.drift.L, self.drift.M, self.policy.M)
+    else:
+      n = lib().mm_compose_backward_workspace_bytes_nd(1, self.nx, self.na, self.nu, self.drift.M, self.policy.M)
+    if n == 0:
       return (f"the policy (M = {self.policy.M} centres on ne = {self.ne} dims, {self.nu} actions) is past the LDS bound of the "
               "multi-action reverse sweep (M <= 256, ne <= 8 and 160 KB of LDS per workgroup: M <= 166 at ne = 8)")
     return None
@@ -638,6 +687,13 @@ class ComposedRollout:
     """The multi-action tape and reverse sweep (``taped_nd`` / ``backward_nd``) take this rollout: f64, policy M <= 256 centres
     on ne <= 8 encoded dims, up to 4 actions, inside the sweep's LDS bound (``backward_nd_refusal`` names the reason if not)."""
     return self.backward_nd_refusal() is None
+
+  def tape_bytes_nd(self, B: int, num_steps: int) -> int:
+    """Size of the tape ``taped_nd`` records (``mm_compose_tape_bytes_nd`` / ``_nd_mixed``; 0: shape refused)."""
+    if self.mixed:
+      return lib().mm_compose_tape_bytes_nd_mixed(B, int(num_steps), self.nx, self.na, self.nu, self.drift.L, self.drift.M,
+                                                  _dtype_code(self.drift.dtype))
+    return lib().mm_compose_tape_bytes_nd(B, int(num_steps), self.nx, self.na, self.nu, self.drift.M, _dtype_code(self.drift.dtype))
 
   def taped_nd(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
     """``mm_rollout_composed_taped_nd``: -> (mx_H, Sxx_H, cost [H, B], tape), for any nu in 1..4."""
@@ -649,17 +705,21 @@ class ComposedRollout:
       raise ValueError(why)
     mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
     cost = torch.empty(H, B, dtype=dt_, device=mx.device)
-    n = lib().mm_compose_tape_bytes_nd(B, H, self.nx, self.na, self.nu, self.drift.M, _dtype_code(dt_))
+    n = self.tape_bytes_nd(B, H)
     tape = torch.empty(n, dtype=torch.uint8, device=mx.device)
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
     scale, shift = self._head_arrays()
-    rc = lib().mm_rollout_composed_taped_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(dt_), B, H, float(dt),
-                                            self.nx, self.na, self._act, self.nu, scale, shift, self.target.data_ptr(),
-                                            self.precis.data_ptr(), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
-                                            wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
-                                            self.drift.status().data_ptr(), _stream(mx.device))
+    args = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
+            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(dt_), B, H, float(dt),
+            self.nx, self.na, self._act, self.nu, scale, shift, self.target.data_ptr(),
+            self.precis.data_ptr(), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
+            wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
+            self.drift.status().data_ptr(), _stream(mx.device))
+    if self.mixed:
+      rc = lib().mm_rollout_composed_taped_nd_mixed(*args, self.mix_W.data_ptr(), _ptr(self.mix_c))
+    else:
+      rc = lib().mm_rollout_composed_taped_nd(*args)
     check(rc, "mm_rollout_composed_taped_nd")
     return mx, Sxx, cost, tape
 
@@ -685,7 +745,10 @@ class ComposedRollout:
     key = ("bwd_nd", B)
     wb = self._wsc.get(key)
     if wb is None:
-      n = lib().mm_compose_backward_workspace_bytes_nd(B, self.nx, self.na, self.nu, self.drift.M, pol.M)
+      if self.mixed:
+        n = lib().mm_compose_backward_workspace_bytes_nd_mixed(B, self.nx, self.na, self.nu, self.drift.L, self.drift.M, pol.M)
+      else:
+        n = lib().mm_compose_backward_workspace_bytes_nd(B, self.nx, self.na, self.nu, self.drift.M, pol.M)
       if n == 0:
         raise ValueError("mm_compose_backward_workspace_bytes_nd rejected the shape")
       wb = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -697,7 +760,9 @@ class ComposedRollout:
             self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), g_cost.data_ptr())
     tail = (g_pol.data_ptr(), _ptr(g_m), _ptr(g_S), wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
             self.drift.status().data_ptr(), _stream(dev))
-    if g_traj is None:
+    if self.mixed:
+      rc = lib().mm_rollout_composed_backward_nd_mixed(*head, _ptr(g_xm), _ptr(g_xS), *tail, self.mix_W.data_ptr())
+    elif g_traj is None:
       rc = lib().mm_rollout_composed_backward_nd(*head, *tail)
     else:
       rc = lib().mm_rollout_composed_backward_nd_seeded(*head, _ptr(g_xm), _ptr(g_xS), *tail)

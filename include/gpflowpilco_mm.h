@@ -327,6 +327,57 @@ int mm_rollout_composed_backward_nd_seeded(const void* drift_packed, size_t drif
                                            void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                            int32_t* status, void* stream);
 
+/* ---- the _nd rollouts with a COREGIONALISED drift (gpflow's LinearCoregionalization; csrc/mm_mix.h) -----------------------------
+ * The drift pack has drift_L = Lg latents on drift_d = nd inputs (packed with C, no mean of its own), 1 <= Lg <= nx, and its nx
+ * outputs are f = W g + c:
+ *   mix_W  device, f64, row-major [nx][drift_L]          (NULL: MM_E_ARG)
+ *   mix_c  device, f64, [nx], or NULL for no output mean
+ * Per step the drift's match runs with L = Lg, full output covariance and model uncertainty (added in latent space, as
+ * moment_matching/models.py:254-286), into a staging block; then ONE launch per step (one workgroup per batch element) writes
+ *   f1 = W g1 + c,   Sff = W Sgg W^T (i <= j computed and mirrored: exactly symmetric),   cross = cross_g W^T  [nd][nx]
+ * in f64 whatever the state type, rounded on store.  Tail, encoder, head and cost see an ordinary drift with nx outputs.  (The packed
+ * [B][Lg] blocks of neighbouring batch elements overlap the [B][nx] ones, so the mixing is not done in place: hence the staging
+ * block and mm_compose_nd_mixed_workspace_bytes.)  The tape stores the mixed moments; its kept drift workspace and kept backward
+ * sums are sized with Lg.  Where the tape does not keep the sums per step, the taped forward still computes the drift's value with
+ * the routine of mm_moment_match_with_sums, into one scratch buffer at the end of the tape: the value of a taped rollout, and its
+ * gradient, are the same in every regime of the tape (element b of a large batch reproduces that element of a small one bit for
+ * bit), at the price of the backward's sweeps in place of the forward's in that taped forward.  The reverse sweep runs the adjoint g g1 = W^T g f1, g Sgg = W^T (g Sff) W, g cross_g = (g cross) W
+ * between the tail's adjoint and the drift match's adjoint with L = Lg.  No gradient w.r.t. W, c or the drift; no floating-point
+ * atomics (two sweeps over one tape are bit-equal).
+ * drift_L < 1 or > nx: MM_E_DIM, and the size queries return 0.  Every other check is that of the _nd entry of the same name with
+ * drift_L in place of nx for the drift's pack and workspace (mm_workspace_bytes(B, drift_L, ...), mm_packed_model_bytes(drift_L, ...)).
+ * The argument lists are those of mm_rollout_composed_nd / _taped_nd / _backward_nd_seeded (null seeds: the plain sweep) with the
+ * mixing operands appended. */
+size_t mm_compose_nd_mixed_workspace_bytes(int B, int nx, int na, int nu, int drift_L, int dtype);
+int mm_rollout_composed_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                 const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                 int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                 int nu, const double* head_scale, const double* head_shift,
+                                 const void* target, const void* precis,
+                                 void* mx, void* Sxx, void* cost, void* traj_mu, void* traj_Sigma,
+                                 void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                                 void* ws_compose, size_t ws_compose_bytes, int32_t* status, void* stream,
+                                 const double* mix_W, const double* mix_c);
+size_t mm_compose_tape_bytes_nd_mixed(int B, int H, int nx, int na, int nu, int drift_L, int drift_M, int dtype);
+int mm_rollout_composed_taped_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                       const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                       int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                       int nu, const double* head_scale, const double* head_shift,
+                                       const void* target, const void* precis, void* mx, void* Sxx, void* cost,
+                                       void* ws_drift, size_t ws_drift_bytes, void* ws_policy, size_t ws_policy_bytes,
+                                       void* tape, size_t tape_bytes, int32_t* status, void* stream,
+                                       const double* mix_W, const double* mix_c);
+size_t mm_compose_backward_workspace_bytes_nd_mixed(int B, int nx, int na, int nu, int drift_L, int drift_M, int policy_M);
+int mm_rollout_composed_backward_nd_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                          const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                          int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                          int nu, const double* head_scale, const double* head_shift,
+                                          const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                          const void* g_cost, const void* g_xm, const void* g_xS,
+                                          void* g_policy, void* g_mx0, void* g_Sxx0,
+                                          void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                          int32_t* status, void* stream, const double* mix_W);
+
 /* ---- backward w.r.t. the input moments, stage A (f64 mode) ---------------------
  * The M x M part of d(f1, Sff, cross)/d(mu, Sigma) reduced to M-sized sums (see csrc/mm_backward.hip);
  * gpflowpilco_amd/autodiff.py finishes the chain rule.  Must follow mm_moment_match / mm_q_forward +
