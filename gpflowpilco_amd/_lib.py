@@ -221,6 +221,16 @@ SIGNATURES = {
                                                         + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
                                                         + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
                                                         + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mm_pathwise_tape_bytes_mixed": (C.c_size_t, [C.c_int] * 8),
+    "mm_pathwise_policy_rollout_mixed": (C.c_int, [C.c_int] * 5 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                         + [C.c_void_p] * 9
+                                         + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                         + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+                                         + [C.c_int, C.c_void_p, C.c_void_p]),
+    "mm_pathwise_policy_rollout_backward_mixed": (C.c_int, [C.c_int] * 3 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                                  + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                                  + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
+                                                  + [C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int, C.c_void_p]),
     "mm_pathwise_basis": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 9),
     "mm_pathwise_pack_stream": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 4),
     "mm_rollout_closed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -22,18 +22,23 @@ struct MMPwTapeLayout {
   size_t jac;    // [H][S][nx][nd] T   d f / d d per step (0 bytes when not differentiating)
   size_t total;
 };
-// nd = nx + na + nu (nu = 1: the one-action tape)
-static inline MMPwTapeLayout mm_pw_tape_layout(int S, int H, int nx, int na, int nu, int dtype, int with_jac) {
+// Lf: the number of drift samples a step keeps -- nx, or the Lg latents of a coregionalised drift (the _mixed entries: the f
+// slot is [S][Lg] and the Jacobian block [H][S][Lg][nd])
+static inline MMPwTapeLayout mm_pw_tape_layout_latent(int S, int H, int nx, int na, int nu, int Lf, int dtype, int with_jac) {
   MMPwTapeLayout o;
   const size_t es = mm_elem_size(dtype), A = 256;
   const int nd = nx + na + nu;
   size_t off = 0;
   o.x = off;   off = mm_align_up(off + (size_t)(H + 1) * S * nx * es, A);
   o.din = off; off = mm_align_up(off + (size_t)H * S * nd * es, A);
-  o.f = off;   off = mm_align_up(off + (size_t)S * nx * es, A);
-  o.jac = off; off = mm_align_up(off + (with_jac ? (size_t)H * S * nx * nd * es : 0), A);
+  o.f = off;   off = mm_align_up(off + (size_t)S * Lf * es, A);
+  o.jac = off; off = mm_align_up(off + (with_jac ? (size_t)H * S * Lf * nd * es : 0), A);
   o.total = off;
   return o;
+}
+// nd = nx + na + nu (nu = 1: the one-action tape)
+static inline MMPwTapeLayout mm_pw_tape_layout(int S, int H, int nx, int na, int nu, int dtype, int with_jac) {
+  return mm_pw_tape_layout_latent(S, H, nx, na, nu, nx, dtype, with_jac);
 }
 
 __device__ __forceinline__ void mmp_encode(const MMComposeDims& D, const double* x, double* e) {

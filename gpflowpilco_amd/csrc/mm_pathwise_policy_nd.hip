@@ -13,6 +13,10 @@
 // (k_pw_head_nd), the one-kernel reverse sweep (k_pw_policy_bwd_nd) and their entries.  The policy is an ordinary mm_pack_model
 // pack with L = nu; only its f64 blocks are read (Z64 [L][M][ne], beta64 [L][M], ls2 [L][ne], var [L], meanc [L]).
 //
+// A third set, the _mixed entries (nd <= 16), takes a COREGIONALISED drift f = W g + c: the stream pass runs with the Lg <= nx
+// latents into a latent-sized tape (sample slot [S][Lg], Jacobians [H][S][Lg][nd]) and both kernels mix in place of a launch of
+// its own (bool MIXED: the head steps x += dt (c + W g), the sweep takes g d = dt J_g^T (W^T g x)).
+//
 // Both kernels are templates in the action count: the loops over the latents unroll, the per-latent constants sit in
 // registers, and with NU = 1 the arithmetic is the one-action kernels' in the same order (outputs bit-equal).
 //
@@ -30,14 +34,18 @@
 // k_pw_head_nd: grid ceil(S / 256), thread = sample.  h in [0, H]:
 //   h > 0: x_h = x_{h-1} + dt f_{h-1} -> tape; cost[h-1][s] of its encoding;    h < H: the drift input (e_h, u_h[nu]) -> tape.
 // LDS: the NU policy blocks one after the other (each Z [M][ne] | beta [M] | 1 / ls2 [ne]), target [ne], W [ne][ne].
-template <typename T, int NU>
+// MIXED (the _mixed entries: a coregionalised drift): f is the LATENT sample g [S][Lg] and the step is
+//   x_{h+1,i} = x_{h,i} + dt (c_i + sum_l mixW[i][l] g_l),   mixW [nx][Lg], mixc [nx] or NULL: f64 in global memory, read at
+// wave-uniform addresses (scalar loads; nothing of it in LDS).  MIXED = false: Lg, mixW, mixc are not read.
+template <typename T, int NU, bool MIXED>
 __global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int h, int H, double dt, const T* __restrict__ xprev,
                                                     const T* __restrict__ f, T* __restrict__ xcur, T* __restrict__ din,
                                                     T* __restrict__ cost, const T* __restrict__ target,
                                                     const T* __restrict__ precis, const double* __restrict__ pZ,
                                                     const double* __restrict__ pbeta, const double* __restrict__ pls2,
                                                     const double* __restrict__ pvar, const double* __restrict__ pmean, int pM,
-                                                    MMHeadND hd) {
+                                                    MMHeadND hd, int Lg, const double* __restrict__ mixW,
+                                                    const double* __restrict__ mixc) {
   extern __shared__ double sm[];
   const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne;
   double* pol = sm;                                        // [NU][M ne + M + ne]
@@ -52,9 +60,20 @@ __global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int 
   if (s >= S) return;
   double x[MMC_NX], e[MMP_NE];
   if (h > 0) {
-    for (int i = 0; i < nx; ++i) {
-      x[i] = (double)xprev[(size_t)s * nx + i] + dt * (double)f[(size_t)s * nx + i];   // Euler.step, solvers.py:50-65
-      xcur[(size_t)s * nx + i] = (T)x[i];
+    if (MIXED) {
+      double g[MMC_NX];
+      for (int l = 0; l < Lg; ++l) g[l] = (double)f[(size_t)s * Lg + l];
+      for (int i = 0; i < nx; ++i) {
+        double fi = mixc ? mixc[i] : 0.0;                    // the constant is added after the mixing; latent order
+        for (int l = 0; l < Lg; ++l) fi = fma(mixW[i * Lg + l], g[l], fi);
+        x[i] = (double)xprev[(size_t)s * nx + i] + dt * fi;
+        xcur[(size_t)s * nx + i] = (T)x[i];
+      }
+    } else {
+      for (int i = 0; i < nx; ++i) {
+        x[i] = (double)xprev[(size_t)s * nx + i] + dt * (double)f[(size_t)s * nx + i];   // Euler.step, solvers.py:50-65
+        xcur[(size_t)s * nx + i] = (T)x[i];
+      }
     }
   } else {
     for (int i = 0; i < nx; ++i) x[i] = (double)xcur[(size_t)s * nx + i];
@@ -80,7 +99,9 @@ __global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int 
 // dvar, dmean (npar1 = M ne + M + ne + 2);  g_x0 [S][nx] (optional).  g_cost [H][S] f64.
 // SEEDED (the _seeded entries with a seed on the states, or without the built-in cost): g_x [H][S][nx] f64, block h = d loss /
 // d x_{h+1} (NULL: none); g_cost NULL: the built-in cost's term is skipped.  SEEDED = false: the built-in cost alone.
-template <typename T, int NU, bool SEEDED>
+// MIXED: jacs is the LATENT Jacobian tape [H][S][Lg][nd] and g d = dt J_g^T (mixW^T g x_{h+1}) in two steps (mixW as in the head
+// kernel: global memory, wave-uniform addresses); everything else is the unmixed sweep.
+template <typename T, int NU, bool SEEDED, bool MIXED>
 __global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
                                                           const T* __restrict__ dins, const T* __restrict__ jacs,
                                                           const double* __restrict__ g_cost, const double* __restrict__ g_x,
@@ -89,7 +110,8 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S
                                                           const double* __restrict__ pls2, const double* __restrict__ pvar,
                                                           const double* __restrict__ pmean, int pM, MMHeadND hd,
                                                           double* __restrict__ gpart,
-                                                          double* __restrict__ g_x0) {
+                                                          double* __restrict__ g_x0, int Lg,
+                                                          const double* __restrict__ mixW) {
   extern __shared__ double sm[];
   const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne, npar1 = blk + 2, npar = NU * npar1;
   double* pol = sm;
@@ -128,11 +150,26 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S
     }
     // x_{h+1} = x_h + dt f(d_h):  g d = dt J^T g x_{h+1}
     double gd[MMP_NE + MMC_NU], e[MMP_NE];
-    const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
-    for (int k = 0; k < nd; ++k) {
-      double r = 0.0;
-      for (int i = 0; i < nx; ++i) r = fma((double)J[i * nd + k], gx[i], r);
-      gd[k] = dt * r;
+    if (MIXED) {
+      double gg[MMC_NX];                                     // adjoint of the latent sample: gg = mixW^T g x_{h+1}
+      for (int l = 0; l < Lg; ++l) {
+        double r = 0.0;
+        for (int i = 0; i < nx; ++i) r = fma(mixW[i * Lg + l], gx[i], r);
+        gg[l] = r;
+      }
+      const T* J = jacs + ((size_t)h * S + sr) * (size_t)Lg * nd;
+      for (int k = 0; k < nd; ++k) {
+        double r = 0.0;
+        for (int l = 0; l < Lg; ++l) r = fma((double)J[l * nd + k], gg[l], r);
+        gd[k] = dt * r;
+      }
+    } else {
+      const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
+      for (int k = 0; k < nd; ++k) {
+        double r = 0.0;
+        for (int i = 0; i < nx; ++i) r = fma((double)J[i * nd + k], gx[i], r);
+        gd[k] = dt * r;
+      }
     }
     const T* dn = dins + ((size_t)h * S + sr) * nd;
     for (int i = 0; i < ne; ++i) e[i] = (double)dn[i];
@@ -209,6 +246,13 @@ extern "C" size_t mm_pathwise_tape_bytes_nd(int S, int H, int nx, int na, int nu
   return mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians).total;
 }
 
+// the _mixed tape: the f slot [S][Lg] and the Jacobian block [H][S][Lg][nd] hold the LATENT sample and its Jacobian
+extern "C" size_t mm_pathwise_tape_bytes_mixed(int S, int H, int nx, int na, int nu, int Lg, int dtype, int with_jacobians) {
+  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU || Lg < 1 ||
+      Lg > nx) return 0;
+  return mm_pw_tape_layout_latent(S, H, nx, na, nu, Lg, dtype, with_jacobians).total;
+}
+
 #define MMP_ND_DISPATCH(nu_, M_)                                                       \
   switch (nu_) {                                                                       \
     case 1: M_(1); break;                                                              \
@@ -222,8 +266,11 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
                             const void* phase, const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
                             const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
                             int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
-                            char* tape, const MMPwTapeLayout& tl, hipStream_t s) {
-  const int nx = D.nx, ne = D.ne, nd = D.nd;
+                            char* tape, const MMPwTapeLayout& tl, int Lg, const double* mix_W, const double* mix_c,
+                            hipStream_t s) {
+  // Lg > 0: the _mixed entries -- the stream pass runs with Lg latents and no latent mean straight into the tape's (latent-sized)
+  // f and Jacobian slots, the head kernel mixes
+  const int nx = D.nx, ne = D.ne, nd = D.nd, Lf = Lg > 0 ? Lg : nx;
   T* xs = (T*)(tape + tl.x); T* dins = (T*)(tape + tl.din); T* f = (T*)(tape + tl.f);
   T* jac = tl.jac != tl.total ? (T*)(tape + tl.jac) : nullptr;
   hipError_t e = hipMemcpyAsync(xs, x0, (size_t)S * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
@@ -231,31 +278,35 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
   const size_t lds = mmp_nd_head_lds(policy_M, ne, nu);
   const dim3 grid((S + 255) / 256);
   for (int h = 0; h <= H; ++h) {
-#define MMP_HEAD(NU_)                                                                                                            \
+#define MMP_HEAD_(NU_, MIXED_)                                                                                                   \
     if (h == 0 && lds > 64 * 1024) {   /* nu >= 3 policies on wide encodings: up to 108 KB at M = 256 */                          \
-      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_head_nd<T, NU_>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                          (int)lds);                                                                             \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_head_nd<T, NU_, MIXED_>,                                             \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
       if (ea != hipSuccess) return (int)ea;                                                                                      \
     }                                                                                                                            \
-    hipLaunchKernelGGL((k_pw_head_nd<T, NU_>), grid, dim3(256), lds, s, D, S, h, H, dt,                                          \
+    hipLaunchKernelGGL((k_pw_head_nd<T, NU_, MIXED_>), grid, dim3(256), lds, s, D, S, h, H, dt,                                  \
                        h > 0 ? xs + (size_t)(h - 1) * S * nx : (const T*)nullptr, (const T*)f, xs + (size_t)h * S * nx,          \
                        h < H ? dins + (size_t)h * S * nd : (T*)nullptr, cost, target, precis, (const double*)(pp + pl.Z64),      \
                        (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),              \
-                       (const double*)(pp + pl.meanc), policy_M, hd)
+                       (const double*)(pp + pl.meanc), policy_M, hd, Lg, mix_W, mix_c)
+#define MMP_HEAD(NU_) if (Lg > 0) { MMP_HEAD_(NU_, true); } else { MMP_HEAD_(NU_, false); }
     MMP_ND_DISPATCH(nu, MMP_HEAD)
 #undef MMP_HEAD
+#undef MMP_HEAD_
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (h == H) break;
-    const int rc = mm_pathwise_launch(S, nx, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
-                                      prior_scale, variance, mean_c, wb, f, jac ? jac + (size_t)h * S * nx * nd : nullptr, s);
+    const int rc = mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
+                                      prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f,
+                                      jac ? jac + (size_t)h * S * Lf * nd : nullptr, s);
     if (rc) return rc;
   }
   return 0;
 }
 
-// the forward entries: _nd (nd_max = 8) and _wide (nd_max = 16) are this function
-static int mmp_nd_rollout(int nd_max, int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+// the forward entries: _nd (nd_max = 8), _wide (nd_max = 16) and _mixed (nd_max = 16, mixed: Lg, mix_W, mix_c) are this function
+static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, const double* mix_c, int S, int M, int K,
+                          int dtype, int H, double dt, int nx, int na,
                           const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
                           const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
                           const double* variance, const double* mean_c, const void* wb,
@@ -266,9 +317,11 @@ static int mmp_nd_rollout(int nd_max, int S, int M, int K, int dtype, int H, dou
   MMComposeDims D;
   int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
+  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
+  if (!mixed) Lg = 0;                                        // (what the launches below take for "no mixing")
   if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !head_scale ||
-      !head_shift || !target || !precis || !x0 || !cost || !tape) return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians);
+      !head_shift || !target || !precis || !x0 || !cost || !tape || (mixed && !mix_W)) return MM_E_ARG;
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, with_jacobians);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
   if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
@@ -279,10 +332,10 @@ static int mmp_nd_rollout(int nd_max, int S, int M, int K, int dtype, int H, dou
   if (dtype == MM_F64)
     return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
                                     wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
-                                    (double*)cost, (char*)tape, tl, s);
+                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s);
   return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
                                  pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
-                                 (char*)tape, tl, s);
+                                 (char*)tape, tl, Lg, mix_W, mix_c, s);
 }
 
 #define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
@@ -292,13 +345,28 @@ static int mmp_nd_rollout(int nd_max, int S, int M, int K, int dtype, int H, dou
                        const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
                        const double* head_shift, const void* target, const void* precis, const void* x0, void* cost, void* tape, \
                        size_t tape_bytes, int with_jacobians, void* stream) {                                                    \
-    return mmp_nd_rollout(nd_max_, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz, x_scale,            \
-                          prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,      \
-                          target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);                                   \
+    return mmp_nd_rollout(nd_max_, false, 0, nullptr, nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase,   \
+                          zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,           \
+                          head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);           \
   }
 MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_nd, 8)
 MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_wide, 16)
 #undef MMP_ROLLOUT_ENTRY
+
+// a coregionalised drift: the paths' operands are those of Lg latents, mean_c is not read (the constant is mix_c)
+extern "C" int mm_pathwise_policy_rollout_mixed(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                                                const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                                                const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                                                const double* variance, const double* mean_c, const void* wb,
+                                                const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                const double* head_scale, const double* head_shift, const void* target,
+                                                const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                                int with_jacobians, void* stream, int Lg, const double* mix_W,
+                                                const double* mix_c) {
+  return mmp_nd_rollout(16, true, Lg, mix_W, mix_c, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz,
+                        x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
+                        target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);
+}
 
 // 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)
 static size_t mmp_nd_scratch_bytes(int nd_max, int S, int policy_M, int ne, int nu) {
@@ -314,8 +382,9 @@ extern "C" size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, i
 }
 
 // the backward entries: _nd (nd_max = 8) and _wide (nd_max = 16), unseeded (g_cost required, g_x = nullptr) and _seeded (either
-// seed may be NULL, not both), are this function
-static int mmp_nd_backward(int nd_max, bool seeded_entry, int S, int dtype, int H, double dt, int nx, int na,
+// seed may be NULL, not both), are this function; so is _mixed (nd_max = 16, seeded, mixed: Lg and mix_W)
+static int mmp_nd_backward(int nd_max, bool seeded_entry, bool mixed, int Lg, const double* mix_W, int S, int dtype, int H,
+                           double dt, int nx, int na,
                            const int32_t* active_dims, int nu, const void* policy_packed,
                            size_t policy_bytes, int policy_M, const double* head_scale,
                            const double* head_shift, const void* target, const void* precis,
@@ -324,13 +393,14 @@ static int mmp_nd_backward(int nd_max, bool seeded_entry, int S, int dtype, int 
   MMComposeDims D;
   int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
+  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
   if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape ||
-      (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch)
+      (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch || (mixed && !mix_W))
     return MM_E_ARG;
   const int ne = D.ne, npar = nu * (policy_M * ne + policy_M + ne + 2);
   const size_t lds = mmp_nd_bwd_lds(policy_M, ne, nu);
   if (lds > MMP_ND_LDS_MAX) return MM_E_DIM;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, nu, dtype, 1);
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   if (scratch_bytes < mmp_nd_scratch_bytes(nd_max, S, policy_M, ne, nu)) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, MM_F64, 1);
@@ -342,24 +412,28 @@ static int mmp_nd_backward(int nd_max, bool seeded_entry, int S, int dtype, int 
   const dim3 grid((S + 255) / 256);
   // (the built-in cost alone: the unseeded instantiation, whichever entry was called -- same arithmetic, bit-equal outputs)
   const bool seeded = g_x != nullptr || g_cost == nullptr;
-#define MMP_BWD(T_, NU_, SEEDED_)                                                                                                 \
+#define MMP_BWD(T_, NU_, SEEDED_, MIXED_)                                                                                         \
   do {                                                                                                                          \
     if (lds > 64 * 1024) {                                                                                                      \
-      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_, SEEDED_>,                                     \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_, SEEDED_, MIXED_>,                             \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
       if (ea != hipSuccess) return (int)ea;                                                                                     \
     }                                                                                                                           \
-    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_, SEEDED_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),     \
-                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const double*)g_x,           \
-                       (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),     \
-                       (const double*)(pp + pl.ls2), (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M, hd, \
-                       (double*)scratch, (double*)g_x0);                                                                        \
+    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_, SEEDED_, MIXED_>), grid, dim3(256), lds, s, D, S, H, dt,                     \
+                       (const T_*)(tp + tl.x), (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost,       \
+                       (const double*)g_x, (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64),                  \
+                       (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),             \
+                       (const double*)(pp + pl.meanc), policy_M, hd, (double*)scratch, (double*)g_x0, Lg, mix_W);               \
   } while (0)
-#define MMP_BWD_F64(NU_) if (seeded) MMP_BWD(double, NU_, true); else MMP_BWD(double, NU_, false)
-#define MMP_BWD_F32(NU_) if (seeded) MMP_BWD(float, NU_, true); else MMP_BWD(float, NU_, false)
+#define MMP_BWD_T(T_, NU_)                                                                                                       \
+  if (mixed) { if (seeded) MMP_BWD(T_, NU_, true, true); else MMP_BWD(T_, NU_, false, true); }                                   \
+  else { if (seeded) MMP_BWD(T_, NU_, true, false); else MMP_BWD(T_, NU_, false, false); }
+#define MMP_BWD_F64(NU_) MMP_BWD_T(double, NU_)
+#define MMP_BWD_F32(NU_) MMP_BWD_T(float, NU_)
   if (dtype == MM_F64) { MMP_ND_DISPATCH(nu, MMP_BWD_F64) } else { MMP_ND_DISPATCH(nu, MMP_BWD_F32) }
 #undef MMP_BWD_F64
 #undef MMP_BWD_F32
+#undef MMP_BWD_T
 #undef MMP_BWD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -371,19 +445,32 @@ static int mmp_nd_backward(int nd_max, bool seeded_entry, int S, int dtype, int 
                        const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
                        const double* head_shift, const void* target, const void* precis, const void* tape, size_t tape_bytes,    \
                        const void* g_cost, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {      \
-    return mmp_nd_backward(nd_max_, false, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M,       \
-                           head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch,   \
-                           scratch_bytes, stream);                                                                              \
+    return mmp_nd_backward(nd_max_, false, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,            \
+                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, nullptr,    \
+                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
   }                                                                                                                             \
   extern "C" int name_##_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,          \
                                 const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,          \
                                 const double* head_shift, const void* target, const void* precis, const void* tape,              \
                                 size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy, void* g_x0,              \
                                 void* scratch, size_t scratch_bytes, void* stream) {                                            \
-    return mmp_nd_backward(nd_max_, true, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes, policy_M,        \
-                           head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch,       \
-                           scratch_bytes, stream);                                                                              \
+    return mmp_nd_backward(nd_max_, true, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,             \
+                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x,        \
+                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
   }
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_nd, 8)
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_wide, 16)
 #undef MMP_BACKWARD_ENTRY
+
+// the reverse sweep of the _mixed rollout: the _seeded signature (either of g_cost and g_x may be NULL, not both) + the mixing
+extern "C" int mm_pathwise_policy_rollout_backward_mixed(int S, int dtype, int H, double dt, int nx, int na,
+                                                         const int32_t* active_dims, int nu, const void* policy_packed,
+                                                         size_t policy_bytes, int policy_M, const double* head_scale,
+                                                         const double* head_shift, const void* target, const void* precis,
+                                                         const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                                         void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes,
+                                                         void* stream, int Lg, const double* mix_W) {
+  return mmp_nd_backward(16, true, true, Lg, mix_W, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes,
+                         policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch,
+                         scratch_bytes, stream);
+}

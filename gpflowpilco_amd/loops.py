@@ -140,6 +140,26 @@ def _drift_mixing(drift):
   return mixing
 
 
+def _pathwise_mixing_obstacle(drift, paths, grad: bool) -> Optional[str]:
+  """Why the ``_mixed`` pathwise entries do not take these sample paths of a coregionalised ``drift`` (None: they do): the paths
+  must carry the drift's mixing -- ``mix_W`` of W's shape, ``mix_c`` exactly when the mean is a ``Constant`` -- and, where a
+  gradient is being taken (``grad``), W and the mean must be constants: the reverse sweep has no adjoint for them."""
+  from .models import Constant
+  W = drift.kernel.W
+  c = drift.mean_function.c if isinstance(drift.mean_function, Constant) else None
+  pW, pc = getattr(paths, "mix_W", None), getattr(paths, "mix_c", None)
+  if pW is None:
+    return "the given paths carry no mixing (mix_W) for the coregionalised drift"
+  if tuple(pW.shape) != tuple(W.shape) or (pc is None) != (c is None) or (pc is not None and pc.shape[0] != W.shape[0]):
+    return (f"the given paths carry a mixing of another shape than the drift's (mix_W {tuple(pW.shape)}, mix_c "
+            f"{None if pc is None else tuple(pc.shape)}; the drift: W {tuple(W.shape)}, mean {None if c is None else tuple(c.shape)})")
+  if grad and W.requires_grad:
+    return "the drift's mixing matrix W requires a gradient (the native reverse sweep takes a frozen drift)"
+  if grad and c is not None and c.requires_grad:
+    return "the coregionalised drift's Constant mean requires a gradient (the native reverse sweep takes a frozen drift)"
+  return None
+
+
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
                        why: Optional[list] = None, native_actions: int = 1, native_no_encoder: bool = False,
                        native_objective: bool = False, native_coregionalized: bool = False):
@@ -518,7 +538,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
                                  dt: float = 1.0, num_bases: int = 1024, paths=None, native: Optional[bool] = None,
                                  generator: Optional[torch.Generator] = None, native_actions: int = 1,
                                  native_inputs: int = 8, native_sampler: bool = False,
-                                 native_no_encoder: bool = False, native_objective: bool = False) -> Callable:
+                                 native_no_encoder: bool = False, native_objective: bool = False,
+                                 native_coregionalized: bool = False) -> Callable:
   """``PathwisePILCO._policy_loss_closure`` (gpflow_pilco/loops/pilco.py:263-298).  Returns ``closure() -> loss [S]``: the cost
   accumulated along one sample rollout per initial state -- per step encoder -> policy -> drift sample path -> Euler -> objective
   of the encoded state (tensor branch of ``forward_sde``, dynamics/forward_sde.py:23-31; ``Euler.step``, solvers.py:50-65).  The
@@ -568,11 +589,22 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   (``mm_pathwise_policy_rollout_backward[_nd|_wide]_seeded``) carries d loss / d x_h back to the policy and the initial states; the
   objective's own parameters get their gradients from the torch part.  A constant ``GaussianObjective`` keeps the in-kernel cost.
   The option composes with ``native_actions``, ``native_inputs``, ``native_no_encoder``, ``native_sampler`` and ``paths`` under their
-  rules; head scale / shift gradients keep falling back."""
+  rules; head scale / shift gradients keep falling back.
+
+  ``native_coregionalized``: with the default False a drift (or policy) with a ``LinearCoregionalization`` kernel takes the torch
+  composition, saying so once (``native=True`` raises) -- on paths that carry the drift's mixing (``Paths.mix_W`` / ``mix_c``:
+  ``generate_paths`` and ``PathSampler`` draw Lg latent paths and ``Paths.__call__`` returns W g + c), so the composition is
+  correct for any Lg.  True runs a coregionalised DRIFT with Lg <= nx latents in the ``_mixed`` native entries, forward and
+  gradient (csrc/mm_pathwise_policy_nd.hip: a latent-sized tape, the mixing inside the head kernel and the reverse sweep), for
+  1 to 4 actions and nd <= 16 under the ``native_actions`` / ``native_inputs`` rules; it composes with ``native_no_encoder``,
+  ``native_objective``, ``native_sampler`` and ``paths=``.  W and the Constant mean are constants of the frozen drift, taken from
+  the paths of the call.  A coregionalised policy, Lg > nx, given ``paths`` that carry no mixing or one of another shape than the
+  drift's, and a W or a mean that requires a gradient each fall back once, with a named reason."""
   from . import ops
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
   from .linalg import index_tensor
+  from .models import LinearCoregionalization
   from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction, PolicyTrajectoryFunction
   drift = system.drift
   if not isinstance(drift, PathwiseSVGP):
@@ -581,7 +613,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   why_not: list = []
   parts = None if native is False else _native_parts(system, objective, why_not, moment_solver=False,
                                                      no_encoder=bool(native_no_encoder),
-                                                     any_objective=bool(native_objective))
+                                                     any_objective=bool(native_objective),
+                                                     coregionalized=bool(native_coregionalized))
   gaussian = isinstance(objective, GaussianObjective)
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
@@ -688,6 +721,11 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
     traj = _uses_trajectory()
     grad = torch.is_grad_enabled()
+    if isinstance(drift.kernel, LinearCoregionalization):      # (native_coregionalized: _native_parts refused it otherwise)
+      obstacle = _pathwise_mixing_obstacle(drift, pth, grad)
+      if obstacle is not None:
+        _fallback(obstacle)
+        return _torch_loss(x0, pth)
     if grad:
       for name, t in outside.items():
         if isinstance(t, torch.Tensor) and t.requires_grad:

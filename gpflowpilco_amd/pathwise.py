@@ -26,7 +26,8 @@ import torch
 from .linalg import cholesky
 
 from . import _lib
-from .models import DEFAULT_FLOAT, DEFAULT_JITTER, SVGP, Constant, Zero, _stack_kernel_params, unpack_multioutput
+from .models import (DEFAULT_FLOAT, DEFAULT_JITTER, SVGP, Constant, LinearCoregionalization, Zero, _stack_kernel_params,
+                     unpack_multioutput)
 from .ops import _dtype_code, _ptr, _require_device, _stream, check
 
 
@@ -41,7 +42,13 @@ def _pad_last(t: torch.Tensor, mult: int) -> torch.Tensor:
 
 @dataclass
 class Paths:
-  """S sample paths of L latent GPs (device tensors, element type ``dtype``)."""
+  """S sample paths of L latent GPs (device tensors, element type ``dtype``).
+
+  ``mix_W`` [nx, Lg] (with ``mix_c`` [nx] or None; both float64): the paths of a coregionalised model, f = W g + c -- L = Lg latent
+  paths mixed to nx outputs, the constant added after the mixing as gpflow does (``mean_c`` is then None).  ``__call__``,
+  ``eval_jac`` and ``eval_with_bound`` return the MIXED quantities (f [S, nx], J = W J_g [S, nx, d], bound |W| err_g): the latent
+  values from the entries below with L = Lg, the mixing as a few float64 torch ops -- the route of the torch composition; the
+  native policy rollout mixes in its own kernels (``PolicyRollout``)."""
   omega: torch.Tensor      # [L, d, Kp]   omega^T / 2 pi  (revolutions, k-major)
   phase: torch.Tensor      # [L, Kp]      b / 2 pi
   zs: torch.Tensor         # [L, d, Mp]   (Z * x_scale)^T, x_scale = sqrt(log2 e) / lengthscales
@@ -52,6 +59,8 @@ class Paths:
   prior_scale: torch.Tensor    # [L] f64  sqrt(2 var / K)
   variance: torch.Tensor       # [L] f64
   mean_c: Optional[torch.Tensor]  # [L] f64 or None
+  mix_W: Optional[torch.Tensor] = None   # [nx, Lg] f64: f = W g + c (None: the latents are the outputs)
+  mix_c: Optional[torch.Tensor] = None   # [nx] f64 or None
 
   @property
   def dtype(self):
@@ -61,11 +70,20 @@ class Paths:
     L, d, Kp = self.omega.shape
     return self.num_samples, L, self.zs.shape[-1], Kp, d
 
+  def _mixed_values(self, g: torch.Tensor) -> torch.Tensor:
+    """g [S, Lg] -> W g + c [S, nx] (float64 arithmetic, this dtype's result)."""
+    f = g.to(DEFAULT_FLOAT) @ self.mix_W.T
+    return (f if self.mix_c is None else f + self.mix_c).to(self.dtype)
+
   def __call__(self, x: torch.Tensor) -> torch.Tensor:
-    """f_s(x_s): x [S, d] -> [S, L].  Differentiable in x where the Jacobian pass exists (d <= 16): the torch composition of a
-    sample rollout (``loops.pathwise_policy_loss_closure``'s fallback) then carries gradients through the paths."""
+    """f_s(x_s): x [S, d] -> [S, L] (mixed paths: [S, nx]).  Differentiable in x where the Jacobian pass exists (d <= 16): the torch
+    composition of a sample rollout (``loops.pathwise_policy_loss_closure``'s fallback) then carries gradients through the paths."""
     if torch.is_grad_enabled() and x.requires_grad:
       return _PathsEval.apply(x, self)
+    g = self._latent_values(x)
+    return g if self.mix_W is None else self._mixed_values(g)
+
+  def _latent_values(self, x: torch.Tensor) -> torch.Tensor:
     _require_device(x, self.wb)
     S, L, Mp, Kp, d = self._dims()
     if x.shape != (S, d) or x.dtype != self.dtype:
@@ -82,7 +100,13 @@ class Paths:
 
   def eval_jac(self, x: torch.Tensor):
     """f_s(x_s) and its Jacobian: x [S, d] -> (f [S, L], d f / d x [S, L, d]) from ONE pass over the weight stream (d <= 16; for
-    d > 8 a wave takes the four samples of a group two at a time).  f is bit-equal to ``__call__``'s."""
+    d > 8 a wave takes the four samples of a group two at a time).  f is bit-equal to ``__call__``'s.  Mixed paths: (W g + c, W J_g)."""
+    g, jac = self._latent_jac(x)
+    if self.mix_W is None:
+      return g, jac
+    return self._mixed_values(g), torch.einsum('il,sld->sid', self.mix_W, jac.to(DEFAULT_FLOAT)).to(self.dtype)
+
+  def _latent_jac(self, x: torch.Tensor):
     _require_device(x, self.wb)
     S, L, Mp, Kp, d = self._dims()
     if x.shape != (S, d) or x.dtype != self.dtype:
@@ -102,7 +126,14 @@ class Paths:
     """f_s(x_s) and a bound on what this dtype's rounding did to it: x [S, d] -> (f [S, L], err [S, L]) from ONE pass over the
     weight stream (``mm_pathwise_eval_bound``).  err = BOUND_ULPS u (scale sum_k |w cos| + var sum_m |v k|): the update weights
     v = Kuu^-1 (u - Phi w) cancel 1e5 .. 1e7-fold in sum_m v_m k(x, z_m) at M = 2000, so a float32 sample's value can have lost
-    its digits (C5 shard: ~2e-2 of max |f|) -- this is where the caller sees it; float64 paths are the accurate mode."""
+    its digits (C5 shard: ~2e-2 of max |f|) -- this is where the caller sees it; float64 paths are the accurate mode.  Mixed paths:
+    (W g + c, |W| err_g)."""
+    g, err = self._latent_bound(x)
+    if self.mix_W is None:
+      return g, err
+    return self._mixed_values(g), (err.to(DEFAULT_FLOAT) @ self.mix_W.abs().T).to(self.dtype)
+
+  def _latent_bound(self, x: torch.Tensor):
     _require_device(x, self.wb)
     S, L, Mp, Kp, d = self._dims()
     if x.shape != (S, d) or x.dtype != self.dtype:
@@ -128,6 +159,9 @@ class Paths:
 
   def rollout(self, x0: torch.Tensor, num_steps: int, dt: float = 1.0, keep_trajectory: bool = False):
     """Drift-only Euler rollout of all S paths (d == L): x <- x + dt f(x), H steps in one ABI call."""
+    if self.mix_W is not None:
+      raise ValueError("Paths.rollout: the drift-only rollout does not mix (these paths carry mix_W: f = W g + c); step "
+                       "x + dt paths(x) in torch, or use PolicyRollout")
     _require_device(x0, self.wb)
     S, L, Mp, Kp, d = self._dims()
     x = x0.contiguous().clone()
@@ -158,9 +192,20 @@ class _PathsEval(torch.autograd.Function):
 
 
 def paths_from_arrays(omega, phase, w, v, Z, lengthscales, variance, mean_c=None, dtype=torch.float32,
-                      device="cuda") -> Paths:
-  """Build ``Paths`` from explicit arrays (omega [L,K,d], phase [L,K], w [S,L,K], v [S,L,M], Z [L,M,d])."""
+                      device="cuda", mix_W=None, mix_c=None) -> Paths:
+  """Build ``Paths`` from explicit arrays (omega [L,K,d], phase [L,K], w [S,L,K], v [S,L,M], Z [L,M,d]).  ``mix_W`` [nx, L] (and
+  ``mix_c`` [nx] or None): the mixing of a coregionalised model; the latents then have no mean of their own."""
   t64 = lambda a: torch.as_tensor(a, dtype=DEFAULT_FLOAT, device=device)
+  if mix_W is None and mix_c is not None:
+    raise ValueError("mix_c without mix_W")
+  if mix_W is not None:
+    if mean_c is not None:
+      raise ValueError("mixed paths carry no latent mean: the constant is mix_c, added after the mixing")
+    mix_W = t64(mix_W).contiguous()
+    mix_c = None if mix_c is None else t64(mix_c).reshape(-1).contiguous()
+    if mix_W.ndim != 2 or mix_W.shape[1] != omega.shape[0] or (mix_c is not None and mix_c.shape[0] != mix_W.shape[0]):
+      raise ValueError(f"mix_W must be [nx, L = {omega.shape[0]}] and mix_c [nx], got {tuple(mix_W.shape)} and "
+                       f"{None if mix_c is None else tuple(mix_c.shape)}")
   mult = 128 if dtype == torch.float64 else 256          # BT: terms per block of the weight stream
   xscale = math.sqrt(math.log2(math.e)) / t64(lengthscales)                    # [L, d]
   zs = t64(Z) * xscale[:, None, :]
@@ -183,7 +228,23 @@ def paths_from_arrays(omega, phase, w, v, Z, lengthscales, variance, mean_c=None
   wb = allw.reshape(G, 4, L, NB, mult).permute(0, 2, 3, 1, 4).to(dtype).contiguous()
   return Paths(omega=omega_p, phase=padk(t64(phase) / two_pi), zs=zs_p, hz=padk(hz), wb=wb, num_samples=S,
                lengthscales=xscale.contiguous(), prior_scale=torch.sqrt(2.0 * var / K).contiguous(),
-               variance=var.contiguous(), mean_c=None if mean_c is None else t64(mean_c).contiguous())
+               variance=var.contiguous(), mean_c=None if mean_c is None else t64(mean_c).contiguous(), mix_W=mix_W, mix_c=mix_c)
+
+
+def _mean_and_mixing(model: SVGP, L: int, device):
+  """-> (mean_c [L] | None, mix_W [nx, Lg] | None, mix_c [nx] | None), float64 on ``device``: a ``LinearCoregionalization`` kernel
+  mixes its L = Lg latent paths with W and adds the Constant mean (nx entries, or one value for all) afterwards."""
+  c = None
+  if isinstance(model.mean_function, Constant):
+    c = model.mean_function.c.detach().to(device=device, dtype=DEFAULT_FLOAT)
+  elif not isinstance(model.mean_function, Zero):
+    raise NotImplementedError
+  if not isinstance(model.kernel, LinearCoregionalization):
+    return (None if c is None else c.expand(L).contiguous()), None, None
+  W = model.kernel.W.detach().to(device=device, dtype=DEFAULT_FLOAT).clone().contiguous()
+  if W.ndim != 2 or W.shape[1] != L:
+    raise ValueError(f"LinearCoregionalization: W {tuple(W.shape)} does not match the {L} latent kernels")
+  return None, W, (None if c is None else c.expand(W.shape[0]).clone().contiguous())
 
 
 def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=torch.float32,
@@ -211,12 +272,8 @@ def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=t
   Phi_Z = torch.sqrt(2.0 * var / K)[:, None, None] * torch.cos(Z @ omega.transpose(1, 2) + phase[:, None, :])  # [L,M,K]
   resid = u - torch.einsum('lmk,slk->slm', Phi_Z, w)
   v = torch.cholesky_solve(resid.permute(1, 2, 0), Luu).permute(2, 0, 1)             # [S, L, M]
-  mean_c = None
-  if isinstance(model.mean_function, Constant):
-    mean_c = model.mean_function.c.to(device=device, dtype=DEFAULT_FLOAT).expand(L).contiguous()
-  elif not isinstance(model.mean_function, Zero):
-    raise NotImplementedError
-  return paths_from_arrays(omega, phase, w, v, Z, ls, var, mean_c, dtype=dtype, device=device)
+  mean_c, mix_W, mix_c = _mean_and_mixing(model, L, device)
+  return paths_from_arrays(omega, phase, w, v, Z, ls, var, mean_c, dtype=dtype, device=device, mix_W=mix_W, mix_c=mix_c)
 
 
 class PathSampler:
@@ -227,7 +284,7 @@ class PathSampler:
   next ``draw`` after an in-place update): the stacked Z, lengthscales and variances, ``Luu = chol(Kuu + jitter)`` (one
   ``linalg.cholesky`` with its check), ``q(u)``'s mean and factor -- mapped through ``Luu`` for a whitened model, so that
   u = c + T eps is one batched GEMM -- and the model-constant operands of ``Paths`` (``zs``, ``hz``, ``lengthscales``, ``prior_scale``,
-  ``variance``, ``mean_c``: the torch expressions of ``paths_from_arrays``).  Preallocated once: the float64 draw buffers
+  ``variance``, ``mean_c``, and for a coregionalised model ``mix_W``, ``mix_c``: the torch expressions of ``paths_from_arrays``).  Preallocated once: the float64 draw buffers
   ``n [L,K,d]``, ``b [L,K]``, ``w [S,L,K]``, ``eps [S,L,M]``, ``Phi_Z [L,M,K]``, the right-hand side ``[L,M,S]`` the two triangular
   solves run in place on, and the outputs ``omega``, ``phase``, ``wb`` in the stream dtype.
 
@@ -251,7 +308,10 @@ class PathSampler:
   # -- what depends on the model alone ------------------------------------------------------------------------------------------
   def _refresh(self):
     model, dev = self.model, self.device
-    key = tuple((id(t), t._version, t.device) for t in model._parameters())
+    params = list(model._parameters())                       # (the Constant mean's tensor is one of them)
+    if isinstance(model.kernel, LinearCoregionalization):
+      params.append(model.kernel.W)
+    key = tuple((id(t), t._version, t.device) for t in params)
     if key == self._key:
       return
     if torch.cuda.is_current_stream_capturing():
@@ -272,11 +332,7 @@ class PathSampler:
       c, T = q_mu.unsqueeze(-1), q_sqrt
       if model.whiten:                                                                # u = Luu (q_mu + q_sqrt eps)
         c, T = Luu @ c, Luu @ T
-      mean_c = None
-      if isinstance(model.mean_function, Constant):
-        mean_c = model.mean_function.c.to(device=dev, dtype=DEFAULT_FLOAT).expand(L).contiguous()
-      elif not isinstance(model.mean_function, Zero):
-        raise NotImplementedError
+      mean_c, mix_W, mix_c = _mean_and_mixing(model, L, dev)
       # the model-constant operands of Paths, by the expressions of paths_from_arrays
       mult = 128 if self.dtype == torch.float64 else 256
       tt = lambda a: a.to(self.dtype).contiguous()
@@ -284,7 +340,8 @@ class PathSampler:
       zs = Z * xscale[:, None, :]
       hz = 0.5 * (zs * zs).sum(-1)
       self._const = dict(zs=tt(_pad_last(zs.transpose(1, 2), mult)), hz=tt(_pad_last(hz, mult)), lengthscales=xscale.contiguous(),
-                         prior_scale=torch.sqrt(2.0 * var / self.K).contiguous(), variance=var.contiguous(), mean_c=mean_c)
+                         prior_scale=torch.sqrt(2.0 * var / self.K).contiguous(), variance=var.contiguous(), mean_c=mean_c,
+                         mix_W=mix_W, mix_c=mix_c)
       self._Z, self._ls, self._var = Z.contiguous(), ls.contiguous(), var.contiguous()
       self._Luu, self._LuuT = Luu.contiguous(), Luu.transpose(1, 2)
       self._c, self._T = c.contiguous(), T.contiguous()
@@ -384,7 +441,11 @@ class PolicyRollout:
   ``target`` / ``precis`` None: a zero target and a zero precision of the right size (the entries need the pointers); the cost
   output is then meaningless -- the rollout of a caller whose loss is its own function of the states: ``trajectory(tape, H)`` gives
   x_1 .. x_H, and ``backward(..., g_states=...)`` (the ``_seeded`` entries) carries d loss / d x_1 .. x_H back to the policy and
-  to x_0, with or without a ``g_cost`` of the built-in cost beside it."""
+  to x_0, with or without a ``g_cost`` of the built-in cost beside it.
+
+  Paths with ``mix_W`` (a coregionalised drift: Lg latents mixed to nx outputs, Lg <= nx) run the ``_mixed`` entries -- nd <= 16,
+  1 to 4 actions, the ``_nd`` shapes of ``g_policy``; ``wide`` and ``nd_entries`` are then ignored.  The tape's sample slot and
+  Jacobian block are latent-sized (``mm_pathwise_tape_bytes_mixed``); the mixing happens in the head kernel and the reverse sweep."""
 
   def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
                target: Optional[torch.Tensor] = None, precis: Optional[torch.Tensor] = None, nd_entries: Optional[bool] = None,
@@ -397,7 +458,20 @@ class PolicyRollout:
     self.ne, self.nd = self.nx + self.na, self.nx + self.na + self.nu
     if not 1 <= self.nu <= 4:
       raise ValueError(f"the pathwise policy rollout takes policies with 1 to 4 latents (one per action), got {self.nu}")
-    if L != self.nx or d != self.nd or policy.d != self.ne:
+    mix_W = getattr(paths, "mix_W", None)
+    self.mixed = mix_W is not None
+    self.Lg = int(L) if self.mixed else 0
+    if self.mixed:
+      if mix_W.ndim != 2 or mix_W.shape[0] != self.nx or mix_W.shape[1] != L:
+        raise ValueError(f"shapes do not compose: mix_W {tuple(mix_W.shape)} (want [nx = {self.nx}, Lg = {L}]: one row per state, "
+                         "one column per latent path)")
+      if L > self.nx:
+        raise ValueError(f"the mixed pathwise policy rollout takes Lg <= nx latents, got Lg = {L} > nx = {self.nx}")
+      mix_c = getattr(paths, "mix_c", None)
+      if mix_c is not None and tuple(mix_c.shape) != (self.nx,):
+        raise ValueError(f"shapes do not compose: mix_c {tuple(mix_c.shape)} (want [nx = {self.nx}])")
+      wide, nd_entries = True, True
+    if (not self.mixed and L != self.nx) or d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: paths L={L} d={d} (want {self.nx}, {self.nd}), policy L={policy.L} d={policy.d} "
                        f"(want {self.nu}, {self.ne})")
     self.wide = bool(wide)
@@ -432,6 +506,9 @@ class PolicyRollout:
                    precis.to(dtype=paths.dtype, device=dev).contiguous())
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
     self._sfx = "wide" if self.wide else "nd"                  # which set of entries with the _nd signatures
+    if self.mixed:                                             # (the scratch query of the mixed sweep is the _wide one)
+      self._mix_W = mix_W.detach().to(dtype=torch.float64, device=dev).contiguous()
+      self._mix_c = None if mix_c is None else mix_c.detach().to(dtype=torch.float64, device=dev).contiguous()
 
   def _policy(self, policy):
     pol = self.policy if policy is None else policy
@@ -453,7 +530,9 @@ class PolicyRollout:
       raise ValueError(f"expected x0 [{S},{self.nx}] of {P.dtype}, got {tuple(x0.shape)} {x0.dtype}")
     H, code = int(num_steps), _dtype_code(P.dtype)
     lib = _lib.lib()
-    if self.nd_entries:
+    if self.mixed:
+      n = lib.mm_pathwise_tape_bytes_mixed(S, H, self.nx, self.na, self.nu, self.Lg, code, int(with_jacobians))
+    elif self.nd_entries:
       n = lib.mm_pathwise_tape_bytes_nd(S, H, self.nx, self.na, self.nu, code, int(with_jacobians))
     else:
       n = lib.mm_pathwise_tape_bytes(S, H, self.nx, self.na, code, int(with_jacobians))
@@ -463,14 +542,15 @@ class PolicyRollout:
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
     if self.nd_entries:
-      entry = f"mm_pathwise_policy_rollout_{self._sfx}"
+      entry = "mm_pathwise_policy_rollout_" + ("mixed" if self.mixed else self._sfx)
+      mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
       rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
                                P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
                                P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
                                _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
                                self._scale_c, self._shift_c, self.target.data_ptr(), self.precis.data_ptr(),
                                x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                               int(with_jacobians), _stream(x0.device))
+                               int(with_jacobians), _stream(x0.device), *mixing)
       check(rc, entry)
       return cost, tape
     rc = lib.mm_pathwise_policy_rollout(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act,
@@ -517,11 +597,13 @@ class PolicyRollout:
   def _sweep(self, pol, tape, g_cost, g_states, H, dt, want_state_grad, seeded):
     """One reverse sweep: the unseeded entry of this rollout's family (one action, ``_nd``, ``_wide``), or -- ``seeded`` -- its
     ``_seeded`` sibling, which takes ``g_x`` after ``g_cost`` (either may be None -> NULL).  g_cost [H, S], g_states [H, S, nx]:
-    contiguous f64."""
+    contiguous f64.  Mixed paths: the one ``_mixed`` entry, which has the seeded signature."""
     S, code, dev = self.paths.num_samples, _dtype_code(self.paths.dtype), tape.device
     npar = pol.M * self.ne + pol.M + self.ne + 2
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
+    seeded = seeded or self.mixed
     seeds = (_ptr(g_cost), _ptr(g_states)) if seeded else (g_cost.data_ptr(),)
+    mixing = (self.Lg, self._mix_W.data_ptr()) if self.mixed else ()
     lib = _lib.lib()
     if self.nd_entries:
       ns = getattr(lib, f"mm_pathwise_backward_scratch_bytes_{self._sfx}")(S, pol.M, self.ne, self.nu)
@@ -529,7 +611,8 @@ class PolicyRollout:
         raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
                          "slabs exceed 160 KiB of LDS (see supports_backward)")
       g_pol = torch.empty(self.nu, npar, dtype=torch.float64, device=dev)
-      entry = f"mm_pathwise_policy_rollout_backward_{self._sfx}" + ("_seeded" if seeded else "")
+      entry = ("mm_pathwise_policy_rollout_backward_mixed" if self.mixed else
+               f"mm_pathwise_policy_rollout_backward_{self._sfx}" + ("_seeded" if seeded else ""))
       head = (self.nu, pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c)
     else:
       ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
@@ -539,7 +622,7 @@ class PolicyRollout:
     scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
     rc = getattr(lib, entry)(S, code, H, dt, self.nx, self.na, self._act, *head, self.target.data_ptr(), self.precis.data_ptr(),
                              tape.data_ptr(), tape.numel(), *seeds, g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
-                             scratch.numel(), _stream(dev))
+                             scratch.numel(), _stream(dev), *mixing)
     check(rc, entry)
     return g_pol, g_x0
 

@@ -584,6 +584,39 @@ int mm_pathwise_policy_rollout_backward_wide_seeded(int S, int dtype, int H, dou
                                                     const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
                                                     void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- the same entries for a COREGIONALISED drift: f = W g + c, Lg latents mixed to nx outputs (1 <= Lg <= nx) --------------------
+ * The paths' operands (omega_t .. wb) are those of mm_pathwise_eval with L = Lg latents on nd = nx + na + nu <= 16 inputs
+ * (1 <= nu <= 4; the same implementation as the _nd / _wide entries, so any nd <= 16 is taken); mean_c is NOT read: the constant
+ * is mix_c, added after the mixing.  mix_W [nx][Lg], mix_c [nx] (may be NULL: zero): f64 DEVICE arrays, appended after the
+ * _nd arguments.  Per step  x_{h+1,i} = x_{h,i} + dt (c_i + sum_l W[i][l] g_l)  in f64, one fma per latent in latent order,
+ * rounded to T on store.  The tape is latent-sized: after the states and drift inputs of the _nd tape come the sample slot
+ * [S][Lg] and the Jacobian block [H][S][Lg][nd] -- the stream pass writes g and d g / d d straight into them, there is no
+ * separate mixing launch -- so mm_pathwise_tape_bytes_mixed(.., Lg = nx, ..) == mm_pathwise_tape_bytes_nd(..) and a smaller Lg
+ * shrinks exactly those two blocks.  states x_0 .. x_H lead the tape as before.
+ * The backward has the arguments of mm_pathwise_policy_rollout_backward_nd_seeded (either of g_cost and g_x may be NULL, not
+ * both) + Lg, mix_W:  g d = dt J_g^T (W^T g x_{h+1}); everything else is the unmixed sweep.  W and c are read from global memory
+ * at wave-uniform addresses, not through LDS: the sweep takes every shape for which
+ * mm_pathwise_backward_scratch_bytes_wide(S, policy_M, ne, nu) is non-zero, with that scratch size; g_policy as in the _nd entries.
+ * Refused: Lg < 1 or Lg > nx, nd > 16, nu outside 1..4, policy_M > 256 (MM_E_DIM; mm_pathwise_tape_bytes_mixed returns 0); a NULL
+ * mix_W or any other required pointer (MM_E_ARG); short buffers (MM_E_WORKSPACE). */
+size_t mm_pathwise_tape_bytes_mixed(int S, int H, int nx, int na, int nu, int Lg, int dtype, int with_jacobians);
+int mm_pathwise_policy_rollout_mixed(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                     int nu, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                                     const double* x_scale, const double* prior_scale, const double* variance,
+                                     const double* mean_c, const void* wb,
+                                     const void* policy_packed, size_t policy_bytes, int policy_M,
+                                     const double* head_scale, const double* head_shift,
+                                     const void* target, const void* precis, const void* x0, void* cost,
+                                     void* tape, size_t tape_bytes, int with_jacobians, void* stream,
+                                     int Lg, const double* mix_W, const double* mix_c);
+int mm_pathwise_policy_rollout_backward_mixed(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                              int nu, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                              const double* head_scale, const double* head_shift,
+                                              const void* target, const void* precis,
+                                              const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                              void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream,
+                                              int Lg, const double* mix_W);
+
 /* ---- path GENERATION: the two reformatting steps of a draw (csrc/mm_pathwise_sample.hip) -----------------------------------
  * PathwisePILCO draws new paths on every optimiser step (loops/pilco.py:281-284).  Between the random draws, two GEMMs and two
  * triangular solves (the caller's: pathwise.PathSampler keeps them on torch's BLAS with a cached Kuu factor) a draw is

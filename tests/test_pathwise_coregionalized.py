@@ -1,0 +1,815 @@
+"""The pathwise side for a COREGIONALISED drift (a LinearCoregionalization kernel: Lg latent paths mixed to nx outputs,
+f = W g + c): Paths with mix_W / mix_c (the torch composition's route), the _mixed entries of the policy rollout and its reverse
+sweep (csrc/mm_pathwise_policy_nd.hip, pathwise.PolicyRollout on such paths) and
+loops.pathwise_policy_loss_closure(native_coregionalized=True), against tests/pathwise_mixed_oracle.py -- a fold of
+oracle.pathwise_oracle and tests/pathwise_multiaction_oracle.py with f = eval_paths(latent paths) @ W.T + c.
+
+Systems (recipe of tests/test_pathwise_wide.py::_system: drift M 50, K 130, policy M 12 with its own Z per latent, w, v and the
+policy's q_mu x 0.3, precis x 0.25, H = 6, dt = 0.5, S = 37 and S = 300; the drift has Lg latents and no latent mean, W is standard
+normal with l2-normalised rows -- SVGP.initialize's recipe --, c uniform in +-0.1):
+  M1  nx 4, angle (1,),    nu 1, Lg 2 -> nd 6    one action through the mixed family                 seed 210
+  M2  nx 4, angles (0, 2), nu 2, Lg 3 -> nd 8    edge of the narrow path                             seed 220
+  M3  nx 6, angles (2, 4), nu 1, Lg 3 -> nd 9    wide path; the README's 6-state system              seed 230
+  M4  nx 5, no angles,     nu 2, Lg 5 -> nd 7    na = 0, dense square W                              seed 240
+  M5  nx 3, angle (0,),    nu 1, Lg 1 -> nd 5    one latent                                          seed 250
+  I8 / I9: M2's / M3's wiring with Lg = nx, W = I, c = None (the identity mixing, against the unmixed _nd / _wide entries)
+  X   nx 3, angle (0,), nu 1, Lg 4: more latents than outputs (torch composition only)
+
+Bars: f64 1e-10 and f32 5e-3 on costs and taped states; f 1e-11 / 2e-3 and J 1e-7 / 3e-3 for the paths and their Jacobian;
+gradients 1e-8 relative per tensor against torch autograd of a torch mirror and 1e-6 max(1, |fd|) against central differences of
+the numpy helper.  An f32 figure that misses its bar while f64 passes is held to twice the unmixed system's figure (same recipe,
+same process), both printed."""
+import copy
+import ctypes
+import functools
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from gpflowpilco_amd import _lib
+from gpflowpilco_amd.synthetic import make_svgp
+from oracle import pathwise_oracle as pw
+from tests import pathwise_mixed_oracle as pmx
+from tests import test_pathwise_multiaction as tm          # _TorchPaths, _policy_params
+from tests import test_pathwise_wide as tw                 # _analytic_jacobian
+from tests.helpers import gp_model_from_oracle, oracle_params, random_svgp_params, scale_err
+
+F64 = torch.float64
+SCALE, SHIFT = (2.0, 1.5, 1.0, 1.2), (-0.5, -0.4, -0.6, -0.45)
+SYSTEMS = {"M1": dict(nx=4, active=(1,), nu=1, Lg=2, seed=210),
+           "M2": dict(nx=4, active=(0, 2), nu=2, Lg=3, seed=220),
+           "M3": dict(nx=6, active=(2, 4), nu=1, Lg=3, seed=230),
+           "M4": dict(nx=5, active=(), nu=2, Lg=5, seed=240),
+           "M5": dict(nx=3, active=(0,), nu=1, Lg=1, seed=250),
+           "I8": dict(nx=4, active=(0, 2), nu=2, Lg=4, seed=220, identity=True),
+           "I9": dict(nx=6, active=(2, 4), nu=1, Lg=6, seed=230, identity=True),
+           "X": dict(nx=3, active=(0,), nu=1, Lg=4, seed=260)}
+MIXED = ["M1", "M2", "M3", "M4", "M5"]
+UNMIXED_OF = {"M1": "I8", "M2": "I8", "M3": "I9", "M4": "I8", "M5": "I8"}   # an unmixed system of the same recipe (narrow / wide)
+H6, DT = 6, 0.5
+F32_BAR, F64_BAR = 5e-3, 1e-10
+
+
+@functools.lru_cache(maxsize=None)
+def _system(name, S, pol_M=12):
+  """The numpy side of a system and its helper rollout (computed once, shared, never modified)."""
+  c = SYSTEMS[name]
+  nx, active, nu, Lg, seed = c["nx"], c["active"], c["nu"], c["Lg"], c["seed"]
+  na = len(active); ne = nx + na; nd = ne + nu
+  rng = np.random.default_rng(seed)
+  drift = oracle_params(make_svgp(Lg, 50, nd, seed=seed + 1, ls_bounds=(0.8, 3.0)))   # the LATENT model: no mean of its own
+  assert drift.mean_c is None
+  drift.Z[..., ne:] = 4.0 * drift.Z[..., ne:] - 2.0                       # action axes in [-2, 2]
+  pol = random_svgp_params(seed=seed + 2, L=nu, M=pol_M, d=ne, whiten=True, ls_bounds=(0.8, 2.0), mean=True, separate_Z=True)
+  pol.q_mu = 0.3 * pol.q_mu
+  paths = pw.draw_paths(rng, drift, S, 130)
+  paths.w *= 0.3; paths.v *= 0.3
+  x0 = rng.uniform(0.2, 0.8, size=(S, nx))
+  target = np.zeros(ne); target[na:2 * na] = 1.0; target[2 * na:] = 0.1
+  A = rng.standard_normal((ne, ne))
+  precis = 0.25 * (0.5 * (A @ A.T) / ne + 0.5 * np.eye(ne))
+  if c.get("identity"):
+    W, cm = np.eye(nx), None
+  else:
+    W = rng.standard_normal((nx, Lg))
+    W = W / np.linalg.norm(W, axis=-1, keepdims=True)
+    cm = rng.uniform(-0.1, 0.1, size=nx)
+  scale, shift = np.array(SCALE[:nu]), np.array(SHIFT[:nu])
+  cost_o, states_o = pmx.policy_rollout_costs_mixed(paths, drift, W, cm, pol, scale, shift, active, target, precis, x0, H6, dt=DT,
+                                                    keep=True)
+  return dict(c, S=S, na=na, ne=ne, nd=nd, drift=drift, pol=pol, paths=paths, x0=x0, target=target, precis=precis, scale=scale,
+              shift=shift, W=W, c=cm, cost_o=cost_o, states_o=states_o)
+
+
+def _oracle(sy, H, pol=None, x0=None, W=None, **kw):
+  return pmx.policy_rollout_costs_mixed(sy["paths"], sy["drift"], sy["W"] if W is None else W, sy["c"],
+                                        sy["pol"] if pol is None else pol, sy["scale"], sy["shift"], sy["active"], sy["target"],
+                                        sy["precis"], sy["x0"] if x0 is None else x0, H, dt=DT, **kw)
+
+
+def _device_paths(sy, device, dtype, mixed=True):
+  from gpflowpilco_amd.pathwise import paths_from_arrays
+  P, dr = sy["paths"], sy["drift"]
+  mix = dict(mix_W=sy["W"], mix_c=sy["c"]) if mixed else {}
+  return paths_from_arrays(P.omega, P.phase, P.w, P.v, dr.Z, dr.lengthscales, dr.variance, None, dtype=dtype, device=device, **mix)
+
+
+def _device_case(sy, device, dtype, mixed=True):
+  """(paths, policy model, PolicyRollout); mixed=False (identity systems only): the same paths through the unmixed entries."""
+  from gpflowpilco_amd.pathwise import PolicyRollout
+  gp_paths = _device_paths(sy, device, dtype, mixed)
+  pol_model = gp_model_from_oracle(sy["pol"], device)
+  roll = PolicyRollout(gp_paths, pol_model.packed(F64, False, device), nx=sy["nx"], active_dims=sy["active"],
+                       head_scale=tuple(sy["scale"]), head_shift=tuple(sy["shift"]), target=torch.tensor(sy["target"]),
+                       precis=torch.tensor(sy["precis"]), nd_entries=None if mixed else True, wide=(not mixed) and sy["nd"] > 8)
+  return gp_paths, pol_model, roll
+
+
+class _TorchMixedPaths:
+  """The mixed sample paths in plain torch ops (CPU): what Paths.__call__ computes on paths with mix_W, for the closure's CPU
+  test -- tm._TorchPaths for the latents, then g W^T + c."""
+
+  def __init__(self, sy):
+    self.latent = tm._TorchPaths(sy["paths"], sy["drift"])
+    self.mix_W = torch.tensor(sy["W"], dtype=F64)
+    self.mix_c = None if sy["c"] is None else torch.tensor(sy["c"], dtype=F64)
+
+  def __call__(self, x):
+    f = self.latent(x) @ self.mix_W.T
+    return f if self.mix_c is None else f + self.mix_c
+
+
+def _torch_system(sy, device):
+  """The system with a coregionalised PathwiseSVGP drift (LinearCoregionalization(kernels, W), Constant(c) mean)."""
+  from gpflowpilco_amd import bijectors as tfb, dynamics, models as gp
+  from gpflowpilco_amd.components import GaussianObjective, TrigonometricEncoder
+  from gpflowpilco_amd.pathwise import PathwiseSVGP
+  t = lambda a: torch.tensor(np.asarray(a), dtype=F64, device=device)
+  dm = copy.copy(sy["drift"])
+  dm.W, dm.mean_c = sy["W"], sy["c"]
+  drift = gp_model_from_oracle(dm, device)
+  assert isinstance(drift.kernel, gp.LinearCoregionalization)
+  pol_model = gp_model_from_oracle(sy["pol"], device)
+  head = tfb.Chain([tfb.Scale(t(sy["scale"])), tfb.Shift(t(sy["shift"])), tfb.NormalCDF()])
+  policy = gp.InverseLinkWrapper(gp.KernelRegressor(pol_model), invlink=head)
+  pdrift = PathwiseSVGP(kernel=drift.kernel, inducing_variable=drift.inducing_variable, q_mu=drift.q_mu, q_sqrt=drift.q_sqrt,
+                        whiten=sy["drift"].whiten, mean_function=drift.mean_function, num_latent_gps=sy["Lg"])
+  encoder = TrigonometricEncoder(active_dims=sy["active"]) if sy["active"] else None
+  system = dynamics.DynamicalSystem(drift=pdrift, policy=policy, encoder=encoder, solver=dynamics.Euler())
+  objective = GaussianObjective(target=t(sy["target"]), precis=t(sy["precis"]))
+  return system, objective, pol_model
+
+
+# ---- CPU 1: the systems ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MIXED)
+def test_systems_are_well_posed_and_wrong_wirings_are_far_outside_the_f32_bar(name):
+  """Costs away from both ends of -exp(-q / 2), states inside the data's support; dropping c, reading W's buffer with the other
+  stride and feeding the latents in rotated order each move the costs by at least 4x the f32 bar.  M5 has one latent: there is
+  nothing to rotate, and a [3, 1] buffer reads the same with either stride -- both are the identity there (asserted as 0); its
+  guard is the constant."""
+  sy = _system(name, 37)
+  assert np.isfinite(sy["cost_o"]).all() and np.abs(sy["states_o"]).max() < 3.0
+  assert sy["cost_o"].max() < -0.05 and sy["cost_o"].min() > -0.999
+  no_c = scale_err(_oracle(sy, H6, wiring="no_c"), sy["cost_o"])
+  stride = scale_err(_oracle(sy, H6, wiring="stride"), sy["cost_o"])
+  rot = scale_err(_oracle(sy, H6, wiring="rotated"), sy["cost_o"])
+  print(f"guards {name}: no c {no_c:.2e}, other stride {stride:.2e}, rotated latents {rot:.2e}; |states| < "
+        f"{np.abs(sy['states_o']).max():.2f}, costs in [{sy['cost_o'].min():.3f}, {sy['cost_o'].max():.3f}]")
+  assert no_c >= 4 * F32_BAR
+  if sy["Lg"] == 1:
+    assert stride == 0.0 and rot == 0.0
+  else:
+    assert stride >= 4 * F32_BAR and rot >= 4 * F32_BAR
+
+
+def test_identity_mixing_is_the_unmixed_helper():
+  from tests import pathwise_multiaction_oracle as pmo
+  for name in ("I8", "I9"):
+    sy = _system(name, 37)
+    want = pmo.policy_rollout_costs_nd(sy["paths"], sy["drift"], sy["pol"], sy["scale"], sy["shift"], sy["active"], sy["target"],
+                                       sy["precis"], sy["x0"], H6, dt=DT)
+    assert np.abs(want - sy["cost_o"]).max() < 1e-14
+
+
+# ---- CPU 2: the ABI --------------------------------------------------------------------------------------------------------------
+def test_argument_validation_and_sizes_of_the_mixed_entries_without_gpu():
+  lib = _lib.lib()
+  buf = (ctypes.c_char * 64)()
+  p = ctypes.addressof(buf)
+  F64c, F32c = _lib.MM_F64, _lib.MM_F32
+  E_ARG, E_DIM, E_DTYPE, E_WS = -1, -2, -3, -4
+  act = (ctypes.c_int32 * 2)(0, 1)
+  sc = (ctypes.c_double * 4)(2.0, 1.5, 1.0, 1.0)
+  sh = (ctypes.c_double * 4)(-0.5, -0.4, -0.6, 0.0)
+  tbm, tbn, sbw = lib.mm_pathwise_tape_bytes_mixed, lib.mm_pathwise_tape_bytes_nd, lib.mm_pathwise_backward_scratch_bytes_wide
+  # ---- the tape query: Lg = nx is the _nd tape; a smaller Lg shrinks exactly the sample slot and the Jacobian block
+  up = lambda n: (n + 255) // 256 * 256
+  for code, es in ((F64c, 8), (F32c, 4)):
+    for S, H, nx, na, nu in ((37, 6, 5, 2, 2), (300, 5, 6, 2, 1), (37, 6, 4, 0, 2), (8, 3, 3, 1, 1)):
+      nd = nx + na + nu
+      for jac in (0, 1):
+        assert tbm(S, H, nx, na, nu, nx, code, jac) == tbn(S, H, nx, na, nu, code, jac) > 0
+        for Lg in range(1, nx):
+          less = (up(S * nx * es) - up(S * Lg * es)) + (up(H * S * nx * nd * es) - up(H * S * Lg * nd * es) if jac else 0)
+          assert tbm(S, H, nx, na, nu, Lg, code, jac) == tbn(S, H, nx, na, nu, code, jac) - less
+  assert tbm(37, 6, 5, 2, 2, 0, F64c, 1) == 0 and tbm(37, 6, 5, 2, 2, 6, F64c, 1) == 0 and tbm(37, 6, 5, 2, 5, 3, F64c, 1) == 0
+  assert tbm(0, 6, 5, 2, 2, 3, F64c, 1) == 0
+
+  # ---- the forward entry (defaults: nx 5, two angles, two actions, three latents: nd 9)
+  def fwd(nu=2, nx=5, na=2, Lg=3, dtype=F64c, a=act, omega=p, pol=p, pol_bytes=1 << 30, pM=12, scale=sc, shift=sh, x0=p, tape=p,
+          tape_bytes=1 << 40, S=37, W=p, c=p):
+    return lib.mm_pathwise_policy_rollout_mixed(S, 128, 256, dtype, 6, 0.5, nx, na, a, nu, omega, p, p, p, p, p, p, None, p, pol,
+                                                pol_bytes, pM, scale, shift, p, p, x0, p, tape, tape_bytes, 1, None, Lg, W, c)
+  assert fwd(Lg=0) == E_DIM and fwd(Lg=6) == E_DIM and fwd(Lg=-1) == E_DIM         # 1 <= Lg <= nx
+  assert fwd(nu=0) == E_DIM and fwd(nu=5) == E_DIM
+  assert fwd(nx=13, na=2, nu=2) == E_DIM and fwd(nx=14, na=2, nu=1) == E_DIM       # nd = 17
+  assert fwd(pM=257) == E_DIM
+  assert fwd(W=None) == E_ARG
+  assert fwd(omega=None) == E_ARG and fwd(pol=None) == E_ARG and fwd(scale=None) == E_ARG and fwd(x0=None) == E_ARG
+  assert fwd(a=None) == E_ARG and fwd(S=0) == E_ARG and fwd(dtype=7) == E_DTYPE
+  need = tbm(37, 6, 5, 2, 2, 3, F64c, 1)
+  assert need > 0 and fwd(tape_bytes=need - 1) == E_WS                             # every check before the tape's passed
+  assert fwd(tape_bytes=need - 1, c=None) == E_WS                                  # a NULL mix_c is accepted
+  assert fwd(Lg=5, tape_bytes=tbm(37, 6, 5, 2, 2, 5, F64c, 1) - 1) == E_WS         # Lg = nx is taken
+  assert fwd(Lg=5, tape_bytes=need) == E_WS                                        # ... and needs the larger tape
+  assert fwd(tape_bytes=need, pol_bytes=64) == E_WS
+  assert fwd(nx=12, na=2, nu=2, Lg=1, tape_bytes=tbm(37, 6, 12, 2, 2, 1, F64c, 1) - 1) == E_WS   # nd 16, one latent
+
+  # ---- the backward entry (the _seeded signature + Lg, mix_W)
+  def bwd(nu=2, nx=5, na=2, Lg=3, dtype=F64c, a=act, pol=p, pol_bytes=1 << 30, pM=12, scale=sc, shift=sh, tape=p,
+          tape_bytes=1 << 40, g_cost=p, g_x=p, g_pol=p, scratch=p, scratch_bytes=1 << 40, W=p):
+    return lib.mm_pathwise_policy_rollout_backward_mixed(37, dtype, 6, 0.5, nx, na, a, nu, pol, pol_bytes, pM, scale, shift, p, p,
+                                                         tape, tape_bytes, g_cost, g_x, g_pol, None, scratch, scratch_bytes, None,
+                                                         Lg, W)
+  assert bwd(Lg=0) == E_DIM and bwd(Lg=6) == E_DIM
+  assert bwd(nu=0) == E_DIM and bwd(nu=5) == E_DIM and bwd(nx=13, na=2, nu=2) == E_DIM and bwd(pM=257) == E_DIM
+  assert bwd(nx=10, na=2, nu=4, pM=78) == E_DIM                                    # ne 12, nu 4, M 78: beyond the LDS bound
+  assert bwd(W=None) == E_ARG
+  assert bwd(pol=None) == E_ARG and bwd(tape=None) == E_ARG and bwd(scratch=None) == E_ARG and bwd(g_pol=None) == E_ARG
+  assert bwd(g_cost=None, g_x=None) == E_ARG                                       # either seed may be NULL, not both
+  assert bwd(dtype=7) == E_DTYPE
+  assert bwd(tape_bytes=need - 1) == E_WS and bwd(tape_bytes=need - 1, g_cost=None) == E_WS and bwd(tape_bytes=need - 1, g_x=None) == E_WS
+  assert sbw(37, 12, 7, 2) > 0 and bwd(tape_bytes=need, scratch_bytes=sbw(37, 12, 7, 2) - 1) == E_WS
+  assert bwd(nx=10, na=2, nu=4, Lg=2, pM=77, tape_bytes=tbm(37, 6, 10, 2, 4, 2, F64c, 1) - 1) == E_WS   # the LDS edge is taken
+  assert lib.mm_abi_version() == 2
+
+
+# ---- CPU 3: routing of the option ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["M2", "X"])
+def test_closure_on_cpu_tensors_accepts_native_coregionalized(name):
+  """On CPU tensors the closure runs the torch composition whatever native_coregionalized says: the helper's numbers, for
+  Lg < nx and for Lg > nx alike; native=True without the option raises on the coregionalised drift."""
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  sy = _system(name, 37)
+  system, objective, _ = _torch_system(sy, "cpu")
+  x0 = torch.tensor(sy["x0"], dtype=F64)
+  tp = _TorchMixedPaths(sy)
+  with torch.no_grad(), warnings.catch_warnings():
+    warnings.simplefilter("error")
+    l_def = pathwise_policy_loss_closure(system, objective, lambda: x0, H6, dt=DT, paths=tp)()
+    l_on = pathwise_policy_loss_closure(system, objective, lambda: x0, H6, dt=DT, paths=tp, native_actions=4, native_inputs=16,
+                                        native_coregionalized=True)()
+  assert torch.equal(l_def, l_on)
+  assert scale_err(l_on, sy["cost_o"].sum(0)) < 1e-10
+  with pytest.raises(ValueError, match="LinearCoregionalization"):
+    pathwise_policy_loss_closure(system, objective, lambda: x0, H6, dt=DT, paths=tp, native=True, native_actions=4)
+  if name == "X":
+    with pytest.raises(ValueError, match=r"Lg = 4 > nx = 3"):
+      pathwise_policy_loss_closure(system, objective, lambda: x0, H6, dt=DT, paths=tp, native=True, native_coregionalized=True)
+  else:
+    pathwise_policy_loss_closure(system, objective, lambda: x0, H6, dt=DT, paths=tp, native=True, native_actions=4,
+                                 native_coregionalized=True)
+
+
+def test_every_refused_wiring_has_its_own_reason():
+  from gpflowpilco_amd import models as gp
+  from gpflowpilco_amd.loops import _native_parts, _pathwise_mixing_obstacle
+  sy = _system("M2", 37)
+  system, objective, pm = _torch_system(sy, "cpu")
+  drift = system.drift
+  reasons = []
+
+  def refusal(sysm, **kw):
+    why = []
+    out = _native_parts(sysm, objective, why, moment_solver=False, **kw)
+    assert (out is None) == (len(why) == 1)
+    return why[0] if why else None
+  assert refusal(system) == "a LinearCoregionalization kernel (its mixing stays on the host)"    # today's reason, option off
+  assert refusal(system, coregionalized=True) is None
+  # a coregionalised policy
+  pol_sys = copy.copy(system)
+  pol_model = gp_model_from_oracle(sy["pol"], "cpu")
+  pol_model.kernel = gp.LinearCoregionalization(pol_model.kernel.kernels, torch.eye(2, dtype=F64))
+  pol_sys.policy = gp.InverseLinkWrapper(gp.KernelRegressor(pol_model), invlink=system.policy.invlink)
+  reasons.append(refusal(pol_sys, coregionalized=True))
+  assert "coregionalised policy" in reasons[-1]
+  # more latents than outputs
+  sx = _system("X", 37)
+  reasons.append(refusal(_torch_system(sx, "cpu")[0], coregionalized=True))
+  assert "Lg = 4 > nx = 3" in reasons[-1]
+  # the paths of the call
+  good = _TorchMixedPaths(sy)
+  assert _pathwise_mixing_obstacle(drift, good, True) is None
+  reasons.append(_pathwise_mixing_obstacle(drift, tm._TorchPaths(sy["paths"], sy["drift"]), False))
+  assert "carry no mixing" in reasons[-1]
+  other = _TorchMixedPaths(sy)
+  other.mix_W = other.mix_W[:, :2]
+  reasons.append(_pathwise_mixing_obstacle(drift, other, False))
+  assert "another shape" in reasons[-1]
+  no_c = _TorchMixedPaths(sy)
+  no_c.mix_c = None
+  assert "another shape" in _pathwise_mixing_obstacle(drift, no_c, False)
+  # a W or a mean that requires a gradient (only where a gradient is being taken)
+  drift.kernel.W.requires_grad_(True)
+  assert _pathwise_mixing_obstacle(drift, good, False) is None
+  reasons.append(_pathwise_mixing_obstacle(drift, good, True))
+  assert "W requires a gradient" in reasons[-1]
+  drift.kernel.W.requires_grad_(False)
+  drift.mean_function.c.requires_grad_(True)
+  reasons.append(_pathwise_mixing_obstacle(drift, good, True))
+  assert "mean requires a gradient" in reasons[-1]
+  assert len(set(reasons)) == len(reasons) == 6
+
+
+def test_policy_rollout_refuses_more_latents_than_states_and_a_mixing_of_the_wrong_shape():
+  from gpflowpilco_amd.pathwise import PolicyRollout
+
+  class _Paths:
+    num_samples, dtype = 8, F64
+    def __init__(self, L, d, W): self.L, self.d, self.mix_W, self.mix_c = L, d, W, None
+    def _dims(self): return 8, self.L, 128, 128, self.d
+
+  class _Pack:
+    def __init__(self, L, d): self.L, self.M, self.d = L, 12, d
+  kw = dict(nx=4, active_dims=(1,), head_scale=1.0, head_shift=0.0, target=None, precis=None)
+  with pytest.raises(ValueError, match=r"Lg <= nx"):
+    PolicyRollout(_Paths(5, 6, torch.zeros(4, 5, dtype=F64)), _Pack(1, 5), **kw)
+  with pytest.raises(ValueError, match=r"mix_W \(4, 3\)"):
+    PolicyRollout(_Paths(2, 6, torch.zeros(4, 3, dtype=F64)), _Pack(1, 5), **kw)
+  with pytest.raises(ValueError, match=r"mix_W \(3, 2\)"):
+    PolicyRollout(_Paths(2, 6, torch.zeros(3, 2, dtype=F64)), _Pack(1, 5), **kw)
+  with pytest.raises(ValueError, match=r"<= 16"):                                  # the mixed family's own bound on nd
+    PolicyRollout(_Paths(3, 17, torch.zeros(12, 3, dtype=F64)), _Pack(4, 13), nx=12, active_dims=(0,), head_scale=1.0,
+                  head_shift=0.0, target=None, precis=None)
+
+
+def test_paths_from_arrays_checks_the_mixing():
+  from gpflowpilco_amd.pathwise import paths_from_arrays
+  sy = _system("M1", 37)
+  P, dr = sy["paths"], sy["drift"]
+  args = (P.omega, P.phase, P.w, P.v, dr.Z, dr.lengthscales, dr.variance)
+  p = paths_from_arrays(*args, None, dtype=F64, device="cpu", mix_W=sy["W"], mix_c=sy["c"])
+  assert p.mix_W.shape == (4, 2) and p.mix_c.shape == (4,) and p.mean_c is None and p.mix_W.dtype == F64
+  assert paths_from_arrays(*args, None, dtype=F64, device="cpu").mix_W is None
+  with pytest.raises(ValueError, match="no latent mean"):
+    paths_from_arrays(*args, np.zeros(2), dtype=F64, device="cpu", mix_W=sy["W"])
+  with pytest.raises(ValueError, match="mix_W must be"):
+    paths_from_arrays(*args, None, dtype=F64, device="cpu", mix_W=sy["W"].T)
+  with pytest.raises(ValueError, match="drift-only"):
+    p.rollout(torch.zeros(37, 6, dtype=F64), 2)
+
+
+# ---- GPU 1: mixed Paths -----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _paths_case(name):
+  """Inputs for the paths of a system and the helper's values: f, and J by central differences (h = 1e-6)."""
+  sy = _system(name, 37)
+  x = np.random.default_rng(sy["seed"] + 5).uniform(0.2, 0.8, size=(37, sy["nd"]))
+  ev = lambda y: pmx.mixed_eval(sy["paths"], sy["drift"], sy["W"], sy["c"], y)
+  fo = ev(x)
+  Jo = np.empty((37, sy["nx"], sy["nd"]))
+  h = 1e-6
+  for k in range(sy["nd"]):
+    dx = np.zeros(sy["nd"]); dx[k] = h
+    Jo[:, :, k] = (ev(x + dx) - ev(x - dx)) / (2 * h)
+  return sy, x, fo, Jo
+
+
+@pytest.mark.parametrize("name", ["M2", "M3", "I8", "I9"])
+def test_central_differences_of_the_helper_are_a_reference_for_the_f64_bar(name):
+  """The reference of the GPU Jacobian test against the closed-form Jacobian W J_g of the same numpy paths: a quarter of the 1e-7
+  bar it serves."""
+  sy, x, _, Jo = _paths_case(name)
+  Ja = np.einsum('il,sld->sid', sy["W"], tw._analytic_jacobian(sy["paths"], sy["drift"], x))
+  e = scale_err(Ja, Jo)
+  print(f"central differences {name}: {e:.3e} of max |J| from the closed form; |v| < {np.abs(sy['paths'].v).max():.1f}")
+  assert e < 2.5e-8
+
+
+@functools.lru_cache(maxsize=None)
+def _unmixed_f32_paths_error(name, device):
+  """(f, J) f32 errors of the unmixed paths of the same recipe (the identity system through the plain entries), same process."""
+  sy, x, fo, Jo = _paths_case(UNMIXED_OF[name])
+  f, J = _device_paths(sy, device, torch.float32, mixed=False).eval_jac(torch.tensor(x, dtype=torch.float32, device=device))
+  return scale_err(f, fo), scale_err(J, Jo)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("name", ["M2", "M3"])
+def test_gpu_mixed_paths_values_jacobian_autograd_and_bound(name, dtype, device):
+  """__call__ / eval_jac against the helper (J against its central differences); autograd through Paths.__call__ gives J's
+  column sums; eval_with_bound's bound |W| err_g holds for every value of this dtype."""
+  sy, x, fo, Jo = _paths_case(name)
+  gp_paths = _device_paths(sy, device, dtype)
+  xt = torch.tensor(x, dtype=dtype, device=device)
+  f, J = gp_paths.eval_jac(xt)
+  assert f.shape == (37, sy["nx"]) and J.shape == (37, sy["nx"], sy["nd"]) and f.dtype == dtype and J.dtype == dtype
+  assert torch.equal(f, gp_paths(xt))
+  ef, eJ = scale_err(f, fo), scale_err(J, Jo)
+  tag = "f64" if dtype == torch.float64 else "f32"
+  print(f"mixed paths {name} {tag}: f {ef:.3e} J {eJ:.3e}")
+  barf, barJ = (1e-11, 1e-7) if dtype == torch.float64 else (2e-3, 3e-3)
+  if dtype == torch.float32 and (ef >= barf or eJ >= barJ):
+    uf, uJ = _unmixed_f32_paths_error(name, str(device))
+    print(f"  unmixed paths of the same recipe, f32, same process: f {uf:.3e} J {uJ:.3e}")
+    barf, barJ = max(barf, 2 * uf), max(barJ, 2 * uJ)
+  assert ef < barf and eJ < barJ
+  xg = xt.clone().requires_grad_(True)
+  fg = gp_paths(xg)
+  assert torch.equal(fg.detach(), f)
+  (gx,) = torch.autograd.grad(fg.sum(), xg)
+  assert scale_err(gx, J.double().sum(1).cpu().numpy()) < (1e-13 if dtype == torch.float64 else 1e-6)
+  fb, err = gp_paths.eval_with_bound(xt)
+  assert torch.equal(fb, f) and err.shape == f.shape
+  slack = np.abs(fb.double().cpu().numpy() - fo) / (err.double().cpu().numpy() + 1e-300)
+  print(f"  observed error / bound: max {slack.max():.3f}")
+  if dtype == torch.float32:                    # (f64: the mixing's own few-ulp rounding is of the bound's order; printed only)
+    assert np.all(slack <= 1.0)
+
+
+# ---- GPU 2: forward ---------------------------------------------------------------------------------------------------------------
+def _forward_errors(sy, roll, dtype, device):
+  x0 = torch.tensor(sy["x0"], dtype=dtype, device=device)
+  cost, tape = roll(x0, H6, dt=DT, with_jacobians=False)
+  cost_j, tape_j = roll(x0, H6, dt=DT, with_jacobians=True)
+  assert tape.numel() < tape_j.numel()
+  assert torch.equal(cost, cost_j) and torch.equal(roll.states(tape, H6), roll.states(tape_j, H6))
+  assert torch.equal(x0, torch.tensor(sy["x0"], dtype=dtype, device=device))           # the input is not modified
+  return scale_err(cost, sy["cost_o"]), scale_err(roll.states(tape, H6), sy["states_o"])
+
+
+@functools.lru_cache(maxsize=None)
+def _unmixed_f32_forward_error(name, S, device):
+  sy = _system(UNMIXED_OF[name], S)
+  return max(_forward_errors(sy, _device_case(sy, device, torch.float32, mixed=False)[2], torch.float32, device))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [37, 300])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("name", MIXED)
+def test_gpu_mixed_rollout_costs_and_states_match_the_helper(name, dtype, S, device):
+  sy = _system(name, S)
+  _, _, roll = _device_case(sy, device, dtype)
+  assert roll.mixed and roll.Lg == sy["Lg"] and roll.nu == sy["nu"] and roll.nd == sy["nd"] and roll.nd_entries
+  ec, es = _forward_errors(sy, roll, dtype, device)
+  print(f"mixed forward {name} S={S} {dtype}: cost {ec:.3e} states {es:.3e}")
+  tol = F64_BAR if dtype == torch.float64 else F32_BAR
+  if dtype == torch.float32 and max(ec, es) >= tol:
+    un = _unmixed_f32_forward_error(name, S, str(device))
+    print(f"  unmixed system {UNMIXED_OF[name]} of the same recipe, f32, same process: {un:.3e}")
+    tol = max(tol, 2 * un)
+  assert ec < tol and es < tol
+
+
+# ---- GPU 3: the identity mixing against the unmixed entries ------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["I8", "I9"])
+def test_gpu_identity_mixing_agrees_with_the_unmixed_entries(name, device):
+  """W = I, c = None, Lg = nx on the same paths: the _mixed entries against _nd (nd 8) / _wide (nd 9) within 1e-13 of scale --
+  the mixed step is fma(1, g_i, 0) plus exact zeros, so bit equality is expected and printed, not asserted."""
+  sy = _system(name, 37)
+  S = 37
+  _, _, rollm = _device_case(sy, device, F64, mixed=True)
+  _, _, rollu = _device_case(sy, device, F64, mixed=False)
+  assert rollm.mixed and not rollu.mixed and rollu.wide == (sy["nd"] > 8)
+  x0 = torch.tensor(sy["x0"], dtype=F64, device=device)
+  g_cost = torch.randn(H6, S, dtype=F64, generator=torch.Generator(device="cpu").manual_seed(7)).to(device)
+  cm, tpm = rollm(x0, H6, dt=DT, with_jacobians=True)
+  cu, tpu = rollu(x0, H6, dt=DT, with_jacobians=True)
+  assert tpm.numel() == tpu.numel()
+  gpm, gxm = rollm.backward(tpm, g_cost, H6, dt=DT, want_state_grad=True)
+  gpu_, gxu = rollu.backward(tpu, g_cost, H6, dt=DT, want_state_grad=True)
+  pairs = {"cost": (cm, cu), "states": (rollm.states(tpm, H6), rollu.states(tpu, H6)), "g_policy": (gpm, gpu_), "g_x0": (gxm, gxu)}
+  for k, (a, b) in pairs.items():
+    e = float((a - b).abs().max()) / max(1e-300, float(b.abs().max()))
+    print(f"identity mixing {name} {k}: {e:.2e} of scale, bit-equal: {torch.equal(a, b)}")
+    assert a.shape == b.shape and float(b.abs().max()) > 0.0 and e < 1e-13
+  assert scale_err(cm, sy["cost_o"]) < F64_BAR
+
+
+# ---- GPU 4: gradient ----------------------------------------------------------------------------------------------------------------
+def _mirror(sy, pm, x0, H, device):
+  """The same composition in differentiable torch ops on the path arrays -> (cost [S, H], states x_1 .. x_H [H, S, nx])."""
+  P, dr = sy["paths"], sy["drift"]
+  nx, nu, active, Lg = sy["nx"], sy["nu"], sy["active"], sy["Lg"]
+  tt = lambda a: torch.tensor(np.asarray(a), dtype=F64, device=device)
+  om, ph, w, v = tt(P.omega), tt(P.phase), tt(P.w), tt(P.v)
+  Zd, lsd, vard = tt(dr.Z), tt(dr.lengthscales), tt(dr.variance)
+  W, c = tt(sy["W"]), (None if sy["c"] is None else tt(sy["c"]))
+  target, precis = tt(sy["target"]), tt(sy["precis"])
+  inactive = [i for i in range(nx) if i not in active]
+  enc = lambda y: torch.cat([torch.sin(y[:, list(active)]), torch.cos(y[:, list(active)]), y[:, inactive]], dim=-1)
+  Zp, lsp, varp, betap, _, mcp = pm.precompute(device)
+  x, costs, states = x0, [], []
+  for _ in range(H):
+    e = enc(x)
+    us = []
+    for a in range(nu):
+      r2 = (((e[:, None, :] - Zp[a][None]) / lsp[a]) ** 2).sum(-1)
+      fp = (varp[a] * torch.exp(-0.5 * r2)) @ betap[a] + mcp[a]
+      us.append(float(sy["scale"][a]) * (0.5 * torch.erfc(-fp / np.sqrt(2.0)) + float(sy["shift"][a])))
+    dd = torch.cat([e, torch.stack(us, dim=-1)], dim=-1)
+    g = []
+    for a in range(Lg):
+      phi = torch.sqrt(2.0 * vard[a] / om.shape[1]) * torch.cos(dd @ om[a].T + ph[a][None])
+      kk = vard[a] * torch.exp(-0.5 * (((dd[:, None, :] - Zd[a][None]) / lsd[a]) ** 2).sum(-1))
+      g.append((w[:, a] * phi).sum(-1) + (v[:, a] * kk).sum(-1))
+    f = torch.stack(g, dim=-1) @ W.T
+    x = x + DT * (f if c is None else f + c)
+    err = enc(x) - target
+    costs.append(-torch.exp(-0.5 * ((err @ precis) * err).sum(-1)))
+    states.append(x)
+  return torch.stack(costs, dim=1), torch.stack(states)
+
+
+def _grad_case(sy, device):
+  _, pm, roll = _device_case(sy, device, F64)
+  assert roll.supports_backward()
+  groups = tm._policy_params(pm, sy["nu"])
+  flat = [t for ts in groups.values() for t in ts]
+  for t in flat:
+    t.requires_grad_(True)
+  x0 = torch.tensor(sy["x0"], dtype=F64, device=device, requires_grad=True)
+  return pm, roll, groups, flat, x0
+
+
+def _grads(loss, groups, x0):
+  for ts in list(groups.values()) + [[x0]]:
+    for t in ts:
+      t.grad = None
+  loss.backward()
+  out = {k: [t.grad.detach().clone() for t in ts] for k, ts in groups.items()}
+  out["x0"] = [x0.grad.detach().clone()]
+  return out
+
+
+def _compare_grads(tag, got, want):
+  for k in want:
+    for a, (g, r) in enumerate(zip(got[k], want[k])):
+      err = float((g - r).abs().max()) / max(1e-14, float(r.abs().max()))
+      print(f"{tag} {k}[{a}]: native vs torch mirror {err:.2e}")
+      assert float(r.abs().max()) > 0.0 and err < 1e-8, (k, a, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,S", [("M1", 37), ("M2", 37), ("M3", 37), ("M4", 37), ("M5", 37), ("M3", 300)])
+def test_gpu_mixed_gradient_of_the_mean_sample_loss(name, S, device):
+  """d mean_s sum_h cost / d (q_mu, Z, lengthscales, variance of every latent, x0) through PolicyRolloutFunction on the mixed
+  entries, f64, H = 5: (i) torch autograd of a torch mirror, 1e-8 relative per tensor; (ii) central differences (h = 1e-6) of
+  the numpy helper along one random direction per parameter group and for x0, 1e-6 max(1, |fd|); two sweeps on one tape are
+  bit-equal."""
+  from gpflowpilco_amd.pathwise import PolicyRolloutFunction
+  sy = _system(name, S)
+  H, nu = 5, sy["nu"]
+  pm, roll, groups, flat, x0 = _grad_case(sy, device)
+  Zp, lsp, varp, betap, _, mcp = pm.precompute(device)
+  loss = PolicyRolloutFunction.apply(x0, Zp, lsp, varp, betap, mcp, roll, H, DT).sum(1).mean()
+  g_native = _grads(loss, groups, x0)
+  assert abs(float(loss.detach()) - sy["cost_o"][:H].sum(0).mean()) < 1e-10
+  lm = _mirror(sy, pm, x0, H, device)[0].sum(1).mean()
+  g_mirror = _grads(lm, groups, x0)
+  assert abs(float(lm.detach()) - float(loss.detach())) < 1e-10
+  _compare_grads(f"mixed gradient {name} S={S}", g_native, g_mirror)
+
+  rng = np.random.default_rng(5)
+  oracle_loss = lambda pol, x_init: _oracle(sy, H, pol=pol, x0=x_init).sum(0).mean()
+  h = 1e-6
+  for field in ("q_mu", "Z", "lengthscales", "variance"):
+    base = np.asarray(getattr(sy["pol"], field), dtype=np.float64)
+    dirn = rng.standard_normal(base.shape)
+    vals = []
+    for sgn in (1.0, -1.0):
+      pol2 = copy.deepcopy(sy["pol"])
+      setattr(pol2, field, base + sgn * h * dirn)
+      vals.append(oracle_loss(pol2, sy["x0"]))
+    fd = (vals[0] - vals[1]) / (2 * h)
+    gn = g_native[field]
+    got = gn[0].cpu().numpy() if field == "q_mu" else np.stack([t.cpu().numpy().reshape(base.shape[1:]) for t in gn])
+    an = float((got.reshape(base.shape) * dirn).sum())
+    print(f"mixed gradient {name} S={S} {field}: native {an:+.8e} fd {fd:+.8e}")
+    assert abs(fd - an) < 1e-6 * max(1.0, abs(fd)), (field, fd, an)
+  dirx = rng.standard_normal(sy["x0"].shape)
+  fd = (oracle_loss(sy["pol"], sy["x0"] + h * dirx) - oracle_loss(sy["pol"], sy["x0"] - h * dirx)) / (2 * h)
+  an = float((g_native["x0"][0].cpu().numpy() * dirx).sum())
+  assert abs(fd - an) < 1e-6 * max(1.0, abs(fd)), ("x0", fd, an)
+
+  with torch.no_grad():
+    _, tape = roll(x0.detach(), H, dt=DT, with_jacobians=True)
+    g_cost = torch.full((H, S), 1.0 / S, dtype=F64, device=device)
+    a1, b1 = roll.backward(tape, g_cost, H, dt=DT, want_state_grad=True)
+    a2, b2 = roll.backward(tape, g_cost, H, dt=DT, want_state_grad=True)
+  assert a1.shape == (nu, 12 * sy["ne"] + 12 + sy["ne"] + 2) and torch.equal(a1, a2) and torch.equal(b1, b2)
+
+
+@pytest.mark.gpu
+def test_gpu_mixed_seeded_sweep_of_a_quadratic_objective_of_the_states(device):
+  """M2 through PolicyTrajectoryFunction: a quadratic objective of x_1 .. x_H alone (g_cost NULL), and together with the built-in
+  cost (g_cost and g_x in one sweep), against the torch mirror."""
+  from gpflowpilco_amd.pathwise import PolicyTrajectoryFunction
+  sy = _system("M2", 37)
+  H = 5
+  pm, roll, groups, flat, x0 = _grad_case(sy, device)
+  Q = torch.rand(H, 1, sy["nx"], dtype=F64, generator=torch.Generator(device="cpu").manual_seed(3)).to(device)
+  quad = lambda xs: (0.5 * Q * (xs - 0.3) ** 2).sum((0, 2)).mean()
+
+  def native():
+    Zp, lsp, varp, betap, _, mcp = pm.precompute(device)
+    return PolicyTrajectoryFunction.apply(x0, Zp, lsp, varp, betap, mcp, roll, H, DT)
+  cost, xs = native()
+  assert xs.shape == (H, 37, sy["nx"]) and scale_err(xs, sy["states_o"][1:H + 1]) < F64_BAR
+  g_states_only = _grads(quad(xs), groups, x0)
+  cost, xs = native()
+  g_both = _grads(quad(xs) + cost.sum(1).mean(), groups, x0)
+  mc, mx = _mirror(sy, pm, x0, H, device)
+  m_states_only = _grads(quad(mx), groups, x0)
+  mc, mx = _mirror(sy, pm, x0, H, device)
+  m_both = _grads(quad(mx) + mc.sum(1).mean(), groups, x0)
+  _compare_grads("mixed seeded sweep M2, states alone", g_states_only, m_states_only)
+  _compare_grads("mixed seeded sweep M2, states and cost", g_both, m_both)
+
+
+# ---- GPU 5: the closure -------------------------------------------------------------------------------------------------------------
+def _closure_case(sy, device, S, nbases=256, seed=3):
+  system, objective, pm = _torch_system(sy, device)
+  params = [t for ts in tm._policy_params(pm, sy["nu"]).values() for t in ts]
+  for t in params:
+    t.requires_grad_(True)
+  g = torch.Generator(device=device).manual_seed(seed)
+  x0 = torch.tensor(sy["x0"][:S], dtype=F64, device=device, requires_grad=True)
+  paths = system.drift.generate_paths(S, nbases, dtype=F64, device=device, generator=g)
+  return system, objective, pm, params, x0, paths
+
+
+def _run_closure(params, x0, system, objective, H, **kw):
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  for t in params + [x0]:
+    t.grad = None
+  loss = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=DT, **kw)()
+  loss.mean().backward()
+  return loss.detach(), [t.grad.detach().clone() for t in params + [x0]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["M3", "M4"])
+def test_gpu_closure_runs_a_coregionalised_drift_natively_when_asked(name, device):
+  """M3 (nd 9: native_inputs=16) and M4 (no encoder: native_no_encoder, two actions): the native result against native=False
+  at 1e-10 (loss) and 1e-8 (gradients), silently; the default warns once with today's reason and returns the torch composition's
+  numbers."""
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  sy = _system(name, 37)
+  S, H = 37, 5
+  system, objective, pm, params, x0, paths = _closure_case(sy, device, S)
+  assert paths.mix_W.shape == (sy["nx"], sy["Lg"]) and paths.mix_c.shape == (sy["nx"],) and paths.mean_c is None
+  assert paths._dims()[1] == sy["Lg"]
+  on = dict(native_coregionalized=True, native_inputs=16, native_actions=4, native_no_encoder=True)
+  with warnings.catch_warnings():
+    warnings.simplefilter("error")
+    ln, gn = _run_closure(params, x0, system, objective, H, paths=paths, **on)
+    lf, _ = _run_closure(params, x0, system, objective, H, paths=paths, native=True, **on)
+    lt, gt = _run_closure(params, x0, system, objective, H, paths=paths, native=False)
+    with torch.no_grad():
+      l0 = pathwise_policy_loss_closure(system, objective, lambda: x0.detach(), H, dt=DT, paths=paths, **on)()
+  assert ln.shape == (S,) and torch.equal(ln, lf)
+  el = float((ln - lt).abs().max())
+  print(f"closure {name}: native vs torch composition, loss {el:.2e}")
+  assert el < 1e-10 and float((l0 - ln).abs().max()) < 1e-12
+  for a_, b_ in zip(gn, gt):
+    eg = float((a_ - b_).abs().max()) / max(1e-12, float(b_.abs().max()))
+    assert float(b_.abs().max()) > 0.0 and eg < 1e-8, eg
+  # the default stays today's routing and reason; the fallback now runs on mixed paths
+  off = {k: v for k, v in on.items() if k != "native_coregionalized"}
+  closure = pathwise_policy_loss_closure(system, objective, lambda: x0.detach(), H, dt=DT, paths=paths, **off)
+  with torch.no_grad():
+    with pytest.warns(RuntimeWarning, match=r"a LinearCoregionalization kernel \(its mixing stays on the host\)") as rec:
+      ld = closure()
+    assert len([w for w in rec if issubclass(w.category, RuntimeWarning)]) == 1
+    with warnings.catch_warnings():
+      warnings.simplefilter("error")
+      assert torch.equal(closure(), ld)                                              # once: the second call is silent
+  assert torch.equal(ld, lt)
+
+
+@pytest.mark.gpu
+def test_gpu_closure_names_each_refused_wiring_once_and_returns_the_torch_numbers(device):
+  """Lg > nx (system X), given paths whose mixing has another shape than the drift's (no constant), and a W that requires a
+  gradient: one named warning each, the torch composition's numbers; for X these are the helper's (the composition is correct
+  for any Lg).  (Paths without any mixing cannot be run against this drift at all -- they return Lg columns for nx states; their
+  reason is checked without a GPU.)"""
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  from gpflowpilco_amd.pathwise import paths_from_arrays
+  S, H = 37, 5
+  on = dict(native_coregionalized=True, native_inputs=16, native_actions=4)
+
+  def once(closure, pattern):
+    with pytest.warns(RuntimeWarning, match=pattern) as rec:
+      out = closure()
+    assert len([w for w in rec if issubclass(w.category, RuntimeWarning)]) == 1
+    with warnings.catch_warnings():
+      warnings.simplefilter("error")
+      closure()
+    return out
+  sx = _system("X", S)
+  system, objective, _ = _torch_system(sx, device)
+  xx = torch.tensor(sx["x0"], dtype=F64, device=device)
+  px = _device_paths(sx, device, F64)
+  with torch.no_grad():
+    lx = once(pathwise_policy_loss_closure(system, objective, lambda: xx, H6, dt=DT, paths=px, **on), r"Lg = 4 > nx = 3")
+  assert scale_err(lx, sx["cost_o"].sum(0)) < F64_BAR
+
+  sy = _system("M2", S)
+  system, objective, pm, params, x0, paths = _closure_case(sy, device, S)
+  lt, gt = _run_closure(params, x0, system, objective, H, paths=paths, native=False)
+  P, dr = sy["paths"], sy["drift"]
+  bare = paths_from_arrays(P.omega, P.phase, P.w, P.v, dr.Z, dr.lengthscales, dr.variance, None, dtype=F64, device=device,
+                           mix_W=sy["W"])                                           # no constant, where the drift has one
+  with torch.no_grad():
+    once(pathwise_policy_loss_closure(system, objective, lambda: x0.detach(), H, dt=DT, paths=bare, **on), r"another shape")
+  system.drift.kernel.W.requires_grad_(True)
+  closure = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=DT, paths=paths, **on)
+  lw = once(closure, r"W requires a gradient")
+  assert torch.equal(lw.detach(), lt)
+  with torch.no_grad(), warnings.catch_warnings():                                 # nothing differentiates: W is a constant, native
+    warnings.simplefilter("error")
+    l0 = pathwise_policy_loss_closure(system, objective, lambda: x0.detach(), H, dt=DT, paths=paths, **on)()
+  assert float((l0 - lt).abs().max()) < 1e-10
+
+
+def _numpy_paths_of(sampler):
+  """The draw in a PathSampler's buffers as the numpy helper's Paths (omega = n / ls, phase = b, w, v = rhs [L, M, S])."""
+  B = sampler.buffers
+  omega = (B["n"] / sampler._ls[:, None, :]).cpu().numpy()
+  return pw.Paths(omega=omega, phase=B["b"].cpu().numpy(), w=B["w"].cpu().numpy(), v=B["rhs"].permute(2, 0, 1).cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_gpu_closure_with_native_sampler_draws_mixed_paths_and_follows_w(device):
+  """native_sampler=True on M3: the same generator state gives generate_paths's loss (to the rounding of the update weights, as in
+  tests/test_path_sampler.py: 1e-7 of the loss); the loss is the helper's on the sampler's own draw; after an in-place change of W
+  the next draw's loss is the helper's for the new W."""
+  from gpflowpilco_amd.loops import pathwise_policy_loss_closure
+  from gpflowpilco_amd.pathwise import PathSampler
+  sy = _system("M3", 37)
+  S, H, K = 37, 5, 256
+  system, objective, pm, params, x0, _ = _closure_case(sy, device, S)
+  drift = system.drift
+  on = dict(native_coregionalized=True, native_inputs=16, num_bases=K)
+  gen = torch.Generator(device=device)
+  x0d = x0.detach()
+
+  def helper_loss(W):
+    ref = PathSampler(drift, S, K, dtype=F64, device=device)
+    ref.draw(torch.Generator(device=device).manual_seed(17))
+    torch.cuda.synchronize()
+    return pmx.policy_rollout_costs_mixed(_numpy_paths_of(ref), sy["drift"], W, sy["c"], sy["pol"], sy["scale"], sy["shift"],
+                                          sy["active"], sy["target"], sy["precis"], sy["x0"], H, dt=DT).sum(0)
+  with warnings.catch_warnings():
+    warnings.simplefilter("error")
+    sampled = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=DT, generator=gen, native_sampler=True, **on)
+    gen.manual_seed(17)
+    la = sampled()
+    la.mean().backward()
+    assert all(float(t.grad.abs().max()) > 0.0 for t in params)
+    gen.manual_seed(17)
+    with torch.no_grad():
+      lg = pathwise_policy_loss_closure(system, objective, lambda: x0d, H, dt=DT, generator=gen, **on)()
+      gen.manual_seed(17)
+      lt = pathwise_policy_loss_closure(system, objective, lambda: x0d, H, dt=DT, generator=gen, native=False, native_sampler=True,
+                                        num_bases=K)()
+  la = la.detach()
+  print(f"sampler against generate_paths, same seed: max |dloss| = {float((lg - la).abs().max()):.2e}; against the torch "
+        f"composition on the sampler's draw {float((lt - la).abs().max()):.2e}")
+  assert float((lg - la).abs().max()) < 1e-7 * float(lg.abs().max()) and float((lt - la).abs().max()) < 1e-10
+  want = helper_loss(sy["W"])
+  assert scale_err(la, want) < F64_BAR
+  # W changes in place: the sampler's cache key covers it, the next draw carries the new mixing
+  W2 = np.random.default_rng(9).standard_normal(sy["W"].shape)
+  W2 = W2 / np.linalg.norm(W2, axis=-1, keepdims=True)
+  with torch.no_grad():
+    drift.kernel.W.copy_(torch.tensor(W2, dtype=F64, device=device))
+    gen.manual_seed(17)
+    with warnings.catch_warnings():
+      warnings.simplefilter("error")
+      lb = sampled()
+  want2 = helper_loss(W2)
+  print(f"after W changed in place: loss moved by {float((lb - la).abs().max()):.2e}, from the helper's new value "
+        f"{scale_err(lb, want2):.2e}")
+  assert scale_err(lb, want2) < F64_BAR and np.abs(want2 - want).max() > 1e-3
+
+
+# ---- GPU 6: capture -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_mixed_forward_replays_bit_equal_under_graph_capture(device):
+  sy = _system("M1", 37)
+  _, _, roll = _device_case(sy, device, F64)
+  x0 = torch.tensor(sy["x0"], dtype=F64, device=device)
+  dev = x0.device
+  eager, _ = roll(x0, H6, dt=DT)
+  side = torch.cuda.Stream(device=dev)
+  side.wait_stream(torch.cuda.current_stream(dev))
+  with torch.cuda.stream(side):
+    roll(x0, H6, dt=DT)
+  torch.cuda.current_stream(dev).wait_stream(side)
+  torch.cuda.synchronize(dev)
+  graph = torch.cuda.CUDAGraph()
+  with torch.cuda.graph(graph):
+    cost, _ = roll(x0, H6, dt=DT)
+  for _ in range(2):
+    cost.zero_()
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert torch.equal(cost, eager)
+  assert scale_err(cost, sy["cost_o"]) < F64_BAR
