@@ -231,6 +231,15 @@ SIGNATURES = {
                                                   + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
                                                   + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
                                                   + [C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int, C.c_void_p]),
+    "mm_pathwise_eval_kern": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 12 + [C.c_int]),
+    "mm_pathwise_rollout_kern": (C.c_int, [C.c_int] * 7 + [C.c_double] + [C.c_void_p] * 13 + [C.c_int]),
+    "mm_pathwise_eval_jac_kern": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_int]),
+    "mm_pathwise_eval_bound_kern": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_int]),
+    "mm_pathwise_policy_rollout_kern": (C.c_int, [C.c_int] * 5 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                        + [C.c_void_p] * 9
+                                        + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                        + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+                                        + [C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "mm_pathwise_basis": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 9),
     "mm_pathwise_pack_stream": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 4),
     "mm_rollout_closed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -25,6 +25,9 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // specialisation mm6_step8 applies (mm_moments6.hip) -- A/B tests and measurements on one build; s56 and estS are bit-identical
 #define MM_ISTAGE_OLD_SPOLY56 (1 << 24)
 
+// kernel families of the pathwise entries' `kernel` argument (mm_pathwise_*_kern): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
+#define MM_PW_KERNELS 3
+
 static inline int mm_num_pairs(int L, int flags) {
   return (flags & MM_FULL_OUTPUT_COV) ? L * (L + 1) / 2 : L;
 }

@@ -9,6 +9,8 @@
 //   x_scale = sqrt(log2 e) / ls_a, zs_t = z_m * x_scale_a, hz = |zs|^2 / 2, hx = |xs|^2 / 2, so that
 //   the SE-ARD kernel exp(-|x - z|^2 / (2 ls^2)) is a bare v_exp_f32.  Shared operands are stored
 //   k-major ([d][K], [d][M]) so that a wave's 16-byte loads are contiguous.
+//   Matern-3/2 / Matern-5/2 latents (template parameter KF, the _kern entries): the same argument a = -(log2 e / 2) r^2, the
+//   update half's 2^a replaced by pw_kern<KF>(a) -- one square root, one 2^x and a short polynomial; KF = 0 is the SE code.
 //
 // Every (sample, latent) owns K + M weights that are used exactly once per step: the kernel is a
 // weight stream, HBM-bound (S L (K+M) sizeof(T) bytes per step; C5 per GPU: 0.8 GB).  The weights
@@ -49,6 +51,39 @@ __device__ __forceinline__ void pw_sincos(float x, float& c, float& s) {
   c = __builtin_amdgcn_cosf(r); s = __builtin_amdgcn_sinf(r);
 }
 __device__ __forceinline__ void pw_sincos(double x, double& c, double& s) { sincospi(2.0 * x, &s, &c); }
+
+// The kernel family of the update half (KF): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2 (gpflow's parametrisation).
+// The stream's argument is arg = zs . xs - hz - hx = -(log2 e / 2) r^2 for every family; pw_kern returns
+//   e = k(r) / var  and  g = -k'(r) / (var r)   (SE: g = e; Matern-3/2: 3 e^-s, s = sqrt3 r; Matern-5/2: 5/3 (1 + s) e^-s, s = sqrt5 r)
+// so that d e / d x_k = ln2 g (c_k - xscale_k^2 x_k) for all three.  With q = s log2 e = sqrt(4 nu log2 e (-arg)) the
+// exponential is a bare 2^-q; -arg is clamped at 0 (expanded form: a sample on an inducing point gives a tiny negative r^2).
+__device__ __forceinline__ float pw_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+__device__ __forceinline__ double pw_sqrt(double x) { return sqrt(x); }
+template <int KF, typename T>
+__device__ __forceinline__ void pw_kern(T arg, T& e, T& g) {
+  if constexpr (KF == 0) {
+    e = PW_EXP(arg); g = e;
+  } else {
+    // q = log2 e sqrt(2 nu) r, r^2 = -2 ln2 arg  =>  q^2 = 4 nu log2 e (-arg)
+    constexpr double c2 = (KF == 1 ? 6.0 : 10.0) * 1.4426950408889634;
+    const T q = pw_sqrt((T)c2 * (arg < (T)0 ? -arg : (T)0));
+    const T p = PW_EXP(-q);
+    const T sq = (T)0.6931471805599453 * q;                  // s = sqrt(2 nu) r
+    if constexpr (KF == 1) {
+      e = ((T)1 + sq) * p; g = (T)3 * p;
+    } else {
+      e = ((T)1 + sq + (T)(1.0 / 3.0) * sq * sq) * p; g = (T)(5.0 / 3.0) * ((T)1 + sq) * p;
+    }
+  }
+}
+
+// ... of a packed f32 sample pair
+template <int KF>
+__device__ __forceinline__ void pw_kern2(const pwf2& arg, pwf2& e, pwf2& g) {
+  float e0, g0, e1, g1;
+  pw_kern<KF, float>(arg[0], e0, g0); pw_kern<KF, float>(arg[1], e1, g1);
+  e = (pwf2){e0, e1}; g = (pwf2){g0, g1};
+}
 
 template <typename T>
 __device__ __forceinline__ void pw_unpack(const float4& v, T (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
@@ -104,7 +139,7 @@ __device__ __forceinline__ float pw_wave_sum63(float v) {
 #define PW_WIDE_NH 2
 
 // k_pathwise<T, DK, true, false>, DK > 8: wave wv owns the latents wv, wv + 4, ... of the workgroup's NS samples, two at a time
-template <typename T, int DK>
+template <typename T, int DK, int KF>
 __device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, const T* __restrict__ x,
                                             const T* __restrict__ omega, const T* __restrict__ phase, const T* __restrict__ zs,
                                             const T* __restrict__ hz, const double* __restrict__ xscale,
@@ -120,11 +155,11 @@ __device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, c
 #pragma unroll 1
     for (int hf = 0; hf < NS / NH; ++hf) {
       const int s0 = g * NS + hf * NH;
-      T xr[NH][DK], accp[NH], accu[NH], accJ[NH][DK];
+      T xr[NH][DK], accp[NH], accu[NH], accg[NH], accJ[NH][DK];       // accg = sum v g (KF != 0; SE: g = e, accu serves)
 #pragma unroll
       for (int s = 0; s < NH; ++s) {
         const int row = (s0 + s < S) ? s0 + s : S - 1;
-        accp[s] = (T)0; accu[s] = (T)0;
+        accp[s] = (T)0; accu[s] = (T)0; accg[s] = (T)0;
 #pragma unroll
         for (int k = 0; k < DK; ++k) {
           const T v = x[(size_t)row * d + (k < d ? k : 0)];
@@ -234,11 +269,14 @@ __device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, c
               T arg = -hv[j] - hx[s];
 #pragma unroll
               for (int k = 0; k < DK; ++k) arg += cv[k][j] * xsc[s][k];
-              const T e = PW_EXP(arg);
+              T e, gq;
+              pw_kern<KF>(arg, e, gq);
               const T t = vv[s][j] * e;
               accu[s] += t;
+              const T tj = KF ? vv[s][j] * gq : t;
+              if constexpr (KF != 0) accg[s] += tj;
 #pragma unroll
-              for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+              for (int k = 0; k < DK; ++k) accJ[s][k] += tj * cv[k][j];
             }
 #pragma unroll
           for (int s = 0; s < NH; ++s) { vq[0][s] = vq[1][s]; vq[1][s] = vq[2][s]; }
@@ -250,7 +288,7 @@ __device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, c
           for (int k = 0; k < DK; ++k) {
             const T scv = (T)xscale[a * d + (k < d ? k : 0)];
             const T sc = (k < d) ? scv : (T)0;
-            accJ[s][k] = fj * sc * (accJ[s][k] - xsc[s][k] * accu[s]);
+            accJ[s][k] = fj * sc * (accJ[s][k] - xsc[s][k] * (KF ? accg[s] : accu[s]));
           }
       }
       // ---- wave reduction, one value and DK Jacobian entries per sample
@@ -277,7 +315,7 @@ __device__ __forceinline__ void pw_wide_jac(int S, int L, int M, int K, int d, c
 // k_pathwise_lds<T, DK, true, false>, DK > 8, after the operands are staged: the wave's work is ONE flat sequence of
 // half-blocks (its groups back to back, per group first half then second, NB blocks each) through the same register ring.
 // f32: the two samples of a half are ONE packed pair (the PK form of the narrow pass, with NP = 1).
-template <typename T, int DK>
+template <typename T, int DK, int KF>
 __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, int NB, int d, int nW, int a, int wgi, int wv,
                                                 int lane, const T* __restrict__ op, const T (&sc)[DK], double ps, double vr,
                                                 double mc, const T* __restrict__ x, const T* __restrict__ wb,
@@ -302,8 +340,8 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
     else if (ld_g + g_stride < ngroups) { ld_g += g_stride; ld_h = 0; ld_tb = 0; }
   };
   int cg = g_first, ch = 0, ctb = 0;                     // half-block being consumed
-  T xr[NH][DK], hx[NH], accp[NH], accu[NH], accJ[NH][PK ? 1 : DK];
-  pwf2 xr2[PK ? DK : 1], hx2, accp2, accu2, accJ2[PK ? DK : 1];
+  T xr[NH][DK], hx[NH], accp[NH], accu[NH], accg[NH], accJ[NH][PK ? 1 : DK];
+  pwf2 xr2[PK ? DK : 1], hx2, accp2, accu2, accg2, accJ2[PK ? DK : 1];
   auto consume = [&](const VT (&q)[NH]) {
     const int s0 = cg * NS + ch * NH;
     if (ctb == 0) {                                      // new half: its two states (wave-uniform loads)
@@ -319,13 +357,13 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
           h += xs * xs;
         }
         hx[s] = (T)0.5 * h;
-        accp[s] = (T)0; accu[s] = (T)0;
+        accp[s] = (T)0; accu[s] = (T)0; accg[s] = (T)0;
 #pragma unroll
         for (int k = 0; k < (PK ? 1 : DK); ++k) accJ[s][k] = (T)0;
       }
       if constexpr (PK) {
         hx2 = (pwf2){(float)hx[0], (float)hx[1]};
-        accp2 = (pwf2){0.0f, 0.0f}; accu2 = (pwf2){0.0f, 0.0f};
+        accp2 = (pwf2){0.0f, 0.0f}; accu2 = (pwf2){0.0f, 0.0f}; accg2 = (pwf2){0.0f, 0.0f};
 #pragma unroll
         for (int k = 0; k < DK; ++k) {
           xr2[k] = (pwf2){(float)xr[0][k], (float)xr[1][k]};
@@ -367,11 +405,15 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
           pwf2 arg = PW_B2(-(float)sv[j]) - hx2;
 #pragma unroll
           for (int k = 0; k < DK; ++k) arg = __builtin_elementwise_fma(PW_B2(cv[k][j]), xr2[k], arg);
-          const pwf2 e2 = {pw_exp(arg[0]), pw_exp(arg[1])};
-          const pwf2 t2 = (pwf2){(float)wv4[0][j], (float)wv4[1][j]} * e2;
+          pwf2 e2, g2;
+          pw_kern2<KF>(arg, e2, g2);
+          const pwf2 v2 = {(float)wv4[0][j], (float)wv4[1][j]};
+          const pwf2 t2 = v2 * e2;
           accu2 = accu2 + t2;
+          const pwf2 tj2 = KF ? v2 * g2 : t2;
+          if constexpr (KF != 0) accg2 = accg2 + tj2;
 #pragma unroll
-          for (int k = 0; k < DK; ++k) accJ2[k] = __builtin_elementwise_fma(t2, PW_B2(cv[k][j]), accJ2[k]);
+          for (int k = 0; k < DK; ++k) accJ2[k] = __builtin_elementwise_fma(tj2, PW_B2(cv[k][j]), accJ2[k]);
         }
       }
     } else {
@@ -404,18 +446,21 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
             T arg = -sv[j] - hx[s];
 #pragma unroll
             for (int k = 0; k < DK; ++k) arg += cv[k][j] * xr[s][k];
-            const T e = PW_EXP(arg);
+            T e, gq;
+            pw_kern<KF>(arg, e, gq);
             const T t = wv4[s][j] * e;
             accu[s] += t;
+            const T tj = KF ? wv4[s][j] * gq : t;
+            if constexpr (KF != 0) accg[s] += tj;
 #pragma unroll
-            for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+            for (int k = 0; k < DK; ++k) accJ[s][k] += tj * cv[k][j];
           }
       }
     }
     if (ctb == NB - 1) {                                 // half done: reduce, Euler update, store
       if constexpr (PK) {
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) { accp[hh] = (T)accp2[hh]; accu[hh] = (T)accu2[hh]; }
+        for (int hh = 0; hh < 2; ++hh) { accp[hh] = (T)accp2[hh]; accu[hh] = (T)accu2[hh]; accg[hh] = (T)accg2[hh]; }
       }
       const T fj = (T)(0.6931471805599453 * vr);
 #pragma unroll
@@ -431,7 +476,7 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
         for (int k = 0; k < DK; ++k) {
           T aj;
           if constexpr (PK) aj = (T)accJ2[k][s]; else aj = accJ[s][k];
-          const T jv = pw_wave_sum63(fj * (aj - sc[k] * sc[k] * xr[s][k] * accu[s]));
+          const T jv = pw_wave_sum63(fj * (aj - sc[k] * sc[k] * xr[s][k] * (KF ? accg[s] : accu[s])));
           if (lane == 63 && s0 + s < S && k < d) jac[((size_t)(s0 + s) * L + a) * d + k] = jv;
         }
       }
@@ -469,7 +514,7 @@ __device__ __forceinline__ void pw_wide_jac_lds(int S, int L, int KT, int nbK, i
 // pass in flight).  EULER != 0: x_out = x + dt f (needs d == L), else f_out = f.
 // CND: the pass also accumulates the ABSOLUTE terms, abs[s,a] = scale_a sum_k |w cos| + var_a sum_m |v 2^arg| -- what the rounding of
 // a T-typed weight stream and T-typed basis values does to f[s,a] is within ~2 eps_T of it (mm_pathwise_eval_bound).
-template <typename T, int DK, bool JAC, bool CND>
+template <typename T, int DK, bool JAC, bool CND, int KF>
 __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, int d,
                                                   const T* __restrict__ x,        // [S,d]
                                                   const T* __restrict__ omega,    // [L,d,K] revolutions
@@ -490,7 +535,7 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
   constexpr int W = PwVec<T>::W, NS = MM_PW_NS, BT = 64 * W;     // BT terms per pass of a wave
   constexpr int NJ = JAC ? DK : 1;
   if constexpr (JAC && DK > 8) {                    // the wide Jacobian pass: half-groups (pw_wide_jac above)
-    pw_wide_jac<T, DK>(S, L, M, K, d, x, omega, phase, zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, euler, dt);
+    pw_wide_jac<T, DK, KF>(S, L, M, K, d, x, omega, phase, zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, euler, dt);
     return;
   }
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -509,10 +554,10 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
   }
 
   for (int a = wv; a < L; a += 4) {
-    T accp[NS], accu[NS], accJ[NS][NJ], absp[NS], absu[NS];
+    T accp[NS], accu[NS], accg[NS], accJ[NS][NJ], absp[NS], absu[NS];   // accg = sum v g (JAC, KF != 0; SE: g = e, accu serves)
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      accp[s] = (T)0; accu[s] = (T)0; absp[s] = (T)0; absu[s] = (T)0;
+      accp[s] = (T)0; accu[s] = (T)0; accg[s] = (T)0; absp[s] = (T)0; absu[s] = (T)0;
 #pragma unroll
       for (int k = 0; k < NJ; ++k) accJ[s][k] = (T)0;
     }
@@ -632,13 +677,16 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
             T arg = -hv[j] - hx[s];
 #pragma unroll
             for (int k = 0; k < DK; ++k) arg += cv[k][j] * xsc[s][k];
-            const T e = PW_EXP(arg);
+            T e, gq;
+            pw_kern<KF>(arg, e, gq);
             const T t = vv[s][j] * e;
             accu[s] += t;
             if constexpr (CND) absu[s] += fabs(vv[s][j]) * e;
             if constexpr (JAC) {
+              const T tj = KF ? vv[s][j] * gq : t;
+              if constexpr (KF != 0) accg[s] += tj;
 #pragma unroll
-              for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+              for (int k = 0; k < DK; ++k) accJ[s][k] += tj * cv[k][j];
             }
           }
 #pragma unroll
@@ -653,7 +701,7 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
           for (int k = 0; k < DK; ++k) {
             const T scv = (T)xscale[a * d + (k < d ? k : 0)];
             const T sc = (k < d) ? scv : (T)0;
-            accJ[s][k] = fj * sc * (accJ[s][k] - xsc[s][k] * accu[s]);
+            accJ[s][k] = fj * sc * (accJ[s][k] - xsc[s][k] * (KF ? accg[s] : accu[s]));
           }
       }
     }
@@ -688,7 +736,7 @@ __global__ __launch_bounds__(256) void k_pathwise(int S, int L, int M, int K, in
 // and then streams many sample groups through it, so the only global traffic in the loop is the
 // weight stream itself (operand re-reads through L2 cost 39 % of the plain kernel's time).
 // grid = L * nW workgroups; wave w of workgroup (a, i) handles sample groups i*8 + w, + nW*8, ...
-template <typename T, int DK, bool JAC, bool CND>
+template <typename T, int DK, bool JAC, bool CND, int KF>
 __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L, int M, int K, int d, int nW,
                                                       const T* __restrict__ x, const T* __restrict__ omega,
                                                       const T* __restrict__ phase, const T* __restrict__ zs,
@@ -737,7 +785,7 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
   }
   const double ps = pscale[a], vr = var[a], mc = meanc ? meanc[a] : 0.0;
   if constexpr (JAC && DK > 8) {                    // the wide Jacobian pass: half-groups (pw_wide_jac_lds above)
-    pw_wide_jac_lds<T, DK>(S, L, KT, nbK, NB, d, nW, a, wgi, wv, lane, op, sc, ps, vr, mc, x, wb, out, traj, jac, euler, dt);
+    pw_wide_jac_lds<T, DK, KF>(S, L, KT, nbK, NB, d, nW, a, wgi, wv, lane, op, sc, ps, vr, mc, x, wb, out, traj, jac, euler, dt);
     return;
   }
 
@@ -759,14 +807,14 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
     else if (ld_g + g_stride < ngroups) { ld_g += g_stride; ld_tb = 0; }
   };
   int cg = g_first, ctb = 0;                            // block being consumed
-  T xr[NS][DK], hx[NS], accp[NS], accu[NS], accJ[NS][NJ], absp[NS], absu[NS];
+  T xr[NS][DK], hx[NS], accp[NS], accu[NS], accg[NS], accJ[NS][NJ], absp[NS], absu[NS];
   // PK (the Jacobian pass of an f32 stream): the NS samples of a group in PAIRS -- every per-(term, sample) operation of the pass
   // (the d FMAs of the argument, the d FMAs of the Jacobian sums, the weight product, the sums) is one v_pk_*_f32 over a sample
   // pair with the shared operand (omega_k / c_k of the term) broadcast: half the FMA-class instructions of a pass that is
   // VALU-bound.  Pairs over SAMPLES need no extra accumulators (pairs over terms did: 256 VGPRs + scratch)
   constexpr bool PK = JAC && sizeof(T) == 4 && NS % 2 == 0;
   constexpr int NP = PK ? NS / 2 : 1, NJP = PK ? DK : 1;
-  pwf2 xr2[NP][NJP], hx2[NP], accp2[NP], accu2[NP], accJ2[NP][NJP];
+  pwf2 xr2[NP][NJP], hx2[NP], accp2[NP], accu2[NP], accg2[NP], accJ2[NP][NJP];
   auto consume = [&](const VT (&q)[NS]) {
     const int s0 = cg * NS;
     if (ctb == 0) {                                     // new group: its NS states (wave-uniform loads)
@@ -782,7 +830,7 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
           h += xs * xs;
         }
         hx[s] = (T)0.5 * h;
-        accp[s] = (T)0; accu[s] = (T)0; absp[s] = (T)0; absu[s] = (T)0;
+        accp[s] = (T)0; accu[s] = (T)0; accg[s] = (T)0; absp[s] = (T)0; absu[s] = (T)0;
 #pragma unroll
         for (int k = 0; k < NJ; ++k) accJ[s][k] = (T)0;
       }
@@ -790,7 +838,7 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
 #pragma unroll
         for (int sp = 0; sp < NP; ++sp) {
           hx2[sp] = (pwf2){(float)hx[2 * sp], (float)hx[2 * sp + 1]};
-          accp2[sp] = (pwf2){0.0f, 0.0f}; accu2[sp] = (pwf2){0.0f, 0.0f};
+          accp2[sp] = (pwf2){0.0f, 0.0f}; accu2[sp] = (pwf2){0.0f, 0.0f}; accg2[sp] = (pwf2){0.0f, 0.0f};
 #pragma unroll
           for (int k = 0; k < DK; ++k) {
             xr2[sp][k] = (pwf2){(float)xr[2 * sp][k], (float)xr[2 * sp + 1][k]};
@@ -841,11 +889,15 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
             pwf2 arg = PW_B2(-(float)sv[j]) - hx2[sp];
 #pragma unroll
             for (int k = 0; k < DK; ++k) arg = __builtin_elementwise_fma(PW_B2(cv[k][j]), xr2[sp][k], arg);
-            const pwf2 e2 = {pw_exp(arg[0]), pw_exp(arg[1])};
-            const pwf2 t2 = (pwf2){(float)wv4[2 * sp][j], (float)wv4[2 * sp + 1][j]} * e2;
+            pwf2 e2, g2;
+            pw_kern2<KF>(arg, e2, g2);
+            const pwf2 v2 = {(float)wv4[2 * sp][j], (float)wv4[2 * sp + 1][j]};
+            const pwf2 t2 = v2 * e2;
             accu2[sp] = accu2[sp] + t2;
+            const pwf2 tj2 = KF ? v2 * g2 : t2;
+            if constexpr (KF != 0) accg2[sp] = accg2[sp] + tj2;
 #pragma unroll
-            for (int k = 0; k < DK; ++k) accJ2[sp][k] = __builtin_elementwise_fma(t2, PW_B2(cv[k][j]), accJ2[sp][k]);
+            for (int k = 0; k < DK; ++k) accJ2[sp][k] = __builtin_elementwise_fma(tj2, PW_B2(cv[k][j]), accJ2[sp][k]);
           }
       }
     } else if (ctb < nbK) {                             // wave-uniform: prior block
@@ -891,13 +943,16 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
           T arg = -sv[j] - hx[s];
 #pragma unroll
           for (int k = 0; k < DK; ++k) arg += cv[k][j] * xr[s][k];
-          const T e = PW_EXP(arg);
+          T e, gq;
+          pw_kern<KF>(arg, e, gq);
           const T t = wv4[s][j] * e;
           accu[s] += t;
           if constexpr (CND) absu[s] += fabs(wv4[s][j]) * e;
           if constexpr (JAC) {
+            const T tj = KF ? wv4[s][j] * gq : t;
+            if constexpr (KF != 0) accg[s] += tj;
 #pragma unroll
-            for (int k = 0; k < DK; ++k) accJ[s][k] += t * cv[k][j];
+            for (int k = 0; k < DK; ++k) accJ[s][k] += tj * cv[k][j];
           }
         }
     }
@@ -907,7 +962,7 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
         for (int sp = 0; sp < NP; ++sp)
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) {
-            accp[2 * sp + hh] = (T)accp2[sp][hh]; accu[2 * sp + hh] = (T)accu2[sp][hh];
+            accp[2 * sp + hh] = (T)accp2[sp][hh]; accu[2 * sp + hh] = (T)accu2[sp][hh]; accg[2 * sp + hh] = (T)accg2[sp][hh];
 #pragma unroll
             for (int k = 0; k < DK; ++k) accJ[2 * sp + hh][PK ? k : 0] = (T)accJ2[sp][k][hh];
           }
@@ -932,7 +987,7 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
           const T fj = (T)(0.6931471805599453 * vr);
 #pragma unroll
           for (int k = 0; k < DK; ++k) {
-            const T jv = pw_wave_sum63(fj * (accJ[s][k] - sc[k] * sc[k] * xr[s][k] * accu[s]));
+            const T jv = pw_wave_sum63(fj * (accJ[s][k] - sc[k] * sc[k] * xr[s][k] * (KF ? accg[s] : accu[s])));
             if (lane == 63 && s0 + s < S && k < d) jac[((size_t)(s0 + s) * L + a) * d + k] = jv;
           }
         }
@@ -958,7 +1013,8 @@ template <typename T>
 static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* omega, const T* phase, const T* zs,
                      const T* hz, const double* xscale, const double* pscale, const double* var,
                      const double* meanc, const T* wb, T* out, T* traj, int euler, double dt, hipStream_t s,
-                     T* jac = nullptr, T* cnd = nullptr) {
+                     T* jac = nullptr, T* cnd = nullptr, int kern = 0) {
+  if (kern < 0 || kern >= MM_PW_KERNELS) return MM_E_ARG;
   if (jac && cnd) return MM_E_ARG;                  // (one extra output per pass)
   if (jac && d > 16) return MM_E_DIM;              // the Jacobian pass: d <= 8 whole groups, 8 < d <= 16 half-groups
   // LDS-resident operands when one latent's (d + 1) x (K + M) block fits (<= 144 KB)
@@ -968,7 +1024,8 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
     const int ngroups = (S + MM_PW_NS - 1) / MM_PW_NS;
     int nW = 256 / L; if (nW < 1) nW = 1;                           // ~ one workgroup per CU
     while (nW > 1 && (nW - 1) * PW_LDS_WAVES >= ngroups) --nW;                 // no idle workgroups on small S
-#define PW_LAUNCH_LDS_(DK_, JAC_, CND_)                                                             \
+#define PW_LAUNCH_LDS_(DK_, JAC_, CND_) do { if (kern == 0) PW_LAUNCH_LDS_K(DK_, JAC_, CND_, 0); else if (kern == 1) PW_LAUNCH_LDS_K(DK_, JAC_, CND_, 1); else PW_LAUNCH_LDS_K(DK_, JAC_, CND_, 2); } while (0)
+#define PW_LAUNCH_LDS_K(DK_, JAC_, CND_, KF_)                                                       \
     do {                                                                                            \
       /* raise the dynamic-LDS limit once per instantiation and device (the call is slow: not per launch) */ \
       static std::atomic<unsigned long long> lds_set{0ull};                                         \
@@ -976,12 +1033,12 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
       if (hipGetDevice(&dev_) != hipSuccess) dev_ = 64;                                             \
       const unsigned long long bit_ = (dev_ >= 0 && dev_ < 64) ? (1ull << dev_) : 0ull;             \
       if (!bit_ || !(lds_set.load() & bit_)) {                                                      \
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pathwise_lds<T, DK_, JAC_, CND_>), \
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pathwise_lds<T, DK_, JAC_, CND_, KF_>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024); \
         if (ea != hipSuccess) return (int)ea;                                                       \
         lds_set.fetch_or(bit_);                                                                     \
       }                                                                                             \
-      hipLaunchKernelGGL((k_pathwise_lds<T, DK_, JAC_, CND_>), dim3(L * nW), dim3(64 * PW_LDS_WAVES), lds_bytes, s, S, L, M, K, d, nW, \
+      hipLaunchKernelGGL((k_pathwise_lds<T, DK_, JAC_, CND_, KF_>), dim3(L * nW), dim3(64 * PW_LDS_WAVES), lds_bytes, s, S, L, M, K, d, nW, \
                          x, omega, phase, zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, cnd, euler, dt); \
     } while (0)
 #define PW_LAUNCH_LDS(DK_) do { if (jac) PW_LAUNCH_LDS_(DK_, true, false); else if (cnd) PW_LAUNCH_LDS_(DK_, false, true); else PW_LAUNCH_LDS_(DK_, false, false); } while (0)
@@ -993,12 +1050,14 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
 #undef PW_LAUNCH_LDS_NJ
 #undef PW_LAUNCH_LDS
 #undef PW_LAUNCH_LDS_
+#undef PW_LAUNCH_LDS_K
     hipError_t el = hipGetLastError();
     return el == hipSuccess ? 0 : (int)el;
   }
   dim3 grid((S + MM_PW_NS - 1) / MM_PW_NS);
-#define PW_LAUNCH_(DK_, JAC_, CND_) hipLaunchKernelGGL((k_pathwise<T, DK_, JAC_, CND_>), grid, dim3(256), 0, s, S, L, M, K, d, x, omega, phase, \
-                                                zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, cnd, euler, dt)
+#define PW_LAUNCH_K(DK_, JAC_, CND_, KF_) hipLaunchKernelGGL((k_pathwise<T, DK_, JAC_, CND_, KF_>), grid, dim3(256), 0, s, S, L, M, K, d, x, \
+                                                omega, phase, zs, hz, xscale, pscale, var, meanc, wb, out, traj, jac, cnd, euler, dt)
+#define PW_LAUNCH_(DK_, JAC_, CND_) do { if (kern == 0) PW_LAUNCH_K(DK_, JAC_, CND_, 0); else if (kern == 1) PW_LAUNCH_K(DK_, JAC_, CND_, 1); else PW_LAUNCH_K(DK_, JAC_, CND_, 2); } while (0)
 #define PW_LAUNCH(DK_) do { if (jac) PW_LAUNCH_(DK_, true, false); else if (cnd) PW_LAUNCH_(DK_, false, true); else PW_LAUNCH_(DK_, false, false); } while (0)
 #define PW_LAUNCH_NJ(DK_) do { if (cnd) PW_LAUNCH_(DK_, false, true); else PW_LAUNCH_(DK_, false, false); } while (0)
   if (d <= 4) PW_LAUNCH(4);
@@ -1008,11 +1067,13 @@ static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* ome
 #undef PW_LAUNCH_NJ
 #undef PW_LAUNCH
 #undef PW_LAUNCH_
+#undef PW_LAUNCH_K
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
 
-static int pw_check(int S, int L, int M, int K, int d, int dtype) {
+static int pw_check(int S, int L, int M, int K, int d, int dtype, int kern = 0) {
+  if (kern < 0 || kern >= MM_PW_KERNELS) return MM_E_ARG;     // 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
   if (S <= 0 || L <= 0 || M <= 0 || K <= 0 || d <= 0) return MM_E_ARG;
   if (d > MM_DMAX) return MM_E_DIM;
   if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
@@ -1021,12 +1082,13 @@ static int pw_check(int S, int L, int M, int K, int d, int dtype) {
   return 0;
 }
 
-extern "C" int mm_pathwise_eval(int S, int L, int M, int K, int d, int dtype,
-                                const void* x, const void* omega_t, const void* phase, const void* zs_t,
-                                const void* hz, const double* x_scale, const double* prior_scale,
-                                const double* variance, const double* mean_c, const void* wb, void* f_out,
-                                void* stream) {
-  int rc = pw_check(S, L, M, K, d, dtype);
+// the entries without a kernel argument are their _kern siblings with kernel = 0 (SquaredExponential)
+extern "C" int mm_pathwise_eval_kern(int S, int L, int M, int K, int d, int dtype,
+                                     const void* x, const void* omega_t, const void* phase, const void* zs_t,
+                                     const void* hz, const double* x_scale, const double* prior_scale,
+                                     const double* variance, const double* mean_c, const void* wb, void* f_out,
+                                     void* stream, int kernel) {
+  int rc = pw_check(S, L, M, K, d, dtype, kernel);
   if (rc) return rc;
   if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out)
     return MM_E_ARG;
@@ -1034,18 +1096,26 @@ extern "C" int mm_pathwise_eval(int S, int L, int M, int K, int d, int dtype,
   if (dtype == MM_F64)
     return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
                              (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s);
+                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, nullptr, nullptr, kernel);
   return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
                           (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s);
+                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, nullptr, nullptr, kernel);
+}
+extern "C" int mm_pathwise_eval(int S, int L, int M, int K, int d, int dtype,
+                                const void* x, const void* omega_t, const void* phase, const void* zs_t,
+                                const void* hz, const double* x_scale, const double* prior_scale,
+                                const double* variance, const double* mean_c, const void* wb, void* f_out,
+                                void* stream) {
+  return mm_pathwise_eval_kern(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
+                               f_out, stream, 0);
 }
 
-extern "C" int mm_pathwise_eval_bound(int S, int L, int M, int K, int d, int dtype,
-                                      const void* x, const void* omega_t, const void* phase, const void* zs_t,
-                                      const void* hz, const double* x_scale, const double* prior_scale,
-                                      const double* variance, const double* mean_c, const void* wb, void* f_out,
-                                      void* abs_out, void* stream) {
-  int rc = pw_check(S, L, M, K, d, dtype);
+extern "C" int mm_pathwise_eval_bound_kern(int S, int L, int M, int K, int d, int dtype,
+                                           const void* x, const void* omega_t, const void* phase, const void* zs_t,
+                                           const void* hz, const double* x_scale, const double* prior_scale,
+                                           const double* variance, const double* mean_c, const void* wb, void* f_out,
+                                           void* abs_out, void* stream, int kernel) {
+  int rc = pw_check(S, L, M, K, d, dtype, kernel);
   if (rc) return rc;
   if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out || !abs_out)
     return MM_E_ARG;
@@ -1053,44 +1123,61 @@ extern "C" int mm_pathwise_eval_bound(int S, int L, int M, int K, int d, int dty
   if (dtype == MM_F64)
     return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
                              (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, nullptr, (double*)abs_out);
+                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, nullptr, (double*)abs_out, kernel);
   return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
                           (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, nullptr, (float*)abs_out);
+                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, nullptr, (float*)abs_out, kernel);
+}
+extern "C" int mm_pathwise_eval_bound(int S, int L, int M, int K, int d, int dtype,
+                                      const void* x, const void* omega_t, const void* phase, const void* zs_t,
+                                      const void* hz, const double* x_scale, const double* prior_scale,
+                                      const double* variance, const double* mean_c, const void* wb, void* f_out,
+                                      void* abs_out, void* stream) {
+  return mm_pathwise_eval_bound_kern(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
+                                     wb, f_out, abs_out, stream, 0);
 }
 
 // one evaluation f [S,L] (and, jac != NULL, d f / d x [S,L,d]) for the other translation units (mm_pathwise_policy.hip)
 int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
                        const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
-                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s) {
-  int rc = pw_check(S, L, M, K, d, dtype);
+                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel) {
+  int rc = pw_check(S, L, M, K, d, dtype, kernel);
   if (rc) return rc;
   if (dtype == MM_F64)
     return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
                              (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, (double*)jac);
+                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, (double*)jac, nullptr, kernel);
   return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
                           (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, (float*)jac);
+                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, (float*)jac, nullptr, kernel);
 }
 
+extern "C" int mm_pathwise_eval_jac_kern(int S, int L, int M, int K, int d, int dtype,
+                                         const void* x, const void* omega_t, const void* phase, const void* zs_t,
+                                         const void* hz, const double* x_scale, const double* prior_scale,
+                                         const double* variance, const double* mean_c, const void* wb, void* f_out,
+                                         void* jac_out, void* stream, int kernel) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;
+  if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out || !jac_out)
+    return MM_E_ARG;
+  return mm_pathwise_launch(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
+                            f_out, jac_out, (hipStream_t)stream, kernel);
+}
 extern "C" int mm_pathwise_eval_jac(int S, int L, int M, int K, int d, int dtype,
                                     const void* x, const void* omega_t, const void* phase, const void* zs_t,
                                     const void* hz, const double* x_scale, const double* prior_scale,
                                     const double* variance, const double* mean_c, const void* wb, void* f_out,
                                     void* jac_out, void* stream) {
-  if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out || !jac_out)
-    return MM_E_ARG;
-  return mm_pathwise_launch(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
-                            f_out, jac_out, (hipStream_t)stream);
+  return mm_pathwise_eval_jac_kern(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
+                                   f_out, jac_out, stream, 0);
 }
 
-extern "C" int mm_pathwise_rollout(int S, int L, int M, int K, int d, int dtype, int H, double dt,
-                                   void* x, void* x_tmp, const void* omega_t, const void* phase, const void* zs_t,
-                                   const void* hz, const double* x_scale, const double* prior_scale,
-                                   const double* variance, const double* mean_c, const void* wb,
-                                   void* traj, void* stream) {
-  int rc = pw_check(S, L, M, K, d, dtype);
+extern "C" int mm_pathwise_rollout_kern(int S, int L, int M, int K, int d, int dtype, int H, double dt,
+                                        void* x, void* x_tmp, const void* omega_t, const void* phase, const void* zs_t,
+                                        const void* hz, const double* x_scale, const double* prior_scale,
+                                        const double* variance, const double* mean_c, const void* wb,
+                                        void* traj, void* stream, int kernel) {
+  int rc = pw_check(S, L, M, K, d, dtype, kernel);
   if (rc) return rc;
   if (H <= 0 || !x || !x_tmp || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb)
     return MM_E_ARG;
@@ -1103,11 +1190,11 @@ extern "C" int mm_pathwise_rollout(int S, int L, int M, int K, int d, int dtype,
     if (dtype == MM_F64)
       rc = pw_launch<double>(S, L, M, K, d, (const double*)cur, (const double*)omega_t, (const double*)phase,
                              (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)nxt, (double*)tr, 1, dt, s);
+                             (const double*)wb, (double*)nxt, (double*)tr, 1, dt, s, nullptr, nullptr, kernel);
     else
       rc = pw_launch<float>(S, L, M, K, d, (const float*)cur, (const float*)omega_t, (const float*)phase,
                             (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                            (const float*)wb, (float*)nxt, (float*)tr, 1, dt, s);
+                            (const float*)wb, (float*)nxt, (float*)tr, 1, dt, s, nullptr, nullptr, kernel);
     if (rc) return rc;
     char* t = cur; cur = nxt; nxt = t;
   }
@@ -1116,4 +1203,12 @@ extern "C" int mm_pathwise_rollout(int S, int L, int M, int K, int d, int dtype,
     if (e != hipSuccess) return (int)e;
   }
   return 0;
+}
+extern "C" int mm_pathwise_rollout(int S, int L, int M, int K, int d, int dtype, int H, double dt,
+                                   void* x, void* x_tmp, const void* omega_t, const void* phase, const void* zs_t,
+                                   const void* hz, const double* x_scale, const double* prior_scale,
+                                   const double* variance, const double* mean_c, const void* wb,
+                                   void* traj, void* stream) {
+  return mm_pathwise_rollout_kern(S, L, M, K, d, dtype, H, dt, x, x_tmp, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance,
+                                  mean_c, wb, traj, stream, 0);
 }

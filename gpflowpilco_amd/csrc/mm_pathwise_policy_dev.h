@@ -8,7 +8,7 @@
 
 int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
                        const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
-                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s);
+                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel = 0);
 // mm_pathwise_policy.hip: k_pw_grad_sum on stream s -- the fixed-order sum of nslab per-wave slabs [nslab][npar] -> g_policy [npar]
 int mm_pw_grad_sum_launch(const double* gpart, int nslab, int npar, double* g_policy, hipStream_t s);
 

@@ -267,7 +267,7 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
                             const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
                             int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
                             char* tape, const MMPwTapeLayout& tl, int Lg, const double* mix_W, const double* mix_c,
-                            hipStream_t s) {
+                            hipStream_t s, int kernel) {
   // Lg > 0: the _mixed entries -- the stream pass runs with Lg latents and no latent mean straight into the tape's (latent-sized)
   // f and Jacobian slots, the head kernel mixes
   const int nx = D.nx, ne = D.ne, nd = D.nd, Lf = Lg > 0 ? Lg : nx;
@@ -298,7 +298,7 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
     if (h == H) break;
     const int rc = mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
                                       prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f,
-                                      jac ? jac + (size_t)h * S * Lf * nd : nullptr, s);
+                                      jac ? jac + (size_t)h * S * Lf * nd : nullptr, s, kernel);
     if (rc) return rc;
   }
   return 0;
@@ -313,7 +313,8 @@ static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, c
                           const void* policy_packed, size_t policy_bytes, int policy_M,
                           const double* head_scale, const double* head_shift, const void* target,
                           const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
-                          int with_jacobians, void* stream) {
+                          int with_jacobians, void* stream, int kernel = 0) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;             // the drift's kernel family (mm_pathwise_eval_kern)
   MMComposeDims D;
   int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, D);
   if (rc) return rc;
@@ -332,10 +333,10 @@ static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, c
   if (dtype == MM_F64)
     return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
                                     wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
-                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s);
+                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
   return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
                                  pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
-                                 (char*)tape, tl, Lg, mix_W, mix_c, s);
+                                 (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
 }
 
 #define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
@@ -366,6 +367,25 @@ extern "C" int mm_pathwise_policy_rollout_mixed(int S, int M, int K, int dtype, 
   return mmp_nd_rollout(16, true, Lg, mix_W, mix_c, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz,
                         x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
                         target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);
+}
+
+// the one forward entry for a drift of any kernel family (kernel: 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2): the argument
+// list of the _mixed entry plus kernel; Lg = 0 / mix_W = NULL: no mixing (then the _wide entry: nd <= 16, 1 .. 4 actions).  The
+// tape layout does not depend on the family, so the reverse sweeps above are used as they are.
+extern "C" int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                                               const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                                               const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                                               const double* variance, const double* mean_c, const void* wb,
+                                               const void* policy_packed, size_t policy_bytes, int policy_M,
+                                               const double* head_scale, const double* head_shift, const void* target,
+                                               const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                               int with_jacobians, void* stream, int Lg, const double* mix_W,
+                                               const double* mix_c, int kernel) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;
+  const bool mixed = Lg != 0 || mix_W != nullptr;
+  return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t,
+                        phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,
+                        head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel);
 }
 
 // 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)

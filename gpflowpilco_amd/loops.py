@@ -38,7 +38,7 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   from . import bijectors as tfb
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
-  from .models import SVGP, InverseLinkWrapper, KernelRegressor, LinearCoregionalization
+  from .models import SVGP, InverseLinkWrapper, KernelRegressor, LinearCoregionalization, kernel_family
   enc, pol, drift = system.encoder, system.policy, system.drift
 
   def no(reason):
@@ -63,6 +63,14 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   pm_, head = pol.model.model, pol.invlink
   if not isinstance(pm_, SVGP) or not isinstance(drift, SVGP):
     return no("the policy or the drift is not an SVGP")
+  try:
+    pol_family, drift_family = kernel_family(pm_.latent_kernels), kernel_family(drift.latent_kernels)
+  except (ValueError, NotImplementedError) as e:
+    return no(str(e))
+  if pol_family != 0:
+    return no(f"a {type(pm_.latent_kernels[0]).__name__} policy (the native head kernels evaluate a SquaredExponential policy)")
+  if moment_solver and drift_family != 0:
+    return no(f"a {type(drift.latent_kernels[0]).__name__} drift (moment matching has closed forms for SquaredExponential only)")
   nu = int(pm_.num_latent_gps)
   if nu < 1 or nu > 4:
     return no(f"a policy with {nu} latents (the native rollout takes 1 to 4 actions)")
@@ -373,7 +381,9 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   composition as before.  True runs a coregionalised DRIFT with Lg <= nx latents natively, forward and gradient, for 1 to 4 actions
   (``native_actions`` still governs the gradient of nu > 1): the mixing f = W g + c is one small launch per step on the device
   (``mm_rollout_composed_nd_mixed`` and its tape / reverse sweep).  A coregionalised policy, Lg > nx, a trainable drift (W and the
-  mean included) and head / objective constants that require a gradient each fall back once, with a named reason."""
+  mean included) and head / objective constants that require a gradient each fall back once, with a named reason.  So does a
+  drift or a policy with Matern latents: moment matching has closed forms for SquaredExponential only (``native=True`` raises with
+  that reason, and the torch composition meets ``moment_matching``'s own ``NotImplementedError``)."""
   uniform = solution_times is None
   if solution_times is None:
     solution_times = np.arange(1, 1 + num_steps, dtype=np.float64)     # pilco.py:186
@@ -393,7 +403,9 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       if fast is None:
         shape_reason = why_not[0] if why_not else "the system is not the shape mm_rollout_composed implements"
   if native is True and fast is None:
-    raise ValueError("native=True: the system is not the shape mm_rollout_composed implements")
+    # (the text SquaredExponential systems have always got; a Matern drift or policy adds its named reason)
+    raise ValueError("native=True: the system is not the shape mm_rollout_composed implements"
+                     + (f" ({shape_reason})" if shape_reason and "SquaredExponential" in shape_reason else ""))
 
   def _accumulate_loss(t, state, loss):                                # pilco.py:199-205
     x = GaussianMoments(moments=state, centered=True)
@@ -599,7 +611,13 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   1 to 4 actions and nd <= 16 under the ``native_actions`` / ``native_inputs`` rules; it composes with ``native_no_encoder``,
   ``native_objective``, ``native_sampler`` and ``paths=``.  W and the Constant mean are constants of the frozen drift, taken from
   the paths of the call.  A coregionalised policy, Lg > nx, given ``paths`` that carry no mixing or one of another shape than the
-  drift's, and a W or a mean that requires a gradient each fall back once, with a named reason."""
+  drift's, and a W or a mean that requires a gradient each fall back once, with a named reason.
+
+  A drift with ``models.Matern32`` / ``Matern52`` latents (one family for the whole model) runs natively under the same rules and
+  options, with no flag of its own: its paths carry ``Paths.kernel`` and ``PolicyRollout`` calls
+  ``mm_pathwise_policy_rollout_kern`` for every shape; the torch composition (``native=False``) works too, because
+  ``Paths.__call__`` routes on the family.  A Matern POLICY falls back once, by name (``native=True`` raises): the native head
+  kernels evaluate a SquaredExponential policy; its torch composition is ``SVGP.predict_mean`` with the family's Gram matrix."""
   from . import ops
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
@@ -734,6 +752,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     scale, shift = head_constants()
     pol_pack = pm_.packed(torch.float64, False, x0.device)
     # (the trajectory route: a zero built-in cost, its output ignored)
+    # (a Matern drift: PolicyRollout routes on pth.kernel -- the one _kern entry, for every shape admitted above)
     roll = PolicyRollout(pth, pol_pack, nx=nx, active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
                          target=None if traj else objective.target, precis=None if traj else objective.precis, wide=nd > 8)
     needs = grad and (x0.requires_grad or any(t.requires_grad for t in pm_._parameters()))

@@ -3,7 +3,7 @@
 Minimal torch equivalents of the gpflow / gpflow_pilco objects the hot path
 reads (fields only; hyper-parameter fitting is out of scope):
 
-* kernels: ``SquaredExponential`` and the multi-output ``SeparateIndependent`` /
+* kernels: ``SquaredExponential``, ``Matern32`` / ``Matern52`` (pathwise sampling only) and the multi-output ``SeparateIndependent`` /
   ``SharedIndependent`` / ``LinearCoregionalization`` (gpflow.kernels), read at
   ``gpflow_pilco/moment_matching/models.py:205-212,279-286,331-354``;
 * inducing variables (gpflow.inducing_variables), read at ``utils/kernel_expectation.py:41-69``;
@@ -40,8 +40,8 @@ class Kernel:
   pass
 
 
-class SquaredExponential(Kernel):
-  """gpflow.kernels.SquaredExponential: variance * exp(-0.5 |(x - x')/lengthscales|^2)."""
+class Stationary(Kernel):
+  """The fields and helpers of a stationary ARD kernel (gpflow.kernels.Stationary): variance, lengthscales, active_dims."""
 
   def __init__(self, variance=1.0, lengthscales=1.0, active_dims: Optional[Sequence[int]] = None):
     self.variance = _as_param(variance)
@@ -67,6 +67,10 @@ class SquaredExponential(Kernel):
     ls = self.lengthscales
     return ls if ls.ndim > 0 else ls.expand(ndims)
 
+
+class SquaredExponential(Stationary):
+  """gpflow.kernels.SquaredExponential: variance * exp(-0.5 |(x - x')/lengthscales|^2)."""
+
   def K(self, X: torch.Tensor, X2: Optional[torch.Tensor] = None) -> torch.Tensor:
     X = self.slice(X)
     ls = self.lengthscales_vector(X.shape[-1]).to(X)
@@ -74,6 +78,79 @@ class SquaredExponential(Kernel):
     B = A if X2 is None else self.slice(X2) / ls
     d2 = (A * A).sum(-1)[:, None] + (B * B).sum(-1)[None, :] - 2.0 * A @ B.T
     return self.variance.to(X) * torch.exp(-0.5 * d2.clamp_min(0.0))
+
+
+def _scaled_sqdist(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+  """r^2 [..., n, m] between the rows of A [..., n, d] and B [..., m, d] (inputs already divided by the lengthscales), expanded
+  form, clamped at 0."""
+  d2 = (A * A).sum(-1)[..., :, None] + (B * B).sum(-1)[..., None, :] - 2.0 * A @ B.transpose(-1, -2)
+  return d2.clamp_min(0.0)
+
+
+# kernel families: the codes of the C ABI's ``kernel`` argument (include/gpflowpilco_mm.h, the _kern entries)
+KERNEL_SE, KERNEL_MATERN32, KERNEL_MATERN52 = 0, 1, 2
+KERNEL_NAMES = ("se", "matern32", "matern52")
+
+
+def stationary_profile(r2: torch.Tensor, family: int) -> torch.Tensor:
+  """k(r) / variance of a kernel family as a function of r^2 (gpflow's parametrisation)."""
+  if family == KERNEL_SE:
+    return torch.exp(-0.5 * r2)
+  if family not in (KERNEL_MATERN32, KERNEL_MATERN52):
+    raise ValueError(f"kernel family {family}: expected 0 (SquaredExponential), 1 (Matern32) or 2 (Matern52)")
+  # (the derivative of sqrt at 0 is infinite: clamp where autograd must pass through r = 0; k itself is smooth there)
+  s = torch.sqrt((3.0 if family == KERNEL_MATERN32 else 5.0) * r2.clamp_min(1e-36))
+  if family == KERNEL_MATERN32:
+    return (1.0 + s) * torch.exp(-s)
+  return (1.0 + s + s * s / 3.0) * torch.exp(-s)
+
+
+class _Matern(Stationary):
+  """A Matern kernel with ``SquaredExponential``'s fields and methods (gpflow.kernels.Matern32 / Matern52); only ``K`` differs.
+  Sampled by the pathwise solver (``pathwise.generate_paths``); moment matching has closed forms for SquaredExponential only."""
+  family = None
+
+  def K(self, X: torch.Tensor, X2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    X = self.slice(X)
+    ls = self.lengthscales_vector(X.shape[-1]).to(X)
+    A = X / ls
+    B = A if X2 is None else self.slice(X2) / ls
+    return self.variance.to(X) * stationary_profile(_scaled_sqdist(A, B), self.family)
+
+
+class Matern32(_Matern):
+  """gpflow.kernels.Matern32: variance (1 + sqrt3 r) exp(-sqrt3 r), r = |(x - x') / lengthscales|."""
+  family = KERNEL_MATERN32
+
+
+class Matern52(_Matern):
+  """gpflow.kernels.Matern52: variance (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r), r = |(x - x') / lengthscales|."""
+  family = KERNEL_MATERN52
+
+
+def kernel_family(kernels) -> int:
+  """The family shared by a list of latent kernels: 0 SquaredExponential, 1 Matern32, 2 Matern52.  Raises ``ValueError`` naming the
+  latents when they differ (one weight-stream pass evaluates one family), ``NotImplementedError`` for any other kernel class."""
+  fams = []
+  for i, k in enumerate(kernels):
+    if isinstance(k, _Matern):
+      fams.append(k.family)
+    elif isinstance(k, SquaredExponential):
+      fams.append(KERNEL_SE)
+    else:
+      raise NotImplementedError(f"latent {i}: kernel {type(k).__name__} (SquaredExponential, Matern32 and Matern52 are implemented)")
+  if any(f != fams[0] for f in fams):
+    raise ValueError("the latent kernels of one model must be of one family, got "
+                     + ", ".join(f"latent {i}: {type(k).__name__}" for i, k in enumerate(kernels)))
+  return fams[0] if fams else KERNEL_SE
+
+
+def require_squared_exponential(kernels, what: str):
+  fam = kernel_family(kernels)
+  if fam != KERNEL_SE:
+    raise NotImplementedError(f"{what}: moment matching has closed forms for SquaredExponential only (the kernel expectations "
+                              f"of utils/kernel_expectation.py), not for {type(kernels[0]).__name__}; a Matern model is evaluated "
+                              "by SVGP.predict_mean and sampled by the pathwise solver")
 
 
 class MultioutputKernel(Kernel):
@@ -263,16 +340,20 @@ class SVGP:
     """Posterior mean at deterministic inputs x [..., D]: K(x, Z) Kuu^-1 u (+ mean function), i.e. the
     mean half of gpflow's ``predict_f``; what ``KernelRegressor.__call__`` returns (models/core.py:60-62).
     Plain torch (policy evaluation on real states; not on the moment-matching hot path)."""
-    Z, ls, var, beta, _, mean_c = self.precompute(x.device)
     kernels = self.latent_kernels
+    family = kernel_family(kernels)
+    Z, ls, var, beta, mean_c = self._mean_weights(x.device, family)
     union, differ = kernel_input_dims(kernels, x.shape[-1])
     xs = (x[..., list(union)] if differ else kernels[0].slice(x)).to(DEFAULT_FLOAT)
     lead = xs.shape[:-1]
     xs2 = xs.reshape(-1, xs.shape[-1])
     A = xs2[None] / ls[:, None, :]                              # [L, n, d]
     Bz = Z / ls[:, None, :]                                     # [L, M, d]
-    d2 = (A * A).sum(-1)[:, :, None] + (Bz * Bz).sum(-1)[:, None, :] - 2.0 * A @ Bz.transpose(1, 2)
-    Kxz = var[:, None, None] * torch.exp(-0.5 * d2.clamp_min(0.0))
+    if family == KERNEL_SE:
+      d2 = (A * A).sum(-1)[:, :, None] + (Bz * Bz).sum(-1)[:, None, :] - 2.0 * A @ Bz.transpose(1, 2)
+      Kxz = var[:, None, None] * torch.exp(-0.5 * d2.clamp_min(0.0))
+    else:
+      Kxz = var[:, None, None] * stationary_profile(_scaled_sqdist(A, Bz), family)
     g = (Kxz @ beta.unsqueeze(-1)).squeeze(-1).T                # [n, L]
     if isinstance(self.kernel, LinearCoregionalization):
       g = g @ self.kernel.W.to(g).T
@@ -301,9 +382,35 @@ class SVGP:
   def latent_kernels(self):
     return unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)[0]
 
-  def precompute(self, device):
-    """-> Z [L,M,d], ls [L,d], var [L], beta [L,M], C [L,M,M], mean_c [L]|None (float64, device)."""
+  def _mean_weights(self, device, family: int):
+    """-> Z, ls, var, beta = Kuu^-1 u, mean_c: what ``predict_mean`` needs.  SquaredExponential: ``precompute``'s; a Matern model
+    (which ``precompute`` refuses) from its own Gram matrix."""
+    if family == KERNEL_SE:
+      Z, ls, var, beta, _, mean_c = self.precompute(device)
+      return Z, ls, var, beta, mean_c
     kernels, Zs = unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)
+    Z, ls, var = _stack_kernel_params(kernels, Zs, device)
+    L, M, d = Z.shape
+    A = Z / ls[:, None, :]
+    Kuu = var[:, None, None] * stationary_profile(_scaled_sqdist(A, A), family)
+    Luu = cholesky(Kuu + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=device))
+    v = self.q_mu.to(device=device, dtype=DEFAULT_FLOAT).T.unsqueeze(-1)
+    if not self.whiten:
+      v = torch.linalg.solve_triangular(Luu, v, upper=False)
+    beta = torch.linalg.solve_triangular(Luu.transpose(1, 2), v, upper=True).squeeze(-1)
+    mean_c = None
+    if isinstance(self.mean_function, Constant):
+      if not isinstance(self.kernel, LinearCoregionalization):
+        mean_c = self.mean_function.c.to(device=device, dtype=DEFAULT_FLOAT).expand(L).contiguous()
+    elif not isinstance(self.mean_function, Zero):
+      raise NotImplementedError
+    return Z, ls, var, beta, mean_c
+
+  def precompute(self, device):
+    """-> Z [L,M,d], ls [L,d], var [L], beta [L,M], C [L,M,M], mean_c [L]|None (float64, device).  SquaredExponential latents
+    only: what is computed here feeds the moment-matching kernels."""
+    kernels, Zs = unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)
+    require_squared_exponential(kernels, "SVGP.precompute")
     Z, ls, var = _stack_kernel_params(kernels, Zs, device)
     L, M, d = Z.shape
     A = Z / ls[:, None, :]
@@ -333,6 +440,7 @@ class SVGP:
     return Z, ls, var, beta, C, mean_c
 
   def packed(self, dtype, with_C: bool, device):
+    """(A Matern model is refused by ``precompute``, which every cache miss runs: nothing is checked per call.)"""
     return self._cache.get(self, dtype, with_C, device)
 
 
@@ -373,6 +481,7 @@ class GPR:
       Y = Y - c
     elif not isinstance(self.mean_function, Zero):
       raise NotImplementedError
+    require_squared_exponential([self.kernel], "GPR.precompute")
     Z, ls, var = _stack_kernel_params([self.kernel], [X], device)
     N = X.shape[0]
     Kyy = self.kernel.K(X) + self.likelihood.variance.to(X) * torch.eye(N, dtype=DEFAULT_FLOAT, device=device)

@@ -17,6 +17,7 @@ from functools import partial
 import torch
 
 from .. import ops
+from ..models import require_squared_exponential
 from ..models import (GPR, SVGP, Constant, InverseLinkWrapper, KernelRegressor,
                       LinearCoregionalization, Zero)
 from .core import Chain, LinearOperatorDiag, dispatcher
@@ -58,6 +59,8 @@ def _run_kernels(x: GaussianMoments, model, full_output_cov, model_uncertainty, 
   kernels = model.latent_kernels
   mu, Sxx, union = _sliced_state(x, kernels)
   if not mu.is_cuda:
+    require_squared_exponential(kernels, "moment_matching")      # (a Matern model names its own reason; on the GPU the pack's
+                                                                 # cache miss does: SVGP.precompute -- nothing is checked per step)
     raise RuntimeError("moment matching of GP models runs on the GPU only (no CPU fallback)")
   lead = mu.shape[:-1]
   d = mu.shape[-1]

@@ -13,6 +13,11 @@ draw neither allocates nor synchronises and can be captured in a HIP graph.  Pat
 -- the per-step hot loop -- runs in ``mm_pathwise_eval`` / ``mm_pathwise_rollout``
 (``csrc/mm_pathwise.hip``).  Parity with gpflow_sampling is unpinned (see
 ``oracle/pathwise_oracle.py``).
+
+The latents of a model are ``SquaredExponential``, ``Matern32`` or ``Matern52`` (one family per model: ``models.kernel_family``).
+The family changes three things -- the distribution of the random-Fourier frequencies (``spectral_frequencies``), the Gram matrix
+the update weights are solved with, and the basis value of the stream pass's update half (``Paths.kernel``: the ``_kern`` entries
+of the C ABI) -- and nothing else: layouts, tapes and reverse sweeps are shared.
 """
 from __future__ import annotations
 
@@ -26,12 +31,49 @@ import torch
 from .linalg import cholesky
 
 from . import _lib
-from .models import (DEFAULT_FLOAT, DEFAULT_JITTER, SVGP, Constant, LinearCoregionalization, Zero, _stack_kernel_params,
-                     unpack_multioutput)
+from .models import (DEFAULT_FLOAT, DEFAULT_JITTER, KERNEL_NAMES, KERNEL_SE, SVGP, Constant, LinearCoregionalization, Zero,
+                     _scaled_sqdist, _stack_kernel_params, kernel_family, stationary_profile, unpack_multioutput)
 from .ops import _dtype_code, _ptr, _require_device, _stream, check
 
 
 BOUND_ULPS = 8.0      # Paths.eval_with_bound: rounding bound = BOUND_ULPS x unit roundoff x the sum of the absolute terms
+
+
+def _kernel_code(kernel) -> int:
+  """"se" | "matern32" | "matern52" (or the code 0 | 1 | 2) -> the C ABI's kernel argument."""
+  if isinstance(kernel, str):
+    if kernel not in KERNEL_NAMES:
+      raise ValueError(f"kernel {kernel!r}: expected one of {KERNEL_NAMES}")
+    return KERNEL_NAMES.index(kernel)
+  if int(kernel) not in range(len(KERNEL_NAMES)):
+    raise ValueError(f"kernel code {kernel}: expected 0 (se), 1 (matern32) or 2 (matern52)")
+  return int(kernel)
+
+
+def spectral_frequencies(n: torch.Tensor, ls: torch.Tensor, family: int, chi: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """The random-Fourier frequencies of a kernel family from standard normals: n [L, K, d], lengthscales ls [L, d] ->
+  omega [L, K, d].  SquaredExponential: n / ls (its spectral density is Gaussian).  Matern-nu: a multivariate Student-t with
+  2 nu degrees of freedom, omega = (n / ls) sqrt(2 nu / chi2) with one chi2_{2 nu} per (latent, basis function) -- the sum of
+  the squares of the 2 nu (3 or 5) standard normals ``chi`` [L, K, 2 nu].  Plain torch: runs on any device."""
+  if family == KERNEL_SE:
+    return n / ls[:, None, :]
+  dof = 3 if family == 1 else 5
+  if chi is None or chi.shape != n.shape[:2] + (dof,):
+    raise ValueError(f"a Matern draw needs chi [L, K, {dof}] standard normals")
+  # (scale first, then the lengthscales: the order of PathSampler, whose basis kernel does the division)
+  return (n * (chi * chi).sum(-1).reciprocal().mul(float(dof)).sqrt()[:, :, None]) / ls[:, None, :]
+
+
+def _gram(Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor, family: int) -> torch.Tensor:
+  """Kuu + jitter [L, M, M] of the family (SquaredExponential: the expression the samplers have always used)."""
+  A = Z / ls[:, None, :]
+  M = Z.shape[1]
+  if family == KERNEL_SE:
+    d2 = (A * A).sum(-1)[:, :, None] + (A * A).sum(-1)[:, None, :] - 2.0 * A @ A.transpose(1, 2)
+    prof = torch.exp(-0.5 * d2.clamp_min(0.0))
+  else:
+    prof = stationary_profile(_scaled_sqdist(A, A), family)
+  return var[:, None, None] * prof + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=Z.device)
 
 
 def _pad_last(t: torch.Tensor, mult: int) -> torch.Tensor:
@@ -61,6 +103,7 @@ class Paths:
   mean_c: Optional[torch.Tensor]  # [L] f64 or None
   mix_W: Optional[torch.Tensor] = None   # [nx, Lg] f64: f = W g + c (None: the latents are the outputs)
   mix_c: Optional[torch.Tensor] = None   # [nx] f64 or None
+  kernel: int = 0                        # the latents' family: 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2 (every entry routes on it)
 
   @property
   def dtype(self):
@@ -83,6 +126,11 @@ class Paths:
     g = self._latent_values(x)
     return g if self.mix_W is None else self._mixed_values(g)
 
+  def _entry(self, name: str):
+    """The ABI entry of these paths' kernel family and its trailing arguments: SquaredExponential paths call the entries they
+    always have, Matern paths the ``_kern`` siblings."""
+    return (name, ()) if self.kernel == 0 else (name + "_kern", (int(self.kernel),))
+
   def _latent_values(self, x: torch.Tensor) -> torch.Tensor:
     _require_device(x, self.wb)
     S, L, Mp, Kp, d = self._dims()
@@ -90,12 +138,13 @@ class Paths:
       raise ValueError(f"expected x [{S},{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
     x = x.contiguous()
     out = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    rc = _lib.lib().mm_pathwise_eval(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                     self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                     self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                     self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                     out.data_ptr(), _stream(x.device))
-    check(rc, "mm_pathwise_eval")
+    entry, kern = self._entry("mm_pathwise_eval")
+    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
+                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
+                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
+                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
+                                    out.data_ptr(), _stream(x.device), *kern)
+    check(rc, entry)
     return out
 
   def eval_jac(self, x: torch.Tensor):
@@ -114,12 +163,13 @@ class Paths:
     x = x.contiguous()
     out = torch.empty(S, L, dtype=self.dtype, device=x.device)
     jac = torch.empty(S, L, d, dtype=self.dtype, device=x.device)
-    rc = _lib.lib().mm_pathwise_eval_jac(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                         self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                         self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                         self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                         out.data_ptr(), jac.data_ptr(), _stream(x.device))
-    check(rc, "mm_pathwise_eval_jac")
+    entry, kern = self._entry("mm_pathwise_eval_jac")
+    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
+                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
+                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
+                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
+                                    out.data_ptr(), jac.data_ptr(), _stream(x.device), *kern)
+    check(rc, entry)
     return out, jac
 
   def eval_with_bound(self, x: torch.Tensor):
@@ -141,12 +191,13 @@ class Paths:
     x = x.contiguous()
     out = torch.empty(S, L, dtype=self.dtype, device=x.device)
     ab = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    rc = _lib.lib().mm_pathwise_eval_bound(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                           self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                           self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                           self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                           out.data_ptr(), ab.data_ptr(), _stream(x.device))
-    check(rc, "mm_pathwise_eval_bound")
+    entry, kern = self._entry("mm_pathwise_eval_bound")
+    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
+                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
+                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
+                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
+                                    out.data_ptr(), ab.data_ptr(), _stream(x.device), *kern)
+    check(rc, entry)
     # unit roundoff u = finfo.eps / 2; v and the basis value each carry ~u, the exponent's own rounding (|arg| up to ~20 at the
     # C5 shape) a few u more: BOUND_ULPS u covers the measured worst case with a factor ~2 in hand (tests/test_pathwise.py)
     return out, ab * (BOUND_ULPS * 0.5 * torch.finfo(self.dtype).eps)
@@ -167,12 +218,13 @@ class Paths:
     x = x0.contiguous().clone()
     tmp = torch.empty_like(x)
     traj = torch.empty(num_steps, S, d, dtype=self.dtype, device=x.device) if keep_trajectory else None
-    rc = _lib.lib().mm_pathwise_rollout(S, L, Mp, Kp, d, _dtype_code(self.dtype), int(num_steps), float(dt),
-                                        x.data_ptr(), tmp.data_ptr(), self.omega.data_ptr(), self.phase.data_ptr(),
-                                        self.zs.data_ptr(), self.hz.data_ptr(), self.lengthscales.data_ptr(),
-                                        self.prior_scale.data_ptr(), self.variance.data_ptr(), _ptr(self.mean_c),
-                                        self.wb.data_ptr(), _ptr(traj), _stream(x.device))
-    check(rc, "mm_pathwise_rollout")
+    entry, kern = self._entry("mm_pathwise_rollout")
+    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), int(num_steps), float(dt),
+                                    x.data_ptr(), tmp.data_ptr(), self.omega.data_ptr(), self.phase.data_ptr(),
+                                    self.zs.data_ptr(), self.hz.data_ptr(), self.lengthscales.data_ptr(),
+                                    self.prior_scale.data_ptr(), self.variance.data_ptr(), _ptr(self.mean_c),
+                                    self.wb.data_ptr(), _ptr(traj), _stream(x.device), *kern)
+    check(rc, entry)
     return (x, traj) if keep_trajectory else x
 
 
@@ -192,9 +244,11 @@ class _PathsEval(torch.autograd.Function):
 
 
 def paths_from_arrays(omega, phase, w, v, Z, lengthscales, variance, mean_c=None, dtype=torch.float32,
-                      device="cuda", mix_W=None, mix_c=None) -> Paths:
+                      device="cuda", mix_W=None, mix_c=None, kernel="se") -> Paths:
   """Build ``Paths`` from explicit arrays (omega [L,K,d], phase [L,K], w [S,L,K], v [S,L,M], Z [L,M,d]).  ``mix_W`` [nx, L] (and
-  ``mix_c`` [nx] or None): the mixing of a coregionalised model; the latents then have no mean of their own."""
+  ``mix_c`` [nx] or None): the mixing of a coregionalised model; the latents then have no mean of their own.  ``kernel``: the
+  family of every latent, "se" | "matern32" | "matern52" (or its code)."""
+  kernel = _kernel_code(kernel)
   t64 = lambda a: torch.as_tensor(a, dtype=DEFAULT_FLOAT, device=device)
   if mix_W is None and mix_c is not None:
     raise ValueError("mix_c without mix_W")
@@ -228,7 +282,8 @@ def paths_from_arrays(omega, phase, w, v, Z, lengthscales, variance, mean_c=None
   wb = allw.reshape(G, 4, L, NB, mult).permute(0, 2, 3, 1, 4).to(dtype).contiguous()
   return Paths(omega=omega_p, phase=padk(t64(phase) / two_pi), zs=zs_p, hz=padk(hz), wb=wb, num_samples=S,
                lengthscales=xscale.contiguous(), prior_scale=torch.sqrt(2.0 * var / K).contiguous(),
-               variance=var.contiguous(), mean_c=None if mean_c is None else t64(mean_c).contiguous(), mix_W=mix_W, mix_c=mix_c)
+               variance=var.contiguous(), mean_c=None if mean_c is None else t64(mean_c).contiguous(), mix_W=mix_W, mix_c=mix_c,
+               kernel=kernel)
 
 
 def _mean_and_mixing(model: SVGP, L: int, device):
@@ -252,20 +307,21 @@ def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=t
   """Draw S decoupled sample paths of an SVGP: random-Fourier prior + inducing-point update
   (gpflow_sampling's decoupled sampler; ``loops/pilco.py:281-284``)."""
   kernels, Zs = unpack_multioutput(model.kernel, model.inducing_variable, model.num_latent_gps)
+  family = kernel_family(kernels)
   Z, ls, var = _stack_kernel_params(kernels, Zs, device)
   L, M, d = Z.shape
   S, K = num_samples, num_bases
   rn = lambda *shape: torch.randn(*shape, dtype=DEFAULT_FLOAT, device=device, generator=generator)
-  omega = rn(L, K, d) / ls[:, None, :]
+  n = rn(L, K, d)
   phase = 2.0 * math.pi * torch.rand(L, K, dtype=DEFAULT_FLOAT, device=device, generator=generator)
   w = rn(S, L, K)
-  A = Z / ls[:, None, :]
-  d2 = (A * A).sum(-1)[:, :, None] + (A * A).sum(-1)[:, None, :] - 2.0 * A @ A.transpose(1, 2)
-  Kuu = var[:, None, None] * torch.exp(-0.5 * d2.clamp_min(0.0)) + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=device)
-  Luu = cholesky(Kuu)
+  Luu = cholesky(_gram(Z, ls, var, family))
   q_mu = model.q_mu.to(device=device, dtype=DEFAULT_FLOAT).T                       # [L, M]
   q_sqrt = torch.tril(model.q_sqrt.to(device=device, dtype=DEFAULT_FLOAT))          # [L, M, M]
   eps = rn(S, L, M)
+  # a Matern model's chi2 normals come AFTER every draw a SquaredExponential model makes: SE draws from a generator state are
+  # what they always were, and PathSampler draws in the same order
+  omega = spectral_frequencies(n, ls, family, None if family == KERNEL_SE else rn(L, K, 3 if family == 1 else 5))
   u = q_mu[None] + torch.einsum('slm,lnm->sln', eps, q_sqrt)                       # samples of q(u)
   if model.whiten:
     u = torch.einsum('lnm,slm->sln', Luu, u)
@@ -273,7 +329,8 @@ def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=t
   resid = u - torch.einsum('lmk,slk->slm', Phi_Z, w)
   v = torch.cholesky_solve(resid.permute(1, 2, 0), Luu).permute(2, 0, 1)             # [S, L, M]
   mean_c, mix_W, mix_c = _mean_and_mixing(model, L, device)
-  return paths_from_arrays(omega, phase, w, v, Z, ls, var, mean_c, dtype=dtype, device=device, mix_W=mix_W, mix_c=mix_c)
+  return paths_from_arrays(omega, phase, w, v, Z, ls, var, mean_c, dtype=dtype, device=device, mix_W=mix_W, mix_c=mix_c,
+                           kernel=family)
 
 
 class PathSampler:
@@ -311,7 +368,8 @@ class PathSampler:
     params = list(model._parameters())                       # (the Constant mean's tensor is one of them)
     if isinstance(model.kernel, LinearCoregionalization):
       params.append(model.kernel.W)
-    key = tuple((id(t), t._version, t.device) for t in params)
+    family = kernel_family(model.latent_kernels)
+    key = tuple((id(t), t._version, t.device) for t in params) + (family,)
     if key == self._key:
       return
     if torch.cuda.is_current_stream_capturing():
@@ -323,10 +381,7 @@ class PathSampler:
       L, M, d = Z.shape
       if d > _lib.MM_DMAX:
         raise ValueError(f"PathSampler: input dimension {d} exceeds MM_DMAX = {_lib.MM_DMAX}")
-      A = Z / ls[:, None, :]
-      d2 = (A * A).sum(-1)[:, :, None] + (A * A).sum(-1)[:, None, :] - 2.0 * A @ A.transpose(1, 2)
-      Kuu = var[:, None, None] * torch.exp(-0.5 * d2.clamp_min(0.0)) + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=dev)
-      Luu = cholesky(Kuu)
+      Luu = cholesky(_gram(Z, ls, var, family))
       q_mu = model.q_mu.to(device=dev, dtype=DEFAULT_FLOAT).T                        # [L, M]
       q_sqrt = torch.tril(model.q_sqrt.to(device=dev, dtype=DEFAULT_FLOAT))           # [L, M, M]
       c, T = q_mu.unsqueeze(-1), q_sqrt
@@ -341,18 +396,21 @@ class PathSampler:
       hz = 0.5 * (zs * zs).sum(-1)
       self._const = dict(zs=tt(_pad_last(zs.transpose(1, 2), mult)), hz=tt(_pad_last(hz, mult)), lengthscales=xscale.contiguous(),
                          prior_scale=torch.sqrt(2.0 * var / self.K).contiguous(), variance=var.contiguous(), mean_c=mean_c,
-                         mix_W=mix_W, mix_c=mix_c)
+                         mix_W=mix_W, mix_c=mix_c, kernel=family)
       self._Z, self._ls, self._var = Z.contiguous(), ls.contiguous(), var.contiguous()
       self._Luu, self._LuuT = Luu.contiguous(), Luu.transpose(1, 2)
       self._c, self._T = c.contiguous(), T.contiguous()
-    if self._bufs is None or self._dims != (L, M, d):
-      self._dims = (L, M, d)
+    dof = 0 if family == KERNEL_SE else 3 if family == 1 else 5
+    if self._bufs is None or self._dims != (L, M, d) or self._dof != dof:
+      self._dims, self._dof = (L, M, d), dof
       S, K = self.S, self.K
       f64 = lambda *shape: torch.empty(*shape, dtype=DEFAULT_FLOAT, device=dev)
       Kp, Mp, G = K + (-K) % mult, M + (-M) % mult, (S + 3) // 4
       out = lambda *shape: torch.empty(*shape, dtype=self.dtype, device=dev)
       self._bufs = dict(n=f64(L, K, d), b=f64(L, K), w=f64(S, L, K), eps=f64(S, L, M), phiZ=f64(L, M, K), rhs=f64(L, M, S),
                         omega=out(L, d, Kp), phase=out(L, Kp), wb=out(G, L, (Kp + Mp) // mult, 4, mult))
+      if dof:                                                # the chi2 normals of a Matern draw and the scale they give
+        self._bufs.update(chi=f64(L, K, dof), tscale=f64(L, K))
     self._key = key
 
   @property
@@ -374,6 +432,14 @@ class PathSampler:
       B["b"].uniform_(generator=generator).mul_(2.0 * math.pi)
       B["w"].normal_(generator=generator)
       B["eps"].normal_(generator=generator)
+      if self._dof:
+        # Matern: n <- n sqrt(2 nu / chi2) in place (spectral_frequencies' expressions, into preallocated buffers), drawn after
+        # everything else as generate_paths does; mm_pathwise_basis then divides by the lengthscales as for any family
+        B["chi"].normal_(generator=generator)
+        torch.mul(B["chi"], B["chi"], out=B["chi"])
+        torch.sum(B["chi"], dim=-1, out=B["tscale"])
+        B["tscale"].reciprocal_().mul_(float(self._dof)).sqrt_()
+        B["n"].mul_(B["tscale"].unsqueeze(-1))
       lib, stream = _lib.lib(), _stream(self.device)
       check(lib.mm_pathwise_basis(L, K, M, d, self._code, B["n"].data_ptr(), B["b"].data_ptr(), self._Z.data_ptr(),
                                   self._ls.data_ptr(), self._var.data_ptr(), B["omega"].data_ptr(), B["phase"].data_ptr(),
@@ -385,7 +451,7 @@ class PathSampler:
       torch.linalg.solve_triangular(self._LuuT, rhs, upper=True, out=rhs)                        # v = Kuu^-1 (u - Phi_Z w)
       check(lib.mm_pathwise_pack_stream(S, L, K, M, self._code, B["w"].data_ptr(), rhs.data_ptr(), B["wb"].data_ptr(), stream),
             "mm_pathwise_pack_stream")
-      cp = (lambda t: None if t is None else t.clone()) if clone else (lambda t: t)
+      cp = (lambda t: t.clone() if isinstance(t, torch.Tensor) else t) if clone else (lambda t: t)
       return Paths(omega=cp(B["omega"]), phase=cp(B["phase"]), wb=cp(B["wb"]), num_samples=S,
                    **{k: cp(v) for k, v in self._const.items()})
 
@@ -445,7 +511,11 @@ class PolicyRollout:
 
   Paths with ``mix_W`` (a coregionalised drift: Lg latents mixed to nx outputs, Lg <= nx) run the ``_mixed`` entries -- nd <= 16,
   1 to 4 actions, the ``_nd`` shapes of ``g_policy``; ``wide`` and ``nd_entries`` are then ignored.  The tape's sample slot and
-  Jacobian block are latent-sized (``mm_pathwise_tape_bytes_mixed``); the mixing happens in the head kernel and the reverse sweep."""
+  Jacobian block are latent-sized (``mm_pathwise_tape_bytes_mixed``); the mixing happens in the head kernel and the reverse sweep.
+
+  Paths of a Matern drift (``paths.kernel`` 1 or 2) run the one forward entry ``mm_pathwise_policy_rollout_kern`` for every shape --
+  one action included -- with the ``_wide`` signatures, tape and reverse sweeps (mixed paths: the ``_mixed`` ones): ``wide`` and
+  ``nd_entries`` are then ignored and ``g_policy`` has the ``_nd`` shape.  The policy stays SquaredExponential."""
 
   def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
                target: Optional[torch.Tensor] = None, precis: Optional[torch.Tensor] = None, nd_entries: Optional[bool] = None,
@@ -459,6 +529,9 @@ class PolicyRollout:
     if not 1 <= self.nu <= 4:
       raise ValueError(f"the pathwise policy rollout takes policies with 1 to 4 latents (one per action), got {self.nu}")
     mix_W = getattr(paths, "mix_W", None)
+    self.kernel = int(getattr(paths, "kernel", 0))
+    if self.kernel:                                            # a Matern drift: the one _kern entry (the _wide signatures and tape)
+      wide, nd_entries = True, True
     self.mixed = mix_W is not None
     self.Lg = int(L) if self.mixed else 0
     if self.mixed:
@@ -542,8 +615,10 @@ class PolicyRollout:
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
     if self.nd_entries:
-      entry = "mm_pathwise_policy_rollout_" + ("mixed" if self.mixed else self._sfx)
+      entry = "mm_pathwise_policy_rollout_" + ("kern" if self.kernel else "mixed" if self.mixed else self._sfx)
       mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
+      if self.kernel:
+        mixing = (mixing or (0, None, None)) + (self.kernel,)
       rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
                                P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
                                P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),

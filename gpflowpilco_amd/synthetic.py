@@ -44,10 +44,12 @@ class SyntheticSVGP:
   def shape(self):
     return self.lengthscales.shape[0], self.Z.shape[0], self.Z.shape[1]
 
-  def to_model(self, device="cpu") -> gp.SVGP:
+  def to_model(self, device="cpu", kernel: str = "se") -> gp.SVGP:
+    """``kernel``: the class of every latent kernel, "se" | "matern32" | "matern52" (the same numbers otherwise)."""
     L = self.lengthscales.shape[0]
-    kernels = [gp.SquaredExponential(variance=torch.tensor(self.variance[a], dtype=F64, device=device),
-                                     lengthscales=torch.tensor(self.lengthscales[a], dtype=F64, device=device))
+    cls = {"se": gp.SquaredExponential, "matern32": gp.Matern32, "matern52": gp.Matern52}[kernel]
+    kernels = [cls(variance=torch.tensor(self.variance[a], dtype=F64, device=device),
+                   lengthscales=torch.tensor(self.lengthscales[a], dtype=F64, device=device))
                for a in range(L)]
     Zt = torch.tensor(self.Z, dtype=F64, device=device)
     iv = gp.SharedIndependentInducingVariables(gp.InducingPoints(Zt))

@@ -617,6 +617,48 @@ int mm_pathwise_policy_rollout_backward_mixed(int S, int dtype, int H, double dt
                                               void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream,
                                               int Lg, const double* mix_W);
 
+/* ---- drifts with a Matern kernel: the _kern siblings ------------------------------------------------------------------------
+ * The entries above evaluate SquaredExponential latents.  Their _kern siblings take one more argument, kernel, the family of
+ * EVERY latent of the paths: 0 SquaredExponential (then bit-equal to the entry without the argument, which is this call),
+ * 1 Matern-3/2, 2 Matern-5/2 in gpflow's parametrisation; anything else is MM_E_ARG, refused before any HIP call.  Operands,
+ * layouts, outputs and the other error codes are unchanged: the stream's argument a = zs_t.(x x_scale) - hz - hx is
+ * -(log2 e / 2) r^2 for every family, and the update half's basis value 2^a becomes
+ *   Matern-3/2: (1 + s) e^-s, s = sqrt3 r        Matern-5/2: (1 + s + s^2 / 3) e^-s, s = sqrt5 r        (r^2 = -2 ln2 a, clamped at 0)
+ * The prior half is the same w cos(.); only the distribution the caller draws omega from differs (a multivariate Student-t with
+ * 2 nu degrees of freedom: pathwise.spectral_frequencies).  abs_out of the _bound entry uses the family's basis value.
+ *
+ * mm_pathwise_policy_rollout_kern is the one policy-rollout entry for such a drift: the argument list of
+ * mm_pathwise_policy_rollout_mixed plus kernel; Lg = 0 with mix_W = NULL means no mixing (then mm_pathwise_policy_rollout_wide:
+ * nd <= 16, 1 <= nu <= 4, tape of mm_pathwise_tape_bytes_nd), otherwise the _mixed entry's rules.  The tape layout does not depend
+ * on the family and the reverse sweeps read the drift only through the taped Jacobian: the backward entries are
+ * mm_pathwise_policy_rollout_backward_wide[_seeded] resp. _backward_mixed, as they are. */
+int mm_pathwise_eval_kern(int S, int L, int M, int K, int d, int dtype,
+                          const void* x, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                          const double* x_scale, const double* prior_scale, const double* variance,
+                          const double* mean_c, const void* wb, void* f_out, void* stream, int kernel);
+int mm_pathwise_eval_bound_kern(int S, int L, int M, int K, int d, int dtype,
+                                const void* x, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                                const double* x_scale, const double* prior_scale, const double* variance,
+                                const double* mean_c, const void* wb, void* f_out, void* abs_out, void* stream, int kernel);
+int mm_pathwise_rollout_kern(int S, int L, int M, int K, int d, int dtype, int H, double dt,
+                             void* x, void* x_tmp, const void* omega_t, const void* phase, const void* zs_t,
+                             const void* hz, const double* x_scale, const double* prior_scale,
+                             const double* variance, const double* mean_c, const void* wb,
+                             void* traj, void* stream, int kernel);
+int mm_pathwise_eval_jac_kern(int S, int L, int M, int K, int d, int dtype,
+                              const void* x, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                              const double* x_scale, const double* prior_scale, const double* variance,
+                              const double* mean_c, const void* wb, void* f_out, void* jac_out, void* stream, int kernel);
+int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                    int nu, const void* omega_t, const void* phase, const void* zs_t, const void* hz,
+                                    const double* x_scale, const double* prior_scale, const double* variance,
+                                    const double* mean_c, const void* wb,
+                                    const void* policy_packed, size_t policy_bytes, int policy_M,
+                                    const double* head_scale, const double* head_shift,
+                                    const void* target, const void* precis, const void* x0, void* cost,
+                                    void* tape, size_t tape_bytes, int with_jacobians, void* stream,
+                                    int Lg, const double* mix_W, const double* mix_c, int kernel);
+
 /* ---- path GENERATION: the two reformatting steps of a draw (csrc/mm_pathwise_sample.hip) -----------------------------------
  * PathwisePILCO draws new paths on every optimiser step (loops/pilco.py:281-284).  Between the random draws, two GEMMs and two
  * triangular solves (the caller's: pathwise.PathSampler keeps them on torch's BLAS with a cached Kuu factor) a draw is
