@@ -1,47 +1,90 @@
-// Pathwise POLICY rollout and its reverse sweep on gfx950 -- SURVEY.md row f-3 completed (rounds 1-3 had the drift
-// evaluation and a drift-only Euler fold).
+// Pathwise POLICY rollout and its reverse sweep on gfx950, for policies with nu = 1 .. 4 actions -- SURVEY.md row f-3 (the
+// cartpole's wiring: nx 4, one angle, one force; the double pendulum's: nx 4, two angles, two torques).
 //
 // What the reference's only caller of sample paths runs and differentiates (PathwisePILCO._policy_loss_closure,
 // gpflow_pilco/loops/pilco.py:263-298; the tensor branch of forward_sde, dynamics/forward_sde.py:23-31; Euler.step,
 // dynamics/solvers.py:50-65; the mean over samples and the gradient tape: examples/cartpole_swingup/train_utils.py:108-135).
-// Per sample path s and step h:
-//     e  = encoder(x_h)              TrigonometricEncoder on tensors: [sin a, cos a, x_inactive]   (components.py:44-75)
-//     u  = scale (Phi(f_pol(e)) + shift),  f_pol(e) = sum_m beta_m k(e, z_m) + c                   (models/core.py:60-71: the
+// On sample paths the policy is evaluated pointwise, so the head has no cross moments: per sample path s and step h
+//     e   = encoder(x_h)                  TrigonometricEncoder on tensors: [sin a, cos a, x_inactive]   (components.py:44-75)
+//     u_a = scale_a (Phi(f_a(e)) + shift_a),  a < nu,   f_a(e) = sum_m beta_am k_a(e, z_am) + c_a       (models/core.py:60-71: the
 //                                          KernelRegressor's predictive MEAN through Chain[Scale, Shift, NormalCDF])
-//     x_{h+1} = x_h + dt f_s([e, u])     f_s: the s-th drift sample path (mm_pathwise.hip: a weight stream, HBM-bound)
-//     cost[h][s] = -exp(-(enc(x_{h+1}) - t)^T W (enc(x_{h+1}) - t) / 2)                              (components.py:39-41)
-// Forward: per step one small kernel (k_pw_head: Euler update of the previous step, cost, encoder, policy -> the drift's
-// input) and one stream pass; the taped forward makes the stream pass also emit d f_s / d d_s [S][nx][nd] (its JAC variant).
-// Backward: samples are independent, so the WHOLE reverse sweep is one kernel (k_pw_policy_bwd: thread = sample, loop over
+//     x_{h+1} = x_h + dt f_s([e, u_0 .. u_{nu-1}])   f_s: the s-th drift sample path (mm_pathwise.hip: a weight stream, HBM-bound);
+//                                          nd = ne + nu drift inputs, actions in latent order (as forward_sde appends them)
+//     cost[h][s] = -exp(-(enc(x_{h+1}) - t)^T W (enc(x_{h+1}) - t) / 2)                                  (components.py:39-41)
+// Forward: per step one small kernel (k_pw_head_nd: Euler update of the previous step, cost, encoder, policy -> the drift's
+// input) and one stream pass (mm_pathwise_launch, d <= 16, as it is); the taped forward makes the stream pass also emit
+// d f_s / d d_s [S][nx][nd] (its JAC variant).
+// Backward: samples are independent, so the WHOLE reverse sweep is one kernel (k_pw_policy_bwd_nd: thread = sample, loop over
 // the steps backwards, the state's adjoint in registers) that reads the tape -- states, drift inputs, Jacobians: no second
 // pass over the weight stream -- and accumulates the packed policy's gradient per wave (fixed-order wave sums -> per-wave
-// slabs -> k_pw_grad_sum: deterministic).  All small algebra in f64 whatever the paths' element type.
+// slabs -> k_pw_grad_sum: deterministic).  All small algebra in f64 whatever the paths' element type.  The policy is an ordinary
+// mm_pack_model pack with L = nu; only its f64 blocks are read (Z64 [L][M][ne], beta64 [L][M], ls2 [L][ne], var [L], meanc [L]).
+//
+// Every set of entries is ONE implementation (mmp_nd_rollout, mmp_nd_backward): the one-action entries (scalar head constants,
+// nu = 1, nd <= 8), the _nd entries (nd <= 8), the _wide entries (same signatures, nd <= 16 -- the cart-double-pendulum: nx 6,
+// two angles, one force: nd 9; a three-link arm: nd 13), the _kern entry (a drift of any kernel family), and
+// the _mixed entries (nd <= 16), which take a COREGIONALISED drift f = W g + c: the stream pass runs with the Lg <= nx
+// latents into a latent-sized tape (sample slot [S][Lg], Jacobians [H][S][Lg][nd]) and both kernels mix in place of a launch of
+// its own (bool MIXED: the head steps x += dt (c + W g), the sweep takes g d = dt J_g^T (W^T g x)).
+//
+// Both kernels are templates in the action count: the loops over the latents unroll and the per-latent constants sit in
+// registers.
+//
+// LDS of the reverse sweep (doubles per workgroup of four waves): the nu policy blocks nu (M ne + M + ne), target and W
+// (ne + ne^2, + 8 spare), and one gradient slab per wave 4 nu (M ne + M + ne + 2).  The kernel takes a shape when
+//     8 (nu (M ne + M + ne) + ne + ne^2 + 8 + 4 nu (M ne + M + ne + 2))  <=  160 KiB        (MMP_ND_LDS_MAX)
+// -- every shape with M <= 64 and ne + nu <= 16 (tightest: nu 4, ne 12, which stops at M = 77); within ne + nu <= 8 at M = 256: nu (ne + 1) <= 15, i.e. nu = 1
+// (any ne <= 7), nu = 2 (ne <= 6: the double pendulum, 144 KB), nu = 3 with ne <= 4; not nu = 3 with ne = 5 (M <= 226 fits) and
+// not nu = 4 with ne = 4 (M <= 203 fits).  mm_pathwise_backward_scratch_bytes_nd / _wide return 0 and the entries MM_E_DIM beyond it.
+// (The one-action entries never meet it: nu = 1, ne <= 7, M <= 256 is at most 83032 bytes.)
 #include "mm_pathwise_policy_dev.h"
 
-// k_pw_head: grid ceil(S / 256), thread = sample.  h in [0, H]:
-//   h > 0: x_h = x_{h-1} + dt f_{h-1} -> tape; cost[h-1][s] of its encoding;    h < H: the drift input (e_h, u_h) -> tape.
-template <typename T>
-__global__ __launch_bounds__(256) void k_pw_head(MMComposeDims D, int S, int h, int H, double dt, const T* __restrict__ xprev,
-                                                 const T* __restrict__ f, T* __restrict__ xcur, T* __restrict__ din,
-                                                 T* __restrict__ cost, const T* __restrict__ target, const T* __restrict__ precis,
-                                                 const double* __restrict__ pZ, const double* __restrict__ pbeta,
-                                                 const double* __restrict__ pls2, const double* __restrict__ pvar,
-                                                 const double* __restrict__ pmean, int pM, double scale, double shift) {
+#define MMP_ND_LDS_MAX ((size_t)160 * 1024)
+
+
+// k_pw_head_nd: grid ceil(S / 256), thread = sample.  h in [0, H]:
+//   h > 0: x_h = x_{h-1} + dt f_{h-1} -> tape; cost[h-1][s] of its encoding;    h < H: the drift input (e_h, u_h[nu]) -> tape.
+// LDS: the NU policy blocks one after the other (each Z [M][ne] | beta [M] | 1 / ls2 [ne]), target [ne], W [ne][ne].
+// MIXED (the _mixed entries: a coregionalised drift): f is the LATENT sample g [S][Lg] and the step is
+//   x_{h+1,i} = x_{h,i} + dt (c_i + sum_l mixW[i][l] g_l),   mixW [nx][Lg], mixc [nx] or NULL: f64 in global memory, read at
+// wave-uniform addresses (scalar loads; nothing of it in LDS).  MIXED = false: Lg, mixW, mixc are not read.
+template <typename T, int NU, bool MIXED>
+__global__ __launch_bounds__(256) void k_pw_head_nd(MMComposeDims D, int S, int h, int H, double dt, const T* __restrict__ xprev,
+                                                    const T* __restrict__ f, T* __restrict__ xcur, T* __restrict__ din,
+                                                    T* __restrict__ cost, const T* __restrict__ target,
+                                                    const T* __restrict__ precis, const double* __restrict__ pZ,
+                                                    const double* __restrict__ pbeta, const double* __restrict__ pls2,
+                                                    const double* __restrict__ pvar, const double* __restrict__ pmean, int pM,
+                                                    MMHeadND hd, int Lg, const double* __restrict__ mixW,
+                                                    const double* __restrict__ mixc) {
   extern __shared__ double sm[];
-  const int nx = D.nx, ne = D.ne, nd = D.nd;
-  double* pol = sm;                                        // M ne + M + ne
-  double* tg = pol + pM * ne + pM + ne;                    // [ne]
+  const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne;
+  double* pol = sm;                                        // [NU][M ne + M + ne]
+  double* tg = pol + NU * blk;                             // [ne]
   double* W = tg + ne;                                     // [ne][ne]
   for (int i = threadIdx.x; i < ne; i += 256) tg[i] = (double)target[i];
   for (int i = threadIdx.x; i < ne * ne; i += 256) W[i] = (double)precis[i];
-  mmp_stage_policy<T>(pZ, pbeta, pls2, pM, ne, pol);
+#pragma unroll
+  for (int a = 0; a < NU; ++a)
+    mmp_stage_policy<T>(pZ + (size_t)a * pM * ne, pbeta + (size_t)a * pM, pls2 + (size_t)a * ne, pM, ne, pol + a * blk);
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= S) return;
   double x[MMC_NX], e[MMP_NE];
   if (h > 0) {
-    for (int i = 0; i < nx; ++i) {
-      x[i] = (double)xprev[(size_t)s * nx + i] + dt * (double)f[(size_t)s * nx + i];   // Euler.step, solvers.py:50-65
-      xcur[(size_t)s * nx + i] = (T)x[i];
+    if (MIXED) {
+      double g[MMC_NX];
+      for (int l = 0; l < Lg; ++l) g[l] = (double)f[(size_t)s * Lg + l];
+      for (int i = 0; i < nx; ++i) {
+        double fi = mixc ? mixc[i] : 0.0;                    // the constant is added after the mixing; latent order
+        for (int l = 0; l < Lg; ++l) fi = fma(mixW[i * Lg + l], g[l], fi);
+        x[i] = (double)xprev[(size_t)s * nx + i] + dt * fi;
+        xcur[(size_t)s * nx + i] = (T)x[i];
+      }
+    } else {
+      for (int i = 0; i < nx; ++i) {
+        x[i] = (double)xprev[(size_t)s * nx + i] + dt * (double)f[(size_t)s * nx + i];   // Euler.step, solvers.py:50-65
+        xcur[(size_t)s * nx + i] = (T)x[i];
+      }
     }
   } else {
     for (int i = 0; i < nx; ++i) x[i] = (double)xcur[(size_t)s * nx + i];
@@ -51,45 +94,54 @@ __global__ __launch_bounds__(256) void k_pw_head(MMComposeDims D, int S, int h, 
   mmp_encode(D, x, e);
   if (h > 0) cost[(size_t)(h - 1) * S + s] = (T)mmp_cost(ne, e, tg, W, nullptr);
   if (h < H) {
-    const MMPwPolicy P{pol, pol + pM * ne, pol + pM * ne + pM, pvar[0], pmean[0], pM};
-    const double u = scale * (mmp_ndtr(mmp_policy_mean(ne, P, e)) + shift);
     for (int i = 0; i < ne; ++i) din[(size_t)s * nd + i] = (T)e[i];
-    din[(size_t)s * nd + ne] = (T)u;
+#pragma unroll
+    for (int a = 0; a < NU; ++a) {
+      const double* pa = pol + a * blk;
+      const MMPwPolicy P{pa, pa + pM * ne, pa + pM * ne + pM, pvar[a], pmean[a], pM};
+      const double u = hd.scale[a] * (mmp_ndtr(mmp_policy_mean(ne, P, e)) + hd.shift[a]);
+      din[(size_t)s * nd + ne + a] = (T)u;
+    }
   }
 }
 
-// k_pw_policy_bwd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][npar] (ASSIGNED): per wave the
-// sum over its 64 samples and all steps of the packed policy's gradient (dZ [M][ne], dbeta [M], dls2 [ne], dvar, dmean);
-// g_x0 [S][nx] (optional).  g_cost [H][S] f64.
-// SEEDED (the _seeded entry with a seed on the states, or without the built-in cost): g_x [H][S][nx] f64, block h = d loss /
-// d x_{h+1}, one more term in the adjoint of x_{h+1} (NULL: none); g_cost NULL: the built-in cost is not part of the loss, its
-// term is skipped.  SEEDED = false is the sweep of the built-in cost alone (g_x is not read).
-template <typename T, bool SEEDED>
-__global__ __launch_bounds__(256) void k_pw_policy_bwd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
-                                                       const T* __restrict__ dins, const T* __restrict__ jacs,
-                                                       const double* __restrict__ g_cost, const double* __restrict__ g_x,
-                                                       const T* __restrict__ target, const T* __restrict__ precis,
-                                                       const double* __restrict__ pZ, const double* __restrict__ pbeta,
-                                                       const double* __restrict__ pls2, const double* __restrict__ pvar,
-                                                       const double* __restrict__ pmean, int pM, double scale, double shift,
-                                                       double* __restrict__ gpart,
-                                                       double* __restrict__ g_x0) {
+// k_pw_policy_bwd_nd: grid ceil(S / 256), thread = sample, all H steps backwards.  gpart [nwaves][NU][npar1] (ASSIGNED): per
+// wave the sum over its 64 samples and all steps of the packed policy's gradient, per latent dZ [M][ne], dbeta [M], dls2 [ne],
+// dvar, dmean (npar1 = M ne + M + ne + 2);  g_x0 [S][nx] (optional).  g_cost [H][S] f64.
+// SEEDED (the _seeded entries with a seed on the states, or without the built-in cost): g_x [H][S][nx] f64, block h = d loss /
+// d x_{h+1} (NULL: none); g_cost NULL: the built-in cost's term is skipped.  SEEDED = false: the built-in cost alone.
+// MIXED: jacs is the LATENT Jacobian tape [H][S][Lg][nd] and g d = dt J_g^T (mixW^T g x_{h+1}) in two steps (mixW as in the head
+// kernel: global memory, wave-uniform addresses); everything else is the unmixed sweep.
+template <typename T, int NU, bool SEEDED, bool MIXED>
+__global__ __launch_bounds__(256) void k_pw_policy_bwd_nd(MMComposeDims D, int S, int H, double dt, const T* __restrict__ xs,
+                                                          const T* __restrict__ dins, const T* __restrict__ jacs,
+                                                          const double* __restrict__ g_cost, const double* __restrict__ g_x,
+                                                          const T* __restrict__ target, const T* __restrict__ precis,
+                                                          const double* __restrict__ pZ, const double* __restrict__ pbeta,
+                                                          const double* __restrict__ pls2, const double* __restrict__ pvar,
+                                                          const double* __restrict__ pmean, int pM, MMHeadND hd,
+                                                          double* __restrict__ gpart,
+                                                          double* __restrict__ g_x0, int Lg,
+                                                          const double* __restrict__ mixW) {
   extern __shared__ double sm[];
-  const int nx = D.nx, ne = D.ne, nd = D.nd, npar = pM * ne + pM + ne + 2;
+  const int nx = D.nx, ne = D.ne, nd = D.nd, blk = pM * ne + pM + ne, npar1 = blk + 2, npar = NU * npar1;
   double* pol = sm;
-  double* tg = pol + pM * ne + pM + ne;
+  double* tg = pol + NU * blk;
   double* W = tg + ne;
-  double* acc = W + ne * ne;                               // [4 waves][npar]
+  double* acc = W + ne * ne;                               // [4 waves][NU][npar1]
   for (int i = threadIdx.x; i < ne; i += 256) tg[i] = (double)target[i];
   for (int i = threadIdx.x; i < ne * ne; i += 256) W[i] = (double)precis[i];
   for (int i = threadIdx.x; i < 4 * npar; i += 256) acc[i] = 0.0;
-  mmp_stage_policy<T>(pZ, pbeta, pls2, pM, ne, pol);
+#pragma unroll
+  for (int a = 0; a < NU; ++a)
+    mmp_stage_policy<T>(pZ + (size_t)a * pM * ne, pbeta + (size_t)a * pM, pls2 + (size_t)a * ne, pM, ne, pol + a * blk);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double* wacc = acc + wv * npar;
   const int s = blockIdx.x * 256 + threadIdx.x;
   const bool live = s < S;
   const int sr = live ? s : S - 1;                         // (idle lanes recompute the last sample with zero adjoints)
-  const MMPwPolicy P{pol, pol + pM * ne, pol + pM * ne + pM, pvar[0], pmean[0], pM};
+  double var[NU], mean[NU];
+#pragma unroll
+  for (int a = 0; a < NU; ++a) { var[a] = pvar[a]; mean[a] = pmean[a]; }
   double gx[MMC_NX];
   for (int i = 0; i < nx; ++i) gx[i] = 0.0;
   for (int h = H - 1; h >= 0; --h) {
@@ -108,44 +160,66 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd(MMComposeDims D, int S, i
       mmp_encode_bwd(D, x1, ge, gx);
     }
     // x_{h+1} = x_h + dt f(d_h):  g d = dt J^T g x_{h+1}
-    double gd[MMP_NE + 1], e[MMP_NE];
-    const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
-    for (int k = 0; k < nd; ++k) {
-      double r = 0.0;
-      for (int i = 0; i < nx; ++i) r = fma((double)J[i * nd + k], gx[i], r);
-      gd[k] = dt * r;
+    double gd[MMP_NE + MMC_NU], e[MMP_NE];
+    if (MIXED) {
+      double gg[MMC_NX];                                     // adjoint of the latent sample: gg = mixW^T g x_{h+1}
+      for (int l = 0; l < Lg; ++l) {
+        double r = 0.0;
+        for (int i = 0; i < nx; ++i) r = fma(mixW[i * Lg + l], gx[i], r);
+        gg[l] = r;
+      }
+      const T* J = jacs + ((size_t)h * S + sr) * (size_t)Lg * nd;
+      for (int k = 0; k < nd; ++k) {
+        double r = 0.0;
+        for (int l = 0; l < Lg; ++l) r = fma((double)J[l * nd + k], gg[l], r);
+        gd[k] = dt * r;
+      }
+    } else {
+      const T* J = jacs + ((size_t)h * S + sr) * (size_t)nx * nd;
+      for (int k = 0; k < nd; ++k) {
+        double r = 0.0;
+        for (int i = 0; i < nx; ++i) r = fma((double)J[i * nd + k], gx[i], r);
+        gd[k] = dt * r;
+      }
     }
     const T* dn = dins + ((size_t)h * S + sr) * nd;
     for (int i = 0; i < ne; ++i) e[i] = (double)dn[i];
-    // policy head: u = scale (Phi(fp) + shift);  g fp = g u scale phi(fp)
-    const double fp = mmp_policy_mean(ne, P, e);
-    const double gfp = gd[ne] * scale * 0.3989422804014327 * exp(-0.5 * fp * fp);
-    // policy mean fp = sum_m beta_m var exp(-sum_k (e_k - z_mk)^2 / (2 ls2_k)) + c: parameters (wave sums) and input
-    double gvar = 0.0, gls2[MMP_NE];
-    for (int k = 0; k < ne; ++k) { ge[k] = gd[k]; gls2[k] = 0.0; }
-    for (int m = 0; m < pM; ++m) {
-      double r2 = 0.0, df[MMP_NE];
-      for (int k = 0; k < ne; ++k) { df[k] = e[k] - P.Z[m * ne + k]; r2 = fma(df[k] * df[k], P.ils2[k], r2); }
-      const double km = exp(-0.5 * r2);                    // k_m / var
-      const double t = gfp * P.beta[m] * P.var * km;       // g fp * beta_m k_m
-      gvar = fma(gfp * P.beta[m], km, gvar);
-      const double sb = mmp_wave_sum(gfp * P.var * km);    // d / d beta_m
-      if (lane == 0) wacc[pM * ne + m] += sb;
-      for (int k = 0; k < ne; ++k) {
-        const double tz = t * df[k] * P.ils2[k];           // d k_m / d z_mk = k_m (e_k - z_mk) / ls2_k = - d k_m / d e_k
-        ge[k] -= tz;
-        gls2[k] = fma(0.5 * tz * df[k], P.ils2[k], gls2[k]);   // d k_m / d ls2_k = k_m (e_k - z_mk)^2 / (2 ls2_k^2)
-        const double sz = mmp_wave_sum(tz);
-        if (lane == 0) wacc[m * ne + k] += sz;
+    for (int k = 0; k < ne; ++k) ge[k] = gd[k];
+#pragma unroll
+    for (int a = 0; a < NU; ++a) {
+      const double* pa = pol + a * blk;
+      const MMPwPolicy P{pa, pa + pM * ne, pa + pM * ne + pM, var[a], mean[a], pM};
+      double* wacc = acc + (wv * NU + a) * npar1;
+      // policy head: u_a = scale_a (Phi(fp) + shift_a);  g fp = g u_a scale_a phi(fp)
+      const double fp = mmp_policy_mean(ne, P, e);
+      const double gfp = gd[ne + a] * hd.scale[a] * 0.3989422804014327 * exp(-0.5 * fp * fp);
+      // policy mean fp = sum_m beta_m var exp(-sum_k (e_k - z_mk)^2 / (2 ls2_k)) + c: parameters (wave sums) and input
+      double gvar = 0.0, gls2[MMP_NE];
+      for (int k = 0; k < ne; ++k) gls2[k] = 0.0;
+      for (int m = 0; m < pM; ++m) {
+        double r2 = 0.0, df[MMP_NE];
+        for (int k = 0; k < ne; ++k) { df[k] = e[k] - P.Z[m * ne + k]; r2 = fma(df[k] * df[k], P.ils2[k], r2); }
+        const double km = exp(-0.5 * r2);                    // k_m / var
+        const double t = gfp * P.beta[m] * P.var * km;       // g fp * beta_m k_m
+        gvar = fma(gfp * P.beta[m], km, gvar);
+        const double sb = mmp_wave_sum(gfp * P.var * km);    // d / d beta_m
+        if (lane == 0) wacc[pM * ne + m] += sb;
+        for (int k = 0; k < ne; ++k) {
+          const double tz = t * df[k] * P.ils2[k];           // d k_m / d z_mk = k_m (e_k - z_mk) / ls2_k = - d k_m / d e_k
+          ge[k] -= tz;
+          gls2[k] = fma(0.5 * tz * df[k], P.ils2[k], gls2[k]);   // d k_m / d ls2_k = k_m (e_k - z_mk)^2 / (2 ls2_k^2)
+          const double sz = mmp_wave_sum(tz);
+          if (lane == 0) wacc[m * ne + k] += sz;
+        }
       }
-    }
-    for (int k = 0; k < ne; ++k) {
-      const double sl = mmp_wave_sum(gls2[k]);
-      if (lane == 0) wacc[pM * ne + pM + k] += sl;
-    }
-    {
-      const double sv = mmp_wave_sum(gvar), sc = mmp_wave_sum(gfp);
-      if (lane == 0) { wacc[pM * ne + pM + ne] += sv; wacc[pM * ne + pM + ne + 1] += sc; }
+      for (int k = 0; k < ne; ++k) {
+        const double sl = mmp_wave_sum(gls2[k]);
+        if (lane == 0) wacc[pM * ne + pM + k] += sl;
+      }
+      {
+        const double sv = mmp_wave_sum(gvar), sc = mmp_wave_sum(gfp);
+        if (lane == 0) { wacc[pM * ne + pM + ne] += sv; wacc[pM * ne + pM + ne + 1] += sc; }
+      }
     }
     // d_h = (enc(x_h), u): adjoint of x_h = that of x_{h+1} (identity part of the Euler step) + the encoder's
     double x0[MMC_NX];
@@ -159,7 +233,8 @@ __global__ __launch_bounds__(256) void k_pw_policy_bwd(MMComposeDims D, int S, i
 }
 
 // fixed-order sum of the per-wave slabs -> g_policy [npar]
-__global__ __launch_bounds__(256) void k_pw_grad_sum(const double* __restrict__ gpart, int nslab, int npar, double* __restrict__ g_policy) {
+static __global__ __launch_bounds__(256) void k_pw_grad_sum(const double* __restrict__ gpart, int nslab, int npar,
+                                                            double* __restrict__ g_policy) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= npar) return;
   double sacc = 0.0;
@@ -167,55 +242,154 @@ __global__ __launch_bounds__(256) void k_pw_grad_sum(const double* __restrict__ 
   g_policy[p] = sacc;
 }
 
-int mm_pw_grad_sum_launch(const double* gpart, int nslab, int npar, double* g_policy, hipStream_t s) {
-  hipLaunchKernelGGL(k_pw_grad_sum, dim3((npar + 255) / 256), dim3(256), 0, s, gpart, nslab, npar, g_policy);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+// ---- host ----------------------------------------------------------------------------------------------------------------
+static inline size_t mmp_nd_head_lds(int pM, int ne, int nu) {
+  return ((size_t)nu * (pM * ne + pM + ne) + ne + ne * ne + 8) * sizeof(double);
+}
+static inline size_t mmp_nd_bwd_lds(int pM, int ne, int nu) {
+  return mmp_nd_head_lds(pM, ne, nu) + (size_t)4 * nu * (pM * ne + pM + ne + 2) * sizeof(double);
 }
 
-static int mmp_check(int S, int M, int K, int dtype, int H, int nx, int na, const int32_t* active_dims, int policy_M, MMComposeDims& D) {
-  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0) return MM_E_ARG;
+// everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions.  one_action: the one-action
+// entries, whose contract differs in one answer -- na > 0 without active_dims is MM_E_DIM from mm_compose_dims (after sizes and
+// dtype), where every other entry says MM_E_ARG first
+static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, int nu, const int32_t* active_dims, int policy_M,
+                        int nd_max, bool one_action, MMComposeDims& D) {
+  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || (!one_action && na > 0 && !active_dims)) return MM_E_ARG;
   if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
-  const int rc = mm_compose_dims(nx, na, active_dims, D);
+  const int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
   if (rc) return rc;
-  if (D.nd > 8 || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;   // the Jacobian pass of the weight stream: nd <= 8
+  // nd_max: 8 for the _nd entries (the Jacobian pass over whole sample groups), 16 for the _wide ones (+ its half-group form)
+  if (D.nd > nd_max || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;
   return 0;
 }
-static inline size_t mmp_head_lds(int pM, int ne) { return (size_t)(pM * ne + pM + ne + ne + ne * ne + 8) * sizeof(double); }
 
+// the shapes the tape queries answer for (0 otherwise)
+static bool mmp_tape_shape_ok(int S, int H, int nx, int na, int nu) {
+  return S > 0 && H > 0 && nx > 0 && nx <= MMC_NX && na >= 0 && na <= MMC_NA && na <= nx && nu >= 1 && nu <= MMC_NU;
+}
+extern "C" size_t mm_pathwise_tape_bytes_nd(int S, int H, int nx, int na, int nu, int dtype, int with_jacobians) {
+  if (!mmp_tape_shape_ok(S, H, nx, na, nu)) return 0;
+  return mm_pw_tape_layout(S, H, nx, na, nu, dtype, with_jacobians).total;
+}
 extern "C" size_t mm_pathwise_tape_bytes(int S, int H, int nx, int na, int dtype, int with_jacobians) {
-  if (S <= 0 || H <= 0 || nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx) return 0;
-  return mm_pw_tape_layout(S, H, nx, na, 1, dtype, with_jacobians).total;
+  return mm_pathwise_tape_bytes_nd(S, H, nx, na, 1, dtype, with_jacobians);
+}
+// the _mixed tape: the f slot [S][Lg] and the Jacobian block [H][S][Lg][nd] hold the LATENT sample and its Jacobian
+extern "C" size_t mm_pathwise_tape_bytes_mixed(int S, int H, int nx, int na, int nu, int Lg, int dtype, int with_jacobians) {
+  if (!mmp_tape_shape_ok(S, H, nx, na, nu) || Lg < 1 || Lg > nx) return 0;
+  return mm_pw_tape_layout_latent(S, H, nx, na, nu, Lg, dtype, with_jacobians).total;
 }
 
+#define MMP_ND_DISPATCH(nu_, M_)                                                       \
+  switch (nu_) {                                                                       \
+    case 1: M_(1); break;                                                              \
+    case 2: M_(2); break;                                                              \
+    case 3: M_(3); break;                                                              \
+    default: M_(4); break;                                                             \
+  }
+
 template <typename T>
-static int mmp_rollout_t(const MMComposeDims& D, int S, int M, int K, int dtype, int H, double dt, const void* omega_t,
-                         const void* phase, const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
-                         const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
-                         int policy_M, double scale, double shift, const T* target, const T* precis, const T* x0, T* cost,
-                         char* tape, const MMPwTapeLayout& tl, hipStream_t s) {
-  const int nx = D.nx, ne = D.ne, nd = D.nd;
+static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K, int dtype, int H, double dt, const void* omega_t,
+                            const void* phase, const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                            const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
+                            int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
+                            char* tape, const MMPwTapeLayout& tl, int Lg, const double* mix_W, const double* mix_c,
+                            hipStream_t s, int kernel) {
+  // Lg > 0: the _mixed entries -- the stream pass runs with Lg latents and no latent mean straight into the tape's (latent-sized)
+  // f and Jacobian slots, the head kernel mixes
+  const int nx = D.nx, ne = D.ne, nd = D.nd, Lf = Lg > 0 ? Lg : nx;
   T* xs = (T*)(tape + tl.x); T* dins = (T*)(tape + tl.din); T* f = (T*)(tape + tl.f);
   T* jac = tl.jac != tl.total ? (T*)(tape + tl.jac) : nullptr;
   hipError_t e = hipMemcpyAsync(xs, x0, (size_t)S * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return (int)e;
-  const size_t lds = mmp_head_lds(policy_M, ne);
+  const size_t lds = mmp_nd_head_lds(policy_M, ne, nu);
   const dim3 grid((S + 255) / 256);
   for (int h = 0; h <= H; ++h) {
-    hipLaunchKernelGGL((k_pw_head<T>), grid, dim3(256), lds, s, D, S, h, H, dt, h > 0 ? xs + (size_t)(h - 1) * S * nx : (const T*)nullptr,
-                       (const T*)f, xs + (size_t)h * S * nx, h < H ? dins + (size_t)h * S * nd : (T*)nullptr, cost, target, precis,
-                       (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2),
-                       (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M, scale, shift);
+#define MMP_HEAD_(NU_, MIXED_)                                                                                                   \
+    if (h == 0 && lds > 64 * 1024) {   /* nu >= 3 policies on wide encodings: up to 108 KB at M = 256 */                          \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_head_nd<T, NU_, MIXED_>,                                             \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
+      if (ea != hipSuccess) return (int)ea;                                                                                      \
+    }                                                                                                                            \
+    hipLaunchKernelGGL((k_pw_head_nd<T, NU_, MIXED_>), grid, dim3(256), lds, s, D, S, h, H, dt,                                  \
+                       h > 0 ? xs + (size_t)(h - 1) * S * nx : (const T*)nullptr, (const T*)f, xs + (size_t)h * S * nx,          \
+                       h < H ? dins + (size_t)h * S * nd : (T*)nullptr, cost, target, precis, (const double*)(pp + pl.Z64),      \
+                       (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),              \
+                       (const double*)(pp + pl.meanc), policy_M, hd, Lg, mix_W, mix_c)
+#define MMP_HEAD(NU_) if (Lg > 0) { MMP_HEAD_(NU_, true); } else { MMP_HEAD_(NU_, false); }
+    MMP_ND_DISPATCH(nu, MMP_HEAD)
+#undef MMP_HEAD
+#undef MMP_HEAD_
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (h == H) break;
-    const int rc = mm_pathwise_launch(S, nx, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
-                                      prior_scale, variance, mean_c, wb, f, jac ? jac + (size_t)h * S * nx * nd : nullptr, s);
+    const int rc = mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
+                                      prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f,
+                                      jac ? jac + (size_t)h * S * Lf * nd : nullptr, s, kernel);
     if (rc) return rc;
   }
   return 0;
 }
 
+// the head's per-action constants as the kernels take them (by value; zero beyond nu)
+static MMHeadND mmp_head_constants(int nu, const double* head_scale, const double* head_shift) {
+  MMHeadND hd;
+  for (int a = 0; a < MMC_NU; ++a) { hd.scale[a] = a < nu ? head_scale[a] : 0.0; hd.shift[a] = a < nu ? head_shift[a] : 0.0; }
+  return hd;
+}
+
+// the forward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8), _wide (nd_max = 16), _mixed (nd_max = 16,
+// mixed: Lg, mix_W, mix_c) and _kern (kernel: the drift's family) are this function
+static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, const double* mix_c, int S, int M, int K,
+                          int dtype, int H, double dt, int nx, int na,
+                          const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                          const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                          const double* variance, const double* mean_c, const void* wb,
+                          const void* policy_packed, size_t policy_bytes, int policy_M,
+                          const double* head_scale, const double* head_shift, const void* target,
+                          const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                          int with_jacobians, void* stream, int kernel = 0, bool one_action = false) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;             // the drift's kernel family (mm_pathwise_eval_kern)
+  MMComposeDims D;
+  int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, one_action, D);
+  if (rc) return rc;
+  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
+  if (!mixed) Lg = 0;                                        // (what the launches below take for "no mixing")
+  if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !head_scale ||
+      !head_shift || !target || !precis || !x0 || !cost || !tape || (mixed && !mix_W)) return MM_E_ARG;
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, with_jacobians);
+  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  const MMModelLayout pl = mm_model_layout(nu, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
+  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  const MMHeadND hd = mmp_head_constants(nu, head_scale, head_shift);
+  const char* pp = (const char*)policy_packed;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MM_F64)
+    return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
+                                    wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
+                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
+  return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
+                                 pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
+                                 (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
+}
+
+#define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
+  extern "C" int name_(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,      \
+                       const void* omega_t, const void* phase, const void* zs_t, const void* hz, const double* x_scale,          \
+                       const double* prior_scale, const double* variance, const double* mean_c, const void* wb,                  \
+                       const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
+                       const double* head_shift, const void* target, const void* precis, const void* x0, void* cost, void* tape, \
+                       size_t tape_bytes, int with_jacobians, void* stream) {                                                    \
+    return mmp_nd_rollout(nd_max_, false, 0, nullptr, nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase,   \
+                          zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,           \
+                          head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);           \
+  }
+MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_nd, 8)
+MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_wide, 16)
+#undef MMP_ROLLOUT_ENTRY
+
+// one action: the _nd entry with nu = 1 and the head constants by value (g_policy [npar] is the _nd one's [1][npar])
 extern "C" int mm_pathwise_policy_rollout(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
                                           const int32_t* active_dims, const void* omega_t, const void* phase, const void* zs_t,
                                           const void* hz, const double* x_scale, const double* prior_scale,
@@ -223,69 +397,115 @@ extern "C" int mm_pathwise_policy_rollout(int S, int M, int K, int dtype, int H,
                                           const void* policy_packed, size_t policy_bytes, int policy_M, double head_scale,
                                           double head_shift, const void* target, const void* precis, const void* x0, void* cost,
                                           void* tape, size_t tape_bytes, int with_jacobians, void* stream) {
-  MMComposeDims D;
-  int rc = mmp_check(S, M, K, dtype, H, nx, na, active_dims, policy_M, D);
-  if (rc) return rc;
-  if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !target || !precis ||
-      !x0 || !cost || !tape) return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, 1, dtype, with_jacobians);
-  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
-  const MMModelLayout pl = mm_model_layout(1, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
-  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
-  const char* pp = (const char*)policy_packed;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MM_F64)
-    return mmp_rollout_t<double>(D, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, pp,
-                                 pl, policy_M, head_scale, head_shift, (const double*)target, (const double*)precis,
-                                 (const double*)x0, (double*)cost, (char*)tape, tl, s);
-  return mmp_rollout_t<float>(D, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, pp, pl,
-                              policy_M, head_scale, head_shift, (const float*)target, (const float*)precis, (const float*)x0,
-                              (float*)cost, (char*)tape, tl, s);
+  return mmp_nd_rollout(8, false, 0, nullptr, nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, 1, omega_t, phase, zs_t, hz,
+                        x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, &head_scale, &head_shift,
+                        target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, 0, true);
 }
 
+// a coregionalised drift: the paths' operands are those of Lg latents, mean_c is not read (the constant is mix_c)
+extern "C" int mm_pathwise_policy_rollout_mixed(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                                                const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                                                const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                                                const double* variance, const double* mean_c, const void* wb,
+                                                const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                const double* head_scale, const double* head_shift, const void* target,
+                                                const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                                int with_jacobians, void* stream, int Lg, const double* mix_W,
+                                                const double* mix_c) {
+  return mmp_nd_rollout(16, true, Lg, mix_W, mix_c, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz,
+                        x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
+                        target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);
+}
+
+// the one forward entry for a drift of any kernel family (kernel: 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2): the argument
+// list of the _mixed entry plus kernel; Lg = 0 / mix_W = NULL: no mixing (then the _wide entry: nd <= 16, 1 .. 4 actions).  The
+// tape layout does not depend on the family, so the reverse sweeps above are used as they are.
+extern "C" int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
+                                               const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
+                                               const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
+                                               const double* variance, const double* mean_c, const void* wb,
+                                               const void* policy_packed, size_t policy_bytes, int policy_M,
+                                               const double* head_scale, const double* head_shift, const void* target,
+                                               const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                               int with_jacobians, void* stream, int Lg, const double* mix_W,
+                                               const double* mix_c, int kernel) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;
+  const bool mixed = Lg != 0 || mix_W != nullptr;
+  return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t,
+                        phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,
+                        head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel);
+}
+
+// 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)
+static size_t mmp_nd_scratch_bytes(int nd_max, int S, int policy_M, int ne, int nu) {
+  if (S <= 0 || policy_M <= 0 || policy_M > MMP_POLICY_MMAX || ne <= 0 || nu < 1 || nu > MMC_NU || ne + nu > nd_max) return 0;
+  if (mmp_nd_bwd_lds(policy_M, ne, nu) > MMP_ND_LDS_MAX) return 0;
+  return (size_t)((S + 255) / 256) * 4 * (size_t)nu * (size_t)(policy_M * ne + policy_M + ne + 2) * sizeof(double);
+}
+// (the one-action query has no upper bounds: it answers for shapes the entries refuse)
 extern "C" size_t mm_pathwise_backward_scratch_bytes(int S, int policy_M, int ne) {
   if (S <= 0 || policy_M <= 0 || ne <= 0) return 0;
   return (size_t)((S + 255) / 256) * 4 * (size_t)(policy_M * ne + policy_M + ne + 2) * sizeof(double);
 }
+extern "C" size_t mm_pathwise_backward_scratch_bytes_nd(int S, int policy_M, int ne, int nu) {
+  return mmp_nd_scratch_bytes(8, S, policy_M, ne, nu);
+}
+extern "C" size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, int ne, int nu) {
+  return mmp_nd_scratch_bytes(16, S, policy_M, ne, nu);
+}
 
-// the backward entries: the unseeded one (g_cost required, g_x = nullptr) and the _seeded one (either seed may be NULL, not both)
-static int mmp_backward(bool seeded_entry, int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
-                        const void* policy_packed, size_t policy_bytes, int policy_M, double head_scale, double head_shift,
-                        const void* target, const void* precis, const void* tape, size_t tape_bytes, const void* g_cost,
-                        const void* g_x, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
+// the backward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8) and _wide (nd_max = 16), unseeded (g_cost required, g_x = nullptr) and _seeded (either
+// seed may be NULL, not both), are this function; so is _mixed (nd_max = 16, seeded, mixed: Lg and mix_W)
+static int mmp_nd_backward(int nd_max, bool seeded_entry, bool mixed, int Lg, const double* mix_W, int S, int dtype, int H,
+                           double dt, int nx, int na,
+                           const int32_t* active_dims, int nu, const void* policy_packed,
+                           size_t policy_bytes, int policy_M, const double* head_scale,
+                           const double* head_shift, const void* target, const void* precis,
+                           const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
+                           void* g_x0, void* scratch, size_t scratch_bytes, void* stream, bool one_action = false) {
   MMComposeDims D;
-  int rc = mmp_check(S, 1, 1, dtype, H, nx, na, active_dims, policy_M, D);
+  int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, one_action, D);
   if (rc) return rc;
-  if (!policy_packed || !target || !precis || !tape || (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch)
+  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
+  if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape ||
+      (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch || (mixed && !mix_W))
     return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout(S, H, nx, na, 1, dtype, 1);
+  const int ne = D.ne, npar = nu * (policy_M * ne + policy_M + ne + 2);
+  const size_t lds = mmp_nd_bwd_lds(policy_M, ne, nu);
+  if (lds > MMP_ND_LDS_MAX) return MM_E_DIM;
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
-  const int ne = D.ne, npar = policy_M * ne + policy_M + ne + 2;
-  if (scratch_bytes < mm_pathwise_backward_scratch_bytes(S, policy_M, ne)) return MM_E_WORKSPACE;
-  const MMModelLayout pl = mm_model_layout(1, policy_M, ne, MM_F64, 1);
+  if (scratch_bytes < mmp_nd_scratch_bytes(nd_max, S, policy_M, ne, nu)) return MM_E_WORKSPACE;
+  const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, MM_F64, 1);
   if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  const MMHeadND hd = mmp_head_constants(nu, head_scale, head_shift);
   const char* pp = (const char*)policy_packed; const char* tp = (const char*)tape;
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = mmp_head_lds(policy_M, ne) + (size_t)4 * npar * sizeof(double);
-  if (lds > 160 * 1024) return MM_E_DIM;
   const dim3 grid((S + 255) / 256);
   // (the built-in cost alone: the unseeded instantiation, whichever entry was called -- same arithmetic, bit-equal outputs)
   const bool seeded = g_x != nullptr || g_cost == nullptr;
-#define MMP_BWD(T_, SEEDED_)                                                                                                     \
+#define MMP_BWD(T_, NU_, SEEDED_, MIXED_)                                                                                         \
   do {                                                                                                                          \
     if (lds > 64 * 1024) {                                                                                                      \
-      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd<T_, SEEDED_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                          (int)lds);                                                                            \
+      hipError_t ea = hipFuncSetAttribute((const void*)k_pw_policy_bwd_nd<T_, NU_, SEEDED_, MIXED_>,                             \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
       if (ea != hipSuccess) return (int)ea;                                                                                     \
     }                                                                                                                           \
-    hipLaunchKernelGGL((k_pw_policy_bwd<T_, SEEDED_>), grid, dim3(256), lds, s, D, S, H, dt, (const T_*)(tp + tl.x),             \
-                       (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost, (const double*)g_x,            \
-                       (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64), (const double*)(pp + pl.beta64),      \
-                       (const double*)(pp + pl.ls2), (const double*)(pp + pl.var), (const double*)(pp + pl.meanc), policy_M,     \
-                       head_scale, head_shift, (double*)scratch, (double*)g_x0);                                                \
+    hipLaunchKernelGGL((k_pw_policy_bwd_nd<T_, NU_, SEEDED_, MIXED_>), grid, dim3(256), lds, s, D, S, H, dt,                     \
+                       (const T_*)(tp + tl.x), (const T_*)(tp + tl.din), (const T_*)(tp + tl.jac), (const double*)g_cost,       \
+                       (const double*)g_x, (const T_*)target, (const T_*)precis, (const double*)(pp + pl.Z64),                  \
+                       (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),             \
+                       (const double*)(pp + pl.meanc), policy_M, hd, (double*)scratch, (double*)g_x0, Lg, mix_W);               \
   } while (0)
-  if (dtype == MM_F64) { if (seeded) MMP_BWD(double, true); else MMP_BWD(double, false); }
-  else { if (seeded) MMP_BWD(float, true); else MMP_BWD(float, false); }
+#define MMP_BWD_T(T_, NU_)                                                                                                       \
+  if (mixed) { if (seeded) MMP_BWD(T_, NU_, true, true); else MMP_BWD(T_, NU_, false, true); }                                   \
+  else { if (seeded) MMP_BWD(T_, NU_, true, false); else MMP_BWD(T_, NU_, false, false); }
+#define MMP_BWD_F64(NU_) MMP_BWD_T(double, NU_)
+#define MMP_BWD_F32(NU_) MMP_BWD_T(float, NU_)
+  if (dtype == MM_F64) { MMP_ND_DISPATCH(nu, MMP_BWD_F64) } else { MMP_ND_DISPATCH(nu, MMP_BWD_F32) }
+#undef MMP_BWD_F64
+#undef MMP_BWD_F32
+#undef MMP_BWD_T
 #undef MMP_BWD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -295,21 +515,58 @@ static int mmp_backward(bool seeded_entry, int S, int dtype, int H, double dt, i
   return e == hipSuccess ? 0 : (int)e;
 }
 
+#define MMP_BACKWARD_ENTRY(name_, nd_max_)                                                                                         \
+  extern "C" int name_(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,                    \
+                       const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
+                       const double* head_shift, const void* target, const void* precis, const void* tape, size_t tape_bytes,    \
+                       const void* g_cost, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {      \
+    return mmp_nd_backward(nd_max_, false, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,            \
+                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, nullptr,    \
+                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
+  }                                                                                                                             \
+  extern "C" int name_##_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,          \
+                                const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,          \
+                                const double* head_shift, const void* target, const void* precis, const void* tape,              \
+                                size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy, void* g_x0,              \
+                                void* scratch, size_t scratch_bytes, void* stream) {                                            \
+    return mmp_nd_backward(nd_max_, true, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,             \
+                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x,        \
+                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
+  }
+MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_nd, 8)
+MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_wide, 16)
+#undef MMP_BACKWARD_ENTRY
+
+// one action: the _nd entries with nu = 1 and the head constants by value
 extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
                                                    const void* policy_packed, size_t policy_bytes, int policy_M,
                                                    double head_scale, double head_shift, const void* target, const void* precis,
                                                    const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
                                                    void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
-  return mmp_backward(false, S, dtype, H, dt, nx, na, active_dims, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
-                      target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch, scratch_bytes, stream);
+  return mmp_nd_backward(8, false, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, 1, policy_packed, policy_bytes,
+                         policy_M, &head_scale, &head_shift, target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0,
+                         scratch, scratch_bytes, stream, true);
 }
-
 extern "C" int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int H, double dt, int nx, int na,
                                                           const int32_t* active_dims, const void* policy_packed,
                                                           size_t policy_bytes, int policy_M, double head_scale, double head_shift,
                                                           const void* target, const void* precis, const void* tape,
                                                           size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
                                                           void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
-  return mmp_backward(true, S, dtype, H, dt, nx, na, active_dims, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
-                      target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch, scratch_bytes, stream);
+  return mmp_nd_backward(8, true, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, 1, policy_packed, policy_bytes,
+                         policy_M, &head_scale, &head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0,
+                         scratch, scratch_bytes, stream, true);
+}
+
+// the reverse sweep of the _mixed rollout: the _seeded signature (either of g_cost and g_x may be NULL, not both) + the mixing
+extern "C" int mm_pathwise_policy_rollout_backward_mixed(int S, int dtype, int H, double dt, int nx, int na,
+                                                         const int32_t* active_dims, int nu, const void* policy_packed,
+                                                         size_t policy_bytes, int policy_M, const double* head_scale,
+                                                         const double* head_shift, const void* target, const void* precis,
+                                                         const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                                                         void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes,
+                                                         void* stream, int Lg, const double* mix_W) {
+  return mmp_nd_backward(16, true, true, Lg, mix_W, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes,
+                         policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch,
+                         scratch_bytes, stream);
 }

@@ -1,5 +1,5 @@
-// Device helpers and the tape layout shared by the pathwise policy rollouts: one action (mm_pathwise_policy.hip) and
-// 1 .. 4 actions (mm_pathwise_policy_nd.hip).  Encoder, cost, the policy's predictive mean, the fixed-order wave sum.
+// Device helpers and the tape layout of the pathwise policy rollout and its reverse sweep (mm_pathwise_policy.hip, 1 .. 4
+// actions).  Encoder, cost, the policy's predictive mean, the fixed-order wave sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -9,8 +9,6 @@
 int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
                        const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
                        const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel = 0);
-// mm_pathwise_policy.hip: k_pw_grad_sum on stream s -- the fixed-order sum of nslab per-wave slabs [nslab][npar] -> g_policy [npar]
-int mm_pw_grad_sum_launch(const double* gpart, int nslab, int npar, double* g_policy, hipStream_t s);
 
 #define MMP_NE 24            // largest encoded dimension (2 na + nb, na <= 8, nx <= 16)
 #define MMP_POLICY_MMAX 256

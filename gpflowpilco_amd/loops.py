@@ -569,7 +569,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
 
   ``native_actions``: the largest number of actions the closure may run natively.  The default 1 keeps a policy with several
   actions on the torch composition (with the "nu > 1" warning; ``native=True`` raises).  With ``native_actions >= nu`` such a
-  policy runs in the multi-action native rollout (csrc/mm_pathwise_policy_nd.hip), forward and gradient, where
+  policy runs in the same native rollout through its ``_nd`` entries (1 to 4 actions), forward and gradient, where
   nx + na + nu <= 8, the policy has <= 256 centres and -- when a gradient is asked for -- the reverse sweep takes the shape
   (``PolicyRollout.supports_backward``); every other case falls back and names its reason.
 
@@ -607,7 +607,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   composition, saying so once (``native=True`` raises) -- on paths that carry the drift's mixing (``Paths.mix_W`` / ``mix_c``:
   ``generate_paths`` and ``PathSampler`` draw Lg latent paths and ``Paths.__call__`` returns W g + c), so the composition is
   correct for any Lg.  True runs a coregionalised DRIFT with Lg <= nx latents in the ``_mixed`` native entries, forward and
-  gradient (csrc/mm_pathwise_policy_nd.hip: a latent-sized tape, the mixing inside the head kernel and the reverse sweep), for
+  gradient (csrc/mm_pathwise_policy.hip: a latent-sized tape, the mixing inside the head kernel and the reverse sweep), for
   1 to 4 actions and nd <= 16 under the ``native_actions`` / ``native_inputs`` rules; it composes with ``native_no_encoder``,
   ``native_objective``, ``native_sampler`` and ``paths=``.  W and the Constant mean are constants of the frozen drift, taken from
   the paths of the call.  A coregionalised policy, Lg > nx, given ``paths`` that carry no mixing or one of another shape than the

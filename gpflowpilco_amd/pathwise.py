@@ -489,15 +489,16 @@ class PathwiseSVGP(SVGP):
 
 
 class PolicyRollout:
-  """The pathwise policy rollout on the device (``mm_pathwise_policy_rollout``, csrc/mm_pathwise_policy.hip; several actions:
-  ``mm_pathwise_policy_rollout_nd``, csrc/mm_pathwise_policy_nd.hip): per sample path encoder -> policy mean through
+  """The pathwise policy rollout on the device (csrc/mm_pathwise_policy.hip: ``mm_pathwise_policy_rollout``; several actions:
+  ``mm_pathwise_policy_rollout_nd``, the same kernels): per sample path encoder -> policy mean through
   Chain[Scale, Shift, NormalCDF] -> drift sample -> Euler -> cost -- the body of ``PathwisePILCO._policy_loss_closure``
   (gpflow_pilco/loops/pilco.py:263-298).
 
   ``paths``: the drift's sample paths (nx latents on nd = nx + na + nu inputs, nd <= 8; ``wide=True``: nd <= 16); ``policy``: an ``ops.PackedModel`` with
   one latent per action (nu = 1 .. 4) on ne = nx + na inputs (any dtype: only its float64 blocks are read); ``head_scale`` /
   ``head_shift``: a float, or one value per action.  The actions follow the encoding in latent order.  A one-latent pack with
-  float head constants runs the one-action entries; nu > 1 (or ``nd_entries=True``) the ``_nd`` entries.  ``wide=True``: the
+  float head constants runs the one-action entries (wrappers of the ``_nd`` ones: nu = 1, head constants by value, ``g_policy``
+  without the latent axis); nu > 1 (or ``nd_entries=True``) the ``_nd`` entries.  ``wide=True``: the
   ``_wide`` entries (same signatures and results, any nu), which take nd <= 16.
   ``__call__(x0, H)`` -> ``(cost [H, S], tape)``; ``backward(tape, g_cost)`` -> ``(g_policy, g_x0 [S, nx] | None)`` with
   g_policy [M ne + M + ne + 2] from the one-action entries and [nu, M ne + M + ne + 2] from the ``_nd`` ones (per latent dZ,
@@ -614,28 +615,23 @@ class PolicyRollout:
     tape = torch.empty(n, dtype=torch.uint8, device=x0.device)
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
+    # the one-action entry takes no action count and its head constants by value; the others the count and one array each
+    mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
     if self.nd_entries:
       entry = "mm_pathwise_policy_rollout_" + ("kern" if self.kernel else "mixed" if self.mixed else self._sfx)
-      mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
       if self.kernel:
         mixing = (mixing or (0, None, None)) + (self.kernel,)
-      rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, self.nu,
-                               P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
-                               P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
-                               _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
-                               self._scale_c, self._shift_c, self.target.data_ptr(), self.precis.data_ptr(),
-                               x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                               int(with_jacobians), _stream(x0.device), *mixing)
-      check(rc, entry)
-      return cost, tape
-    rc = lib.mm_pathwise_policy_rollout(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act,
-                                        P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
-                                        P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
-                                        _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
-                                        self.scale, self.shift, self.target.data_ptr(), self.precis.data_ptr(),
-                                        x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                                        int(with_jacobians), _stream(x0.device))
-    check(rc, "mm_pathwise_policy_rollout")
+      nu, head = (self.nu,), (self._scale_c, self._shift_c)
+    else:
+      entry, nu, head = "mm_pathwise_policy_rollout", (), (self.scale, self.shift)
+    rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, *nu,
+                             P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
+                             P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
+                             _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
+                             *head, self.target.data_ptr(), self.precis.data_ptr(),
+                             x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
+                             int(with_jacobians), _stream(x0.device), *mixing)
+    check(rc, entry)
     return cost, tape
 
   def states(self, tape: torch.Tensor, num_steps: int) -> torch.Tensor:

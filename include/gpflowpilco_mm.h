@@ -517,14 +517,16 @@ int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int H, double d
                                                const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
                                                void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream);
 
-/* ---- the same for policies with SEVERAL actions (csrc/mm_pathwise_policy_nd.hip): 1 <= nu <= 4 ------------------------------
+/* ---- the same for policies with SEVERAL actions (csrc/mm_pathwise_policy.hip): 1 <= nu <= 4 ---------------------------------
  * On sample paths the policy is evaluated pointwise, so its nu actions are nu independent heads appended to the encoding in
  * latent order: u_a = head_scale[a] (Phi(f_a(e)) + head_shift[a]), drift input d = (e, u_0 .. u_{nu-1}), nd = nx + na + nu <= 8
  * (the double pendulum: nx 4, two angles, two torques -> nd = 8).  The policy is an mm_pack_model pack with L = nu latents
  * (M <= 256 centres each on ne = nx + na inputs; only its f64 blocks are read); head_scale, head_shift: HOST arrays [nu].
  * Everything else -- operands, tape (with nd = nx + na + nu), g_cost, g_x0 -- as in the one-action entries above;
  * g_policy [nu][M ne + M + ne + 2] f64: per latent dZ, dbeta, d ls^2, dvar, dmean.  With nu = 1 the size queries return the
- * one-action sizes and the rollout, the tape and the gradients equal the one-action entries' bit for bit.
+ * one-action sizes, and the rollout, the tape and the gradients are the one-action entries': those are these entries called
+ * with nu = 1 and their by-value head constants (the same code; they differ only in answering MM_E_DIM, after the size and dtype
+ * checks, where these answer MM_E_ARG for na > 0 without active_dims, and in a scratch query without upper bounds).
  * Refused before any HIP call: nu outside 1..4, nx + na + nu > 8 or policy_M > 256 (MM_E_DIM); a null pointer (MM_E_ARG); a dtype
  * other than MM_F32 / MM_F64 (MM_E_DTYPE); a short tape, policy buffer or scratch (MM_E_WORKSPACE).
  * The reverse sweep keeps the nu policy blocks and one gradient slab per wave in LDS and takes a shape when

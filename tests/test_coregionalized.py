@@ -14,6 +14,7 @@ import copy
 import ctypes
 import functools
 import os
+import subprocess
 import warnings
 
 import numpy as np
@@ -146,12 +147,23 @@ def _dp(a):
   return a.ctypes.data_as(ctypes.c_void_p)
 
 
+@functools.lru_cache(maxsize=None)
+def _host_mix_lib():
+  """tests/hostcheck/libmm_mix_host.so, built by ``__graft_entry__.build()``; rebuilt here when it is missing or older than its
+  sources, as tests/test_adjoint_host.py does for its library."""
+  hostcheck = os.path.dirname(HOSTLIB)
+  deps = [os.path.join(hostcheck, "mm_mix_host.hip"), os.path.join(os.path.dirname(hostcheck), os.pardir, "gpflowpilco_amd", "csrc", "mm_mix.h")]
+  if not os.path.exists(HOSTLIB) or os.path.getmtime(HOSTLIB) < max(os.path.getmtime(p) for p in deps):
+    subprocess.run(["bash", os.path.join(hostcheck, "build_mix.sh")], check=True)
+  return ctypes.CDLL(HOSTLIB)
+
+
 @pytest.mark.parametrize("nx,Lg,nd", [(4, 2, 6), (3, 3, 7), (2, 1, 3)])
 def test_host_mixing_and_adjoint_match_torch(nx, Lg, nd):
   """mma_mix_fwd / mma_mix_bwd (csrc/mm_mix.h, built for the host) against torch f64 and its autograd, 1e-13 relative (the
   step-adjoint bar of tests/test_adjoint_nd_host.py); Sff comes out exactly symmetric; the adjoint is seeded with an unsymmetric
   g Sff."""
-  hc = ctypes.CDLL(HOSTLIB)
+  hc = _host_mix_lib()
   rng = np.random.default_rng(100 * nx + 10 * Lg + nd)
   W, c = rng.standard_normal((nx, Lg)), rng.standard_normal(nx)
   g1 = rng.standard_normal(Lg); Sgg = generate_covariance(rng, Lg, (), 0.7); cg = rng.standard_normal((nd, Lg))

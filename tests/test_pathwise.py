@@ -345,3 +345,129 @@ def test_pathwise_policy_loss_closure_native_equals_the_torch_composition(device
     loss = pathwise_policy_loss_closure(system, objective, lambda: x0, H, dt=0.5, paths=paths)()
   loss.mean().backward()
   assert target.grad is not None and float(target.grad.abs().max()) > 0.0
+
+
+# ---- the one-action C entries refuse exactly as they did when they had kernels of their own ---------------------------------
+_RO_ARGS = ("S M K dtype H dt nx na active_dims omega_t phase zs_t hz x_scale prior_scale variance mean_c wb policy policy_bytes "
+            "policy_M head_scale head_shift target precis x0 cost tape tape_bytes with_jacobians stream").split()
+_BW_ARGS = ("S dtype H dt nx na active_dims policy policy_bytes policy_M head_scale head_shift target precis tape tape_bytes g_cost "
+            "g_policy g_x0 scratch scratch_bytes stream").split()
+_BS_ARGS = _BW_ARGS[:17] + ["g_x"] + _BW_ARGS[17:]
+
+
+def _up256(n):
+  return (n + 255) // 256 * 256
+
+
+def _one_action_tape_bytes(S, H, nx, na, es, jac):
+  nd = nx + na + 1
+  return (_up256((H + 1) * S * nx * es) + _up256(H * S * nd * es) + _up256(S * nx * es)
+          + _up256(H * S * nx * nd * es if jac else 0))
+
+
+def _one_action_refusal_table():
+  """[(entry, [argument, ...])]: the calls of tests/golden/pathwise_one_action_refusals.json.  An argument is a number, None
+  (NULL), "buf" (a 64-byte dummy buffer) or a list of ints (an int32 array).  No call gets past the checks to a launch: every
+  row of the three entries carries at least one refusal."""
+  F32, F64 = 0, 1
+  ne, pM = 5, 12
+  need = {(dt_, j): _one_action_tape_bytes(37, 6, 4, 1, 4 + 4 * dt_, j) for dt_ in (F32, F64) for j in (0, 1)}
+  sb = 4 * (pM * ne + pM + ne + 2) * 8                                             # one workgroup of four waves
+  pol_need = 4 * 256 + _up256(ne * 128 * 8) + _up256(pM * ne * 8) + _up256(pM * 8)   # the pack's f64 blocks: up to Zc64
+  rows = []
+
+  def add(entry, names, base, **kw):
+    assert set(kw) <= set(names), kw
+    rows.append((entry, [kw.get(n, base[n]) for n in names]))
+
+  ro = dict(S=37, M=40, K=64, dtype=F64, H=6, dt=0.5, nx=4, na=1, active_dims=[1], mean_c=None, policy_bytes=1 << 30, policy_M=pM,
+            head_scale=2.0, head_shift=-0.5, tape_bytes=1 << 40, with_jacobians=1, stream=None)
+  ro.update({n: "buf" for n in _RO_ARGS if n not in ro})
+  bw = dict(S=37, dtype=F64, H=6, dt=0.5, nx=4, na=1, active_dims=[1], policy_bytes=1 << 30, policy_M=pM, head_scale=2.0,
+            head_shift=-0.5, tape_bytes=1 << 40, g_x0=None, scratch_bytes=1 << 40, stream=None)
+  bw.update({n: "buf" for n in _BS_ARGS if n not in bw})
+  # what every entry checks, in the combinations that fix the order: sizes -> dtype -> dimensions -> pointers -> buffer sizes
+  common = [dict(S=0), dict(S=-1), dict(H=0), dict(H=-3), dict(policy_M=0), dict(policy_M=-1), dict(dtype=7), dict(dtype=-1),
+            dict(na=-1), dict(na=5), dict(nx=0), dict(nx=17), dict(na=2, active_dims=[1, 1]), dict(active_dims=[4]),
+            dict(active_dims=[-1]), dict(active_dims=None), dict(S=0, active_dims=None), dict(dtype=7, active_dims=None),
+            dict(active_dims=None, policy_M=257), dict(active_dims=None, policy=None), dict(active_dims=None, tape_bytes=0),
+            dict(na=0, active_dims=None, tape_bytes=_one_action_tape_bytes(37, 6, 4, 0, 8, 1) - 1),
+            dict(nx=7), dict(nx=6, tape_bytes=_one_action_tape_bytes(37, 6, 6, 1, 8, 1) - 1),
+            dict(policy_M=257), dict(policy_M=256, tape_bytes=need[F64, 1] - 1),
+            dict(tape_bytes=need[F64, 1] - 1), dict(dtype=F32, tape_bytes=need[F32, 1] - 1), dict(tape_bytes=0),
+            dict(S=0, dtype=7, policy_M=257, policy=None), dict(dtype=7, policy_M=257, policy=None),
+            dict(nx=7, policy=None), dict(policy_M=257, policy=None, tape_bytes=0), dict(policy=None, tape_bytes=0),
+            dict(active_dims=[4], policy=None), dict(active_dims=[4], dtype=7), dict(tape_bytes=0, policy_bytes=0)]
+  for kw in common:
+    add("mm_pathwise_policy_rollout", _RO_ARGS, ro, **kw)
+  for n in (n for n in _RO_ARGS if ro[n] == "buf"):                                # each pointer NULL in turn (mean_c may be)
+    add("mm_pathwise_policy_rollout", _RO_ARGS, ro, tape_bytes=need[F64, 1] - 1, **{n: None})
+  for kw in (dict(M=0), dict(K=0), dict(M=-2, dtype=7), dict(with_jacobians=0, tape_bytes=need[F64, 0] - 1),
+             dict(dtype=F32, with_jacobians=0, tape_bytes=need[F32, 0] - 1),
+             dict(with_jacobians=0, tape_bytes=need[F64, 1] - 1, policy_bytes=pol_need - 1),
+             dict(tape_bytes=need[F64, 1], policy_bytes=pol_need - 1), dict(tape_bytes=need[F64, 1], policy_bytes=64)):
+    add("mm_pathwise_policy_rollout", _RO_ARGS, ro, **kw)
+  sweep = common + [dict(tape_bytes=need[F64, 1], scratch_bytes=sb - 1), dict(tape_bytes=need[F64, 1], scratch_bytes=0, policy_bytes=0),
+                    dict(tape_bytes=need[F64, 1], scratch_bytes=sb, policy_bytes=pol_need - 1),
+                    dict(tape_bytes=need[F64, 1], scratch_bytes=sb, policy_bytes=64),
+                    dict(tape_bytes=need[F64, 0]), dict(S=300, tape_bytes=_one_action_tape_bytes(300, 6, 4, 1, 8, 1), scratch_bytes=2 * sb - 1),
+                    dict(scratch=None, scratch_bytes=0), dict(g_policy=None, tape_bytes=0)]
+  sweep += [dict({n: None}, tape_bytes=need[F64, 1] - 1) for n in ("policy", "target", "precis", "tape", "g_policy", "g_x0", "scratch")]
+  for kw in sweep:
+    add("mm_pathwise_policy_rollout_backward", _BW_ARGS, bw, **kw)
+    for seeds in (dict(), dict(g_cost=None), dict(g_x=None), dict(g_cost=None, g_x=None)):   # neither, either, both seeds NULL
+      add("mm_pathwise_policy_rollout_backward_seeded", _BS_ARGS, bw, **kw, **seeds)
+  for kw in (dict(g_cost=None), dict(g_cost=None, S=0), dict(g_cost=None, dtype=7), dict(g_cost=None, policy_M=257),
+             dict(g_cost=None, tape_bytes=0), dict(g_cost=None, active_dims=None)):
+    add("mm_pathwise_policy_rollout_backward", _BW_ARGS, bw, **kw)
+  # the two size queries (these only compute)
+  for a in [(37, 6, 4, 1, dt_, j) for dt_ in (F32, F64) for j in (0, 1)] + [
+      (300, 6, 4, 1, F64, 1), (37, 6, 4, 0, F64, 1), (37, 6, 6, 1, F64, 1), (37, 6, 7, 1, F64, 1), (37, 6, 16, 8, F64, 1),
+      (0, 6, 4, 1, F64, 1), (-1, 6, 4, 1, F64, 1), (37, 0, 4, 1, F64, 1), (37, 6, 0, 0, F64, 1), (37, 6, 17, 1, F64, 1),
+      (37, 6, 4, -1, F64, 1), (37, 6, 4, 5, F64, 1), (37, 6, 16, 9, F64, 1)]:
+    rows.append(("mm_pathwise_tape_bytes", list(a)))
+  for S in (37, 300):
+    for M in (12, 256, 257, 1000):
+      for e in (1, 5, 7, 8, 23):
+        rows.append(("mm_pathwise_backward_scratch_bytes", [S, M, e]))
+  for a in ((0, 12, 5), (-1, 12, 5), (37, 0, 5), (37, -1, 5), (37, 12, 0), (37, 12, -1)):
+    rows.append(("mm_pathwise_backward_scratch_bytes", list(a)))
+  return rows
+
+
+def _call_refusal_row(lib, entry, args):
+  import ctypes
+  buf = (ctypes.c_char * 64)()
+  keep = [buf]
+
+  def conv(a):
+    if a == "buf":
+      return ctypes.addressof(buf)
+    if isinstance(a, list):
+      keep.append((ctypes.c_int32 * len(a))(*a))
+      return keep[-1]
+    return a
+  return int(getattr(lib, entry)(*[conv(a) for a in args]))
+
+
+def test_one_action_entries_refuse_as_recorded_before_they_became_wrappers():
+  """mm_pathwise_policy_rollout, its two reverse sweeps and the two one-action size queries are wrappers of the code behind the
+  _nd entries.  tests/golden/pathwise_one_action_refusals.json holds what the last commit at which they had kernels and checks of
+  their own (b8a8c9e) returned for the calls of _one_action_refusal_table(): `[{"entry", "args", "ret"}]`, written with
+  _call_refusal_row against that commit's library.  The table and the recording list the same calls, and the library answers each
+  as recorded -- in particular MM_E_DIM (not the _nd entries' MM_E_ARG) for na > 0 without active_dims, after sizes and dtype, and a
+  scratch query without upper bounds.  Refusals precede every HIP call: no GPU is needed."""
+  import json
+  import os
+  from gpflowpilco_amd import _lib
+  with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pathwise_one_action_refusals.json")) as fh:
+    recorded = json.load(fh)
+  table = _one_action_refusal_table()
+  assert [(r["entry"], r["args"]) for r in recorded] == [(e, a) for e, a in table]
+  lib = _lib.lib()
+  entries = ("mm_pathwise_policy_rollout", "mm_pathwise_policy_rollout_backward", "mm_pathwise_policy_rollout_backward_seeded")
+  assert {r["entry"] for r in recorded} == set(entries) | {"mm_pathwise_tape_bytes", "mm_pathwise_backward_scratch_bytes"}
+  for r in recorded:
+    if r["entry"] in entries:
+      assert r["ret"] in (-1, -2, -3, -4), r                                       # (never replay a call that was not refused)
+    assert _call_refusal_row(lib, r["entry"], r["args"]) == r["ret"], r

@@ -1,6 +1,6 @@
 """The pathwise side for a COREGIONALISED drift (a LinearCoregionalization kernel: Lg latent paths mixed to nx outputs,
 f = W g + c): Paths with mix_W / mix_c (the torch composition's route), the _mixed entries of the policy rollout and its reverse
-sweep (csrc/mm_pathwise_policy_nd.hip, pathwise.PolicyRollout on such paths) and
+sweep (csrc/mm_pathwise_policy.hip, pathwise.PolicyRollout on such paths) and
 loops.pathwise_policy_loss_closure(native_coregionalized=True), against tests/pathwise_mixed_oracle.py -- a fold of
 oracle.pathwise_oracle and tests/pathwise_multiaction_oracle.py with f = eval_paths(latent paths) @ W.T + c.
 

@@ -1,4 +1,4 @@
-"""The native pathwise policy rollout and its gradient for policies with several actions (csrc/mm_pathwise_policy_nd.hip,
+"""The native pathwise policy rollout and its gradient for policies with several actions (csrc/mm_pathwise_policy.hip,
 pathwise.PolicyRollout with an L = nu pack, loops.pathwise_policy_loss_closure(native_actions=...)) against the numpy
 restatement tests/pathwise_multiaction_oracle.py (a fold of oracle.pathwise_oracle's own functions).
 
@@ -272,6 +272,10 @@ def _tape_blocks(tape, S, H, nx, nd, es, jac):
 @pytest.mark.parametrize("S", [37, 300])
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
 def test_gpu_one_action_through_the_nd_entries_is_bit_equal(dtype, S, device):
+  """The one-action entries are the ``_nd`` entries called with nu = 1, so both rollouts run the same kernels: what this checks
+  is the wrappers' argument marshalling -- head constants by value against one-element arrays, the tape size of the one-action
+  query, ``g_policy`` [npar] against [1, npar].  (While the one-action entries had kernels of their own, it was the evidence that
+  the two pairs of kernels computed the same bits.)"""
   sy = _system("C", S)
   _, _, roll1 = _device_case(sy, device, dtype)
   _, _, rolln = _device_case(sy, device, dtype, nd_entries=True)

@@ -1,6 +1,5 @@
 """Caller-defined objectives on the native pathwise policy rollouts (``native_objective=True``): the seeded reverse sweeps
-``mm_pathwise_policy_rollout_backward_seeded`` / ``_nd_seeded`` / ``_wide_seeded`` (csrc/mm_pathwise_policy.hip,
-csrc/mm_pathwise_policy_nd.hip), ``pathwise.PolicyRollout.backward(g_states=...)`` / ``.trajectory``,
+``mm_pathwise_policy_rollout_backward_seeded`` / ``_nd_seeded`` / ``_wide_seeded`` (csrc/mm_pathwise_policy.hip), ``pathwise.PolicyRollout.backward(g_states=...)`` / ``.trajectory``,
 ``pathwise.PolicyTrajectoryFunction`` and the routing of ``loops.pathwise_policy_loss_closure``.
 
 Systems (the ones the pathwise tests share; drift M 50 (M0: 40), K 130 (M0: 64), policy M 12; H = 6, dt = 0.5; S = 37: one partial

@@ -1,6 +1,6 @@
 """The pathwise side for 9 to 16 drift inputs: the Jacobian pass of the weight stream over half sample groups
 (csrc/mm_pathwise.hip, Paths.eval_jac / Paths.__call__ under autograd), the _wide entries of the policy rollout and its reverse
-sweep (csrc/mm_pathwise_policy_nd.hip, pathwise.PolicyRollout(wide=True)) and loops.pathwise_policy_loss_closure(native_inputs=16),
+sweep (csrc/mm_pathwise_policy.hip, pathwise.PolicyRollout(wide=True)) and loops.pathwise_policy_loss_closure(native_inputs=16),
 against oracle.pathwise_oracle and its multi-action fold tests/pathwise_multiaction_oracle.py.
 
 Systems (recipe of tests/test_pathwise_multiaction.py::_system: drift M 50, K 130, policy M 12 with its own Z per latent, w and v

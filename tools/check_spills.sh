@@ -5,13 +5,13 @@
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 tmp="$(mktemp -d)"
-for f in mm_kernels mm_mfma mm_f64 mm_moments6 mm_backward mm_pathwise mm_compose_nd mm_pathwise_policy_nd mm_compose_bwd_nd mm_pathwise_sample; do
+for f in mm_kernels mm_mfma mm_f64 mm_moments6 mm_backward mm_pathwise mm_compose_nd mm_pathwise_policy mm_compose_bwd_nd mm_pathwise_sample; do
   extra=()
   [[ $f == mm_mfma ]] && extra=(-fno-honor-nans)
   [[ $f == mm_pathwise ]] && extra=(-fno-slp-vectorize)
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only -w "${extra[@]}" \
     "${here}/gpflowpilco_amd/csrc/${f}.hip" -o "${tmp}/${f}.s"
-  grep -E "^_Z[0-9]+k_[a-z0-9_]+|ScratchSize:|TotalNumVgprs" "${tmp}/${f}.s" | paste - - - \
+  grep -E "^_ZL?[0-9]+k_[a-z0-9_]+|ScratchSize:|TotalNumVgprs" "${tmp}/${f}.s" | paste - - - \
     | awk -v f="$f" '{ if ($NF + 0 > 0 || $(NF-3) + 0 > 256) print f ": " substr($1, 1, 70), "vgprs", $(NF-3), "scratch", $NF }'
 done
 rm -rf "${tmp}"
