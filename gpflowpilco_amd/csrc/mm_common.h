@@ -24,6 +24,11 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // degree-4..6 contraction at d = 8: take the generic steps (mm6_step: every size a run-time value) even where the d = 8
 // specialisation mm6_step8 applies (mm_moments6.hip) -- A/B tests and measurements on one build; s56 and estS are bit-identical
 #define MM_ISTAGE_OLD_SPOLY56 (1 << 24)
+// forward diagonal f64 sweep (k_qred_f64_mfma<., true, ., .>, mm_f64.hip): give every XCD one contiguous range of work items
+// instead of dealing the tiles of every latent over the eight XCDs -- A/B tests and measurements of the two maps on one build;
+// every workgroup runs the same code on the same operands, so the slab is bit-identical.  (The backward's k_bwd_diag keeps its
+// contiguous map -- dealing its column strips did not clear the noise of the c3_grad row, DESIGN.md 4.5 -- and ignores the bit.)
+#define MM_ISTAGE_OLD_DIAG_MAP (1 << 25)
 
 // kernel families of the pathwise entries' `kernel` argument (mm_pathwise_*_kern): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
 #define MM_PW_KERNELS 3

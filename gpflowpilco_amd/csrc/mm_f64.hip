@@ -23,7 +23,12 @@
 //   pipeline  : diagonal pairs: the tile's operands of batch element b + 1 land in a two-slot LDS ring
 //               (global_load_lds_dwordx4) while b is reduced; off-diagonal pairs: prefetched into a second
 //               register set; per-thread partials of 16 batch elements staged in LDS and reduced together;
-//   grid      : 1-D, remapped so that an XCD owns a contiguous (pair, chunk, tile) range;
+//   grid      : 1-D over work items ordered (pair, chunk, tile), tile fastest.  The diagonal pairs' launch takes them in block
+//               order: the round-robin dispatch deals the consecutive tiles of every (latent, chunk) over the eight XCDs, so
+//               all XCDs work through the same latent together, each on every 8th tile of its norm-ordered triangle.  A
+//               latent's tile tiers follow its own lengthscales (mean degree 6.5 ... 10.4 per latent at the C3 shape,
+//               tools/diag_balance_study.py), and a contiguous range per XCD -- the off-diagonal pairs' map, and the diagonal
+//               pairs' until MM_ISTAGE_OLD_DIAG_MAP -- gave each XCD one whole latent there;
 //   output    : per (b, pair, tile) partial sums -> slab (deterministic, no atomics).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -122,7 +127,7 @@ __device__ __forceinline__ void mmq_f64_body(const double* __restrict__ Zc, int 
                                              const double* __restrict__ beta, int M,
                                              int L, int Mp, int d, int P, int NS, int p0,
                                              int B, int bchunk, int np, int nslots, int nchunk, int nwork,
-                                             int force_worst,
+                                             int force_worst, int deal,
                                              const double* __restrict__ w,
                                              const double* __restrict__ q,
                                              const double* __restrict__ rowA,
@@ -130,13 +135,16 @@ __device__ __forceinline__ void mmq_f64_body(const double* __restrict__ Zc, int 
                                              double* __restrict__ partB,
                                              double* __restrict__ partC, int orig, double (*stage)[256], double (*part16)[16],
                                              double* __restrict__ ring) {
-  // 1-D grid, XCD-aware: workgroups b and b + 8 share an XCD (round-robin dispatch), so the remap
-  // hands every XCD one contiguous range of work items ordered (pair, batch chunk, tile): the
-  // per-batch-element operands of one latent stay in ONE XCD's L2.  Bijective for any nwork.
+  // 1-D grid over work items ordered (pair, batch chunk, tile); workgroups b and b + 8 share an XCD (round-robin dispatch).
+  // deal != 0 (the diagonal pairs' launch): work item = block index, so eight consecutive tiles of a latent go to the eight XCDs
+  // and every XCD carries the same mix of latents and of tile tiers.  deal == 0: the remap hands every XCD one contiguous
+  // range of work items (bijective for any nwork) -- whole latents at the C3 shape, whose modelled costs differ by up to 1.26x
+  // (measured there: 3.22 -> 2.88 ms with the tiles dealt; runs of 8 tiles per XCD read less through L2 but were no faster).
+  // (`deal` is a kernel argument: wave-uniform, no further instantiations.)
   const int nt = Mp / MM_F64_TILE;
   const int xcd = orig & 7, slot = orig >> 3;
   const int qn = nwork >> 3, rn = nwork & 7;
-  const int wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
+  const int wi = deal ? orig : (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
   const int tile = wi % nslots;
   const int chunk = (wi / nslots) % nchunk;
   const int lp = wi / (nslots * nchunk);
@@ -450,7 +458,7 @@ __global__ __launch_bounds__(256, (KS4 >= 6 ? 1 : (DIAG && KS4 <= MM_F64_3WAVE_K
                                                           const double* __restrict__ beta, int M,
                                                           int L, int Mp, int d, int P, int NS, int p0,
                                                           int B, int bchunk, int np, int nslots, int nchunk, int nwork,
-                                                          int force_worst,
+                                                          int force_worst, int deal,
                                                           const double* __restrict__ w,
                                                           const double* __restrict__ q,
                                                           const double* __restrict__ rowA,
@@ -461,7 +469,7 @@ __global__ __launch_bounds__(256, (KS4 >= 6 ? 1 : (DIAG && KS4 <= MM_F64_3WAVE_K
   __shared__ double part16[MM_F64_NB][16];
   __shared__ double ring[DIAG ? 2 * MM_F64_RING_ROWS(KS4) * 64 : 1];
   mmq_f64_body<KS4, DIAG, WITHC, LOWP>(Zc, Kz, Cm, beta, M, L, Mp, d, P, NS, p0, B, bchunk, np, nslots, nchunk, nwork, force_worst,
-                                       w, q, rowA, colB, partB, partC, (int)blockIdx.x, stage, part16, ring);
+                                       deal, w, q, rowA, colB, partB, partC, (int)blockIdx.x, stage, part16, ring);
 }
 
 // Both reduces of a SMALL f64 model in one launch (cartpole sizes: every kernel of the step costs ~ 4-5 us whatever it does, so
@@ -483,10 +491,10 @@ __global__ __launch_bounds__(256, (KS4 >= 6 ? 1 : 2)) void k_qred_f64_both(const
   const int orig = (int)blockIdx.x;
   if (orig < sd.nwork)
     mmq_f64_body<KS4, true, WITHC, false>(Zc, Kz, Cm, beta, M, L, Mp, d, P, NS, sd.p0, B, sd.bchunk, sd.np, sd.nslots, sd.nchunk, sd.nwork,
-                                          force_worst, sd.w, sd.q, sd.rowA, sd.colB, partB, partC, orig, stage, part16, ring);
+                                          force_worst, 0, sd.w, sd.q, sd.rowA, sd.colB, partB, partC, orig, stage, part16, ring);
   else
     mmq_f64_body<KS4, false, false, false>(Zc, Kz, nullptr, beta, M, L, Mp, d, P, NS, so.p0, B, so.bchunk, so.np, so.nslots, so.nchunk,
-                                           so.nwork, force_worst, so.w, so.q, so.rowA, so.colB, partB, partC, orig - sd.nwork, stage,
+                                           so.nwork, force_worst, 0, so.w, so.q, so.rowA, so.colB, partB, partC, orig - sd.nwork, stage,
                                            part16, ring);
 }
 
@@ -552,9 +560,10 @@ int mm_launch_qred_f64_both(const double* Zc, int Kz, const double* Cm, const do
 
 int mm_launch_qred_f64(const double* Zc, int Kz, const double* Cm, const double* beta, int M, int L, int Mp, int d,
                        int P, int NS, int p0, int npairs, int B, int diag, int lowp, int force_worst,
-                       const double* w, const double* q, const double* rowA, const double* colB,
+                       int old_map, const double* w, const double* q, const double* rowA, const double* colB,
                        double* partB, double* partC, hipStream_t stream) {
   if (npairs <= 0) return 0;
+  const int deal = (diag && !old_map) ? 1 : 0;      // diagonal pairs: tiles dealt over the XCDs (MM_ISTAGE_OLD_DIAG_MAP: contiguous ranges)
   const int nslots = mm_f64_num_slots(Mp, diag);
   if (nslots > NS) return MM_E_WORKSPACE;
   // batch chunk: enough workgroups to fill the chip evenly (>= ~32 per CU), as few C re-reads as possible
@@ -577,7 +586,7 @@ int mm_launch_qred_f64(const double* Zc, int Kz, const double* Cm, const double*
   const int ks4 = (d + 3) / 4;
 #define MM_LAUNCH_F64_(KS_, DG_, WC_, LP_)                                                                  \
   hipLaunchKernelGGL((k_qred_f64_mfma<KS_, DG_, WC_, LP_>), grid, dim3(256), 0, stream, Zc, Kz, Cm, beta, M, \
-                     L, Mp, d, P, NS, p0, B, bchunk, npairs, nslots, nchunk, nwork, force_worst, w, q, rowA, colB, partB, partC)
+                     L, Mp, d, P, NS, p0, B, bchunk, npairs, nslots, nchunk, nwork, force_worst, deal, w, q, rowA, colB, partB, partC)
 #define MM_LAUNCH_F64(KS_, DG_)                                                  \
   do {                                                                           \
     const bool wc = DG_ && Cm != nullptr;                                        \

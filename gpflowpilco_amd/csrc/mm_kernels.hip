@@ -1355,7 +1355,7 @@ int mm_launch_qred_f64_both(const double* Zc, int Kz, const double* Cm, const do
                             double* partB, double* partC, hipStream_t stream, bool* launched);
 int mm_launch_qred_f64(const double* Zc, int Kz, const double* Cm, const double* beta, int M, int L, int Mp, int d,
                        int P, int NS, int p0, int npairs, int B, int diag, int lowp, int force_worst,
-                       const double* w, const double* q, const double* rowA, const double* colB,
+                       int old_map, const double* w, const double* q, const double* rowA, const double* colB,
                        double* partB, double* partC, hipStream_t stream);
 int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
                         int B, int L, int d, int flags, hipStream_t stream);
@@ -1581,6 +1581,7 @@ static int mm_Q_reduce_t(const char* packed, const MMModelLayout& ml, bool has_C
       const int rc = mm_launch_qred_f64((const double*)(packed + ml.Zc64), ml.Kz, Cm,
                                         (const double*)(packed + ml.beta64), M, L, wl.Mp, d, wl.P, wl.NS,
                                         0, L, B, 1, sizeof(T) == 4 ? 1 : 0, (flags & MM_FORCE_WORST_TIER) ? 1 : 0,
+                                        (flags & MM_ISTAGE_OLD_DIAG_MAP) ? 1 : 0,
                                         (const double*)(ws + wl.qhR), (const double*)(ws + wl.qhC),   // factored weights
                                         (const double*)(ws + wl.rowD), (const double*)(ws + wl.colD),
                                         partB, partC, s);
@@ -1604,7 +1605,7 @@ static int mm_Q_reduce_t(const char* packed, const MMModelLayout& ml, bool has_C
     } else if (sizeof(T) == 8 && !generic) {
       const int rc = mm_launch_qred_f64((const double*)(packed + ml.Zc64), ml.Kz, nullptr,
                                         (const double*)(packed + ml.beta64), M, L, wl.Mp, d, wl.P, wl.NS,
-                                        L, wl.Po, B, 0, 0, (flags & MM_FORCE_WORST_TIER) ? 1 : 0, (const double*)(ws + wl.w64), (const double*)(ws + wl.q64),
+                                        L, wl.Po, B, 0, 0, (flags & MM_FORCE_WORST_TIER) ? 1 : 0, 0, (const double*)(ws + wl.w64), (const double*)(ws + wl.q64),
                                         (const double*)(ws + wl.rowO), (const double*)(ws + wl.colO),
                                         partB, partC, s);
       if (rc) return rc;

@@ -15,6 +15,8 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--recipe", default="baseline", choices=["baseline", "pilco"])
 ap.add_argument("--reduce", action="store_true", help="also run the two sweeps (stage calls)")
+ap.add_argument("--extra-flags", type=int, default=0,
+                help="internal bits OR-ed into every call, e.g. 33554432 = MM_ISTAGE_OLD_DIAG_MAP (csrc/mm_common.h)")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 L = d = 8; M = 2000
@@ -24,12 +26,19 @@ syn = make_svgp(L, M, d, seed=1002, device=str(dev), **kw)
 pm = syn.to_model(dev).packed(torch.float32, True, dev)
 mu, S = make_inputs(a.batch, d, seed=3002, scale=0.1, lo=lo, hi=hi)
 mu = torch.tensor(mu, dtype=torch.float32, device=dev); S = torch.tensor(S, dtype=torch.float32, device=dev)
-base = ops.make_flags(True, True, False)
+base = ops.make_flags(True, True, False) | a.extra_flags
+t_diag = []
 for _ in range(a.reps):
   ops.q_forward(pm, mu, S, base)
   if a.reduce:
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
     ops.Q_reduce_forward(pm, a.batch, base | F.MM_STAGE_DIAG)
+    e1.record()
+    t_diag.append((e0, e1))
     ops.Q_reduce_forward(pm, a.batch, base | F.MM_STAGE_OFFDIAG)
     ops.Q_reduce_forward(pm, a.batch, base | F.MM_STAGE_FINALIZE)
 torch.cuda.synchronize()
+if t_diag:   # the diagonal sweep's stage call between two events (no profiler needed): every launch, first one included
+  print("diag sweep ms:", " ".join("%.3f" % e0.elapsed_time(e1) for e0, e1 in t_diag))
 print("collapsed, total, inside, routed:", ops.offdiag_stats(pm, a.batch, base))
