@@ -28,6 +28,10 @@ MM_WORKSPACE_CURRENT = 128
 MM_FORCE_ROUTE = 256
 MM_NO_ROUTE = 512
 MM_SUMS_CURRENT = 1024
+# internal A/B bits of the f32 off-diagonal sweep's bound-based tile skipping (csrc/mm_common.h; results are bit-identical):
+# the Euclidean bound at every site / no bound-based skipping at all
+MM_ISTAGE_OLD_SKIP_BOUND = 1 << 26
+MM_ISTAGE_NO_BOUND_SKIP = 1 << 27
 
 ERRORS = {
     -1: "MM_E_ARG: NULL pointer or non-positive size",
@@ -61,6 +65,9 @@ SIGNATURES = {
     "mm_expected_cost": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "mm_offdiag_stats": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mm_offdiag_worklist_len": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mm_offdiag_skip_bounds": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm_route_estimates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mm_compose_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

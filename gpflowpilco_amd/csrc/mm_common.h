@@ -29,6 +29,15 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // every workgroup runs the same code on the same operands, so the slab is bit-identical.  (The backward's k_bwd_diag keeps its
 // contiguous map -- dealing its column strips did not clear the noise of the c3_grad row, DESIGN.md 4.5 -- and ignores the bit.)
 #define MM_ISTAGE_OLD_DIAG_MAP (1 << 25)
+// forward off-diagonal f32 sweep, bound-based skipping of a collapsed row group's column tiles (mm_mfma.hip: ct_first, wave_inside,
+// the need loops, k_offdiag_worklist) -- A/B tests and measurements on one build; a skipped tile is one the screening would have
+// left without adding anything, so every output is bit-identical under all three:
+//   default         : the lengthscale-scaled Cauchy-Schwarz bound |A_i o l_a'| |zc'_j / l_a'| (gmax2s x zt2s)
+//   OLD_SKIP_BOUND  : the Euclidean bound |A_i| |zc'_j| (gmax2 x zt2 / zmax2) at every site
+//   NO_BOUND_SKIP   : no bound-based skipping inside listed items and groups: every tile of a collapsed group goes through the
+//                     screening product, and every item with a collapsed or dense group is listed
+#define MM_ISTAGE_OLD_SKIP_BOUND (1 << 26)
+#define MM_ISTAGE_NO_BOUND_SKIP (1 << 27)
 
 // kernel families of the pathwise entries' `kernel` argument (mm_pathwise_*_kern): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
 #define MM_PW_KERNELS 3
@@ -124,6 +133,9 @@ struct MMModelLayout {
   size_t zt2;     // [L][Mp/32] f32: max |zc_m|^2 over the 32 points of a column tile, rounded up (with the pack in norm order nearly
                   // ascending): the f32 sweep skips the column tiles whose Cauchy-Schwarz bound with the wave's own rows is inside
                   // the collapsed range without touching them (mm_mfma.hip)
+  size_t zt2s;    // [L][Mp/32] f32: max over the tile's real points of sum_k zc_mk^2 / Lambda_k (k < d; the pack's sort key, so
+                  // ascending over the real tiles of a sorted pack; 0 for a tile of padding alone), rounded up: the column side of
+                  // the lengthscale-scaled bound |A_i . zc'_j| <= |A_i o l_a'| |zc'_j / l_a'| that the f32 sweep skips tiles by
   size_t Cm;      // [L][Mp][Mp] f64 Kuu^-1 S Kuu^-1 - Kuu^-1, zero padded (absent: == total).
                   // Always f64: with Kuu jitter 1e-6 its norm reaches 1e6.
   size_t total;
@@ -165,6 +177,7 @@ static inline MMModelLayout mm_model_layout(int L, int M, int d, int dtype, int 
   o.perm = off;   off = mm_align_up(off + (size_t)L * o.Mp * 4, A);
   o.skey = off;   off = mm_align_up(off + (size_t)L * o.Mp * 8, A);
   o.zt2 = off;    off = mm_align_up(off + (size_t)L * (o.Mp / 32) * 4, A);
+  o.zt2s = off;   off = mm_align_up(off + (size_t)L * (o.Mp / 32) * 4, A);
   o.Cm = off;
   if (with_C) off = mm_align_up(off + (size_t)L * o.Mp * o.Mp * 8, A);
   o.total = off;
@@ -324,6 +337,8 @@ struct MMWorkspaceLayout {
   size_t gmax2;    // [B][Po][Mp/64] f32 (f32 mode, d <= 8): max_i |A_i|^2 over the rows of the group, rounded up (k_pairvec_reg): the
                    //              sweep's Cauchy-Schwarz skipping reads it instead of the rows (a collapsed group all of whose
                    //              tiles are inside the collapsed range loads nothing at all)
+  size_t gmax2s;   // [B][Po][Mp/64] f32 (f32 mode, d <= 8): max_i |A_i o l_a'|^2 = max_i sum_k (u_k + t0_k)^2 / Lambda_a',k over the rows of
+                   //              the group, rounded up (k_pairvec_reg): the row side of the lengthscale-scaled bound (MMModelLayout::zt2s)
   size_t partB;    // [B][P][NS] f64 partial sums of w_i expm1(delta_ij) w_j
   size_t partC;    // [B][L][NS] f64 partial sums of C_ij q_i expm1(delta_ij) q_j  (+ q^T C q)
   size_t mu64;     // [B][d] f64    the state mean as the q stage read it (mm_route.hip re-derives A_i = G^T (z_i - mu) in f64)
@@ -390,6 +405,7 @@ static inline MMWorkspaceLayout mm_workspace_layout(int B, int L, int M, int d, 
   o.amaxc = off;   off = mm_align_up(off + (size_t)B * o.Po * 4, A);
   o.gflag = off;   off = mm_align_up(off + (dtype == MM_F64 ? 0 : (size_t)B * o.Po * (o.Mp / 64)), A);
   o.gmax2 = off;   off = mm_align_up(off + (dtype == MM_F64 ? 0 : (size_t)B * o.Po * (o.Mp / 64) * 4), A);
+  o.gmax2s = off;  off = mm_align_up(off + (dtype == MM_F64 ? 0 : (size_t)B * o.Po * (o.Mp / 64) * 4), A);
   o.gperm = off;   off = mm_align_up(off + (dtype == MM_F64 || L < 2 ? 0 : ((size_t)L * (L - 1) * B + 3 * L) * 4), A);
   o.s12 = off;     off = mm_align_up(off + (size_t)B * o.Po * 8, A);
   o.partB = off;   off = mm_align_up(off + (size_t)B * o.P * o.NS * 8, A);

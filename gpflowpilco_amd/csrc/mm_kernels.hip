@@ -263,17 +263,25 @@ __global__ void k_pack_vectors(char* packed, MMModelLayout lay, int L, int M, in
     if (tid == 0) ((double*)(packed + lay.zmax2))[a] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
     __syncthreads();
     // the same per 32-point column tile (MMModelLayout::zt2)
+    // ... and in the lengthscale-scaled metric, sum_k zc_k^2 / Lambda_k (MMModelLayout::zt2s; the padding points count as 0)
     float* zt2 = (float*)(packed + lay.zt2) + (size_t)a * (lay.Mp / 32);
+    float* zt2s = (float*)(packed + lay.zt2s) + (size_t)a * (lay.Mp / 32);
     for (int t = tid; t < lay.Mp / 32; t += 256) {
-      double mx = 0.0;
+      double mx = 0.0, mxs = 0.0;
       for (int j = 0; j < 32; ++j) {
         const int m = t * 32 + j;
         if (m >= M) break;
-        double s2 = 0.0;
-        for (int k = 0; k < d; ++k) { const double v = Z[((size_t)a * M + m) * d + k] - zb[k]; s2 += v * v; }
+        double s2 = 0.0, s2s = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double v = Z[((size_t)a * M + m) * d + k] - zb[k], l = ls[a * d + k];
+          s2 += v * v;
+          s2s += v * v / (l * l);
+        }
         mx = s2 > mx ? s2 : mx;
+        mxs = s2s > mxs ? s2s : mxs;
       }
       zt2[t] = (float)(mx * 1.000001);
+      zt2s[t] = (float)(mxs * 1.000001);
     }
   }
   if (sizeof(T) != 8) {
@@ -655,7 +663,8 @@ __global__ __launch_bounds__(256) void k_pairvec(const double* __restrict__ Zt64
                                                  double* __restrict__ qhC, int with_unc, int nblk,
                                                  const double* __restrict__ lq, const double* __restrict__ beta64,
                                                  const double* __restrict__ zmax2, unsigned short* __restrict__ /* wsp: d <= 8 only */,
-                                                 unsigned char* __restrict__ /* gflag */, float* __restrict__ /* gmax2 */, int /* allow */, int p0) {
+                                                 unsigned char* __restrict__ /* gflag */, float* __restrict__ /* gmax2 */, float* __restrict__ /* gmax2s */,
+                                                 int /* allow */, int p0) {
   static_assert(DK > 8, "d <= 8 takes k_pairvec_reg");
   // a workgroup owns the 256-row chunks blockIdx.x, blockIdx.x + gridDim.x, ... of one (b, pair): the
   // pair's matrix is fetched once per workgroup, not once per chunk
@@ -841,7 +850,7 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
                                                     double (*vecs)[DK], const double* __restrict__ lq,
                                                     const double* __restrict__ beta64, int p, const double* __restrict__ zmax2,
                                                     unsigned short* __restrict__ wsp, unsigned char* __restrict__ gflag, float* __restrict__ gmax2,
-                                                    int allow) {
+                                                    float* __restrict__ gmax2s, int allow) {
   constexpr bool diag = MODE == 0;
   const int b = blockIdx.z, tid = threadIdx.x;
   const int Po = P - L;
@@ -955,6 +964,7 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
   const double cst = pm[d * d];
   float a2max = 0.0f;                                         // max_i |A_i|^2 over this thread's rows (f32 off-diagonal pairs)
   float a2cmax = 0.0f, a2in = 0.0f;                           // ... over the rows of COLLAPSED groups alone (mm_mono.h: row-group collapse)
+  float a2sin = 0.0f;                                         // this row's |A_i o l_a'|^2 (MMWorkspaceLayout::gmax2s)
   const bool cancoll = MODE == 1 && allow && recentred;       // no group is collapsed where the caller rules it out or the rows stay at mu
   const double zm2c = MODE == 1 ? zmax2[a2] : 0.0;
   typedef const __attribute__((address_space(3))) double* lds_cptr;
@@ -1023,7 +1033,7 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
           sr[k] = (o.zr[k] - muk) * vl[DK + k]; sc[k] = (o.zc[k] - muk) * vl[2 * DK + k];
           cj = fma(vl[5 * DK + k], sc[k], cj);
         }
-        double tA = 0.0, tg = 0.0, corrA = 0.0, asq = 0.0;
+        double tA = 0.0, tg = 0.0, corrA = 0.0, asq = 0.0, asqs = 0.0;
 #pragma unroll
         for (int i = 0; i < DK; ++i) {
           double u = 0.0, vh = 0.0;
@@ -1037,6 +1047,7 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
           tg = fma(sc[i], fma(2.0, vh, Tr[tsym(i, i)] * sc[i]), tg);
           const double av = (u + vl[5 * DK + i]) * vl[2 * DK + i];   // A_i = G^T (z_i - zbar_a)  (G^T (z_i - mu) if not recentred)
           asq = fma(av, av, asq);
+          asqs = fma(u + vl[5 * DK + i], av, asqs);          // (u_i + t0_i)^2 / Lam_a',i = |A_i l_a',i|^2: the scaled norm
           corrA = fma(vl[3 * DK + i], u, corrA);
           rO[rowi(i) + m] = (T)av;
         }
@@ -1044,12 +1055,13 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
         a2max = fmaxf(a2max, a2row);
         rowok = mm_collapse_bound2(__float_as_uint(a2row), zm2c) <= MM_COLLAPSE_BOUND2;
         a2in = a2row;
+        a2sin = (float)asqs * 1.000001f;
         whr = o.br * exp(fmin(o.wr - 0.5 * (o.r1r - tA) + cst - corrA, (double)MM_EXP_CAP_F32));
         whc = o.bc * exp(fmin(o.wc - 0.5 * (o.r1c - tg) - cj, (double)MM_EXP_CAP_F32));
       } else {
 #pragma unroll
         for (int i = 0; i < DK; ++i) rO[rowi(i) + m] = (T)0;  // zero rows: b = 0 in the padding
-        a2in = 0.0f;
+        a2in = 0.0f; a2sin = 0.0f;
       }
       rO[rowd + m] = (T)whr; cO[m] = (T)whc; hR[m] = whr; hC[m] = whc;
       if (wsp) {
@@ -1059,10 +1071,14 @@ __device__ __forceinline__ void mm_pairvec_reg_body(const double* __restrict__ Z
         float g2 = a2in;                                     // the group's max |A_i|^2 (MMWorkspaceLayout::gmax2)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) g2 = fmaxf(g2, __shfl_xor(g2, off, 64));
+        float g2s = a2sin;                                   // ... and its max |A_i o l_a'|^2 (gmax2s)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) g2s = fmaxf(g2s, __shfl_xor(g2s, off, 64));
         if ((tid & 63) == 0) {
           const size_t gi = ((size_t)b * Po + (p - L)) * (size_t)(Mp / MM_GROUP_ROWS) + (m >> 6);
           gflag[gi] = inner ? 1 : 0;
           gmax2[gi] = g2;
+          gmax2s[gi] = g2s;
         }
         if (inner) a2cmax = fmaxf(a2cmax, a2in);
         // bf16 2-way split of both weights: the A operand of the degree-4/5/6 moment GEMM (mm_moments6.hip), [side][h, m][Mp];
@@ -1142,7 +1158,8 @@ __global__ __launch_bounds__(256, 2) void k_pairvec_reg(const double* __restrict
                                                         double* __restrict__ qhC, int with_unc, int nblk,
                                                         const double* __restrict__ lq, const double* __restrict__ beta64,
                                                         const double* __restrict__ zmax2, unsigned short* __restrict__ wsp,
-                                                        unsigned char* __restrict__ gflag, float* __restrict__ gmax2, int allow, int p0) {
+                                                        unsigned char* __restrict__ gflag, float* __restrict__ gmax2,
+                                                        float* __restrict__ gmax2s, int allow, int p0) {
   // (grid.y = the pairs [p0, p0 + gridDim.y): the q stage launches the diagonal pairs' operands first -- the diagonal sweep needs
   // nothing else -- and the off-diagonal pairs' on the side stream beside that sweep)
   static_assert(DK <= 8, "register form: d <= 8");
@@ -1153,7 +1170,7 @@ __global__ __launch_bounds__(256, 2) void k_pairvec_reg(const double* __restrict
   mm_decode_pair(p, L, a, a2);
 #define MM_PV_BODY(MODE_)                                                                                           \
   mm_pairvec_reg_body<T, DK, MODE_>(Zt64, zbar, ls2, L, M, Mp, d, P, mu, pairmat, rho1, rowD, colD, rowO, colO, w64, \
-                                    whR, whC, amax, q64, qhR, qhC, with_unc, nblk, a, a2, vecs, lq, beta64, p, zmax2, wsp, gflag, gmax2, allow)
+                                    whR, whC, amax, q64, qhR, qhC, with_unc, nblk, a, a2, vecs, lq, beta64, p, zmax2, wsp, gflag, gmax2, gmax2s, allow)
   if (p < L) MM_PV_BODY(0);
   else if (sizeof(T) == 4) MM_PV_BODY(1);
   else MM_PV_BODY(2);
@@ -1493,7 +1510,7 @@ static int mm_q_forward_t(const char* packed, const MMModelLayout& ml, char* ws,
     (const double*)(ws + wl.q64), (double*)(ws + wl.qhR), (double*)(ws + wl.qhC), (flags & MM_MODEL_UNCERTAINTY) ? 1 : 0, nblk, \
     (const double*)(ws + wl.lq), (const double*)(packed + ml.beta64), (const double*)(packed + ml.zmax2),                       \
     ((sizeof(T) == 4 && d <= 8) ? (unsigned short*)(ws + wl.wsp) : (unsigned short*)nullptr),                                \
-    (unsigned char*)(ws + wl.gflag), (float*)(ws + wl.gmax2), ((flags & (MM_FORCE_WORST_TIER | MM_ISTAGE_NO_M56)) ? 0 : 1)
+    (unsigned char*)(ws + wl.gflag), (float*)(ws + wl.gmax2), (float*)(ws + wl.gmax2s), ((flags & (MM_FORCE_WORST_TIER | MM_ISTAGE_NO_M56)) ? 0 : 1)
     auto pairvec = [&](int p0, int npairs, hipStream_t st) {
       if (npairs <= 0) return;
       if constexpr (DK <= 8) {

@@ -37,6 +37,31 @@ __device__ __forceinline__ void mm_decode_pair_o(int p, int L, int& a, int& a2) 
   a = i; a2 = i + 1 + r;
 }
 
+// BOUND-BASED SKIPPING of a collapsed row group's column tiles.  For any positive scale vector s, |A_i . zc'_j| <= |A_i o s| |zc'_j / s|
+// (Cauchy-Schwarz in the scaled metric).  With s = l_a' (the column latent's lengthscales) the column factor is the pack's sort key
+// (MMModelLayout::zt2s per 32-column tile) and the row factor is MMWorkspaceLayout::gmax2s per 64-row group (k_pairvec_reg); with
+// lengthscales spread over a decade |A_i| and |zc'_j| are dominated by different dimensions and the Euclidean product (gmax2 x zt2)
+// is loose: on the BASELINE recipe at C3 it leaves 13 x the wave tiles to the screening product that the scaled one does
+// (tools/pack_order_study.py section 4).  gmax2s == nullptr (d > 8 has no row groups; MM_ISTAGE_OLD_SKIP_BOUND): the Euclidean test.
+// The collapse DECISION (gflag, amax, amaxc, gmax2, MM_COLLAPSE_BOUND2), thr_skip and the error estimate stay Euclidean.
+//
+// the largest zt2s of a latent (every lane of the wave calls; the result is wave-uniform)
+__device__ __forceinline__ float mm_wave_max_tiles(const float* __restrict__ zt, int nct, int lane) {
+  float m = 0.0f;
+  for (int c = lane; c < nct; c += 64) m = fmaxf(m, zt[c]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  return m;
+}
+// group gi has no tile to visit: its bound with the latent's largest point is inside the collapsed range (zsmax: mm_wave_max_tiles
+// of zt2s, read where gmax2s != nullptr only).  The same products, factor by factor, as the tile scan at ct_first: a group is
+// inside exactly when that scan finds no tile (f32 multiplication by a2w >= 0 is monotone)
+__device__ __forceinline__ bool mm_group_inside(const float* __restrict__ gmax2, const float* __restrict__ gmax2s, size_t gi,
+                                                double zmax2a, float zsmax) {
+  return gmax2s ? (gmax2s[gi] * 1.000001f) * zsmax <= MM_INSIDE_BOUND2
+                : mm_collapse_bound2(__float_as_uint(gmax2[gi]), zmax2a) <= MM_INSIDE_BOUND2;
+}
+
 // largest tile range max|b| for which the 2-way (h + m) product is used without the (h,l)/(l,h) terms
 // (measured at C3: 1/64, 1/32 and 1/16 all leave the Sff error at 3.5e-6; 1/32 keeps a factor 4 in hand)
 #ifndef MM_TWO_WAY_MAX
@@ -138,6 +163,8 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
                                                           const unsigned int* __restrict__ amaxc,
                                                           const unsigned char* __restrict__ gflag, const float* __restrict__ gmax2,
                                                           const double* __restrict__ zmax2, const float* __restrict__ zt2,
+                                                          const float* __restrict__ gmax2s, const float* __restrict__ zt2s,
+                                                          int noskip,
                                                           const float* __restrict__ rowO,
                                                           const float* __restrict__ colO,
                                                           double* __restrict__ partB, float* __restrict__ estO,
@@ -163,7 +190,9 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
   if constexpr (ND8 == 1) {
     // Cauchy-Schwarz already bounds every |b_ij| of this (b, pair) by MM_C6_MAX: the remainder is p6 everywhere, which the
     // moments carry (k_spoly, k_spoly56) -- every tile would be skipped: no sweep at all
-    if (!force_worst && zmax2 && mm_collapse_bound2(amax[(size_t)b * Po + lp], zmax2[a2]) <= MM_INSIDE_BOUND2) {
+    // (noskip -- MM_ISTAGE_NO_BOUND_SKIP: an item with collapsed groups stays and its tiles go through the screening product)
+    if (!force_worst && zmax2 && mm_collapse_bound2(amax[(size_t)b * Po + lp], zmax2[a2]) <= MM_INSIDE_BOUND2 &&
+        !(noskip && mm_item_collapsed(amaxc[(size_t)b * Po + lp]))) {
       for (int panel = (int)threadIdx.x; panel < npanel; panel += 256) {
         if (panel % npw != pgrp) continue;                   // (this workgroup's panels: pgrp, pgrp + npw, ...)
         partB[((size_t)b * P + p) * NS + panel] = 0.0;
@@ -179,13 +208,16 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
   const bool icoll_wg = (ND8 == 1) && !force_worst && zmax2 != nullptr && zt2 != nullptr && gmax2 != nullptr &&
                         mm_item_collapsed(amaxc[(size_t)b * Po + lp]);
   const size_t grp0 = ((size_t)b * Po + lp) * (size_t)(Mp / MM_GROUP_ROWS);
+  // scaled: the skip sites take the lengthscale-scaled bound (gmax2s x zt2s), else the Euclidean one (wave-uniform)
+  const bool scaled = gmax2s != nullptr && zt2s != nullptr;
   if constexpr (ND8 == 1) {
-    if (icoll_wg) {
+    if (icoll_wg && !noskip) {
+      const float zsmax = scaled ? mm_wave_max_tiles(zt2s + (size_t)a2 * (Mp >> 5), Mp >> 5, lane) : 0.0f;
       bool need = false;
       for (int panel = pgrp; panel < npanel; panel += npw) {
         const int g = (panel * MM_PANEL_ROWS + wv * 64) >> 6;
         if (g < Mp / MM_GROUP_ROWS)
-          need = need || !(gflag[grp0 + g] != 0 && mm_collapse_bound2(__float_as_uint(gmax2[grp0 + g]), zmax2[a2]) <= MM_INSIDE_BOUND2);
+          need = need || !(gflag[grp0 + g] != 0 && mm_group_inside(gmax2, scaled ? gmax2s : nullptr, grp0 + g, zmax2[a2], zsmax));
       }
       if (!__syncthreads_or(need ? 1 : 0)) {
         for (int panel = (int)threadIdx.x; panel < npanel; panel += 256) {
@@ -239,9 +271,46 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
   // k_pairvec_reg decided, with the Cauchy-Schwarz bound of the group's rows, |b_ij| <= |A_i| |zc_j|); g2: its rows' max |A_i|^2
   const bool icoll = icoll_wg;
   const bool coll = icoll && row0 < Mp && gflag[grp0 + (row0 >> 6)] != 0;
-  const float g2 = coll ? gmax2[grp0 + (row0 >> 6)] : 0.0f;
-  // (a collapsed group with every tile inside the collapsed range: nothing to load, nothing to add)
-  const bool wave_inside = coll && mm_collapse_bound2(__float_as_uint(g2), zmax2[a2]) <= MM_INSIDE_BOUND2;
+  // (with the scaled skip bound g2 is the group's max |A_i o l_a'|^2, gmax2s)
+  const float g2 = coll ? (scaled ? gmax2s : gmax2)[grp0 + (row0 >> 6)] : 0.0f;
+  // A collapsed row group visits the column tiles [ct_first, ct_end) alone: it skips, without touching them, the tiles whose
+  // Cauchy-Schwarz bound with ITS rows is inside the collapsed range,
+  //     max_i |A_i o l_a'|^2 (this wave's rows: gmax2s) x max_j |zc'_j / l_a'|^2 (the tile's real points: zt2s) <= MM_INSIDE_BOUND2
+  // (Euclidean norms, gmax2 x zt2, where scaled is false).  zt2s is the pack's sort key, so the tiles inside are a PREFIX of a sorted
+  // pack, then come the tiles to visit, then the tiles of padding alone (zt2s = 0: b = 0 there); whatever the order, every tile
+  // before the first and after the last one outside the bound is inside it.  On the BASELINE recipe at C3 the scaled bound leaves
+  // 8 % of the wave tiles to the screening product that the Euclidean one does (and the product finds 98 % of those inside).
+  // RIGOUR: a skipped tile must be one the screened path leaves without adding anything -- the max |b| of its COMPUTED two-way
+  // product is <= MM_C6_MAX, so that process_tile returns at its first or its second check with (emx, ewc) = 0.  The exact
+  // |b_ij| = |sum_k (A_ik l_k) (zc'_jk / l_k)| <= |A_i o l| |zc'_j / l| <= sqrt(0.998) / 4 by Cauchy-Schwarz in the scaled metric.
+  // What the computed value adds -- the f32 rounding of A_i and zc'_j, the bf16 split product without the terms of its l parts,
+  // the f32 accumulation -- is bounded relative to sum_k |A_ik| |zc'_jk| <= |A_i| |zc'_j| (2^-16 of it and less), and that
+  // EUCLIDEAN product is <= 1/2 because the group is collapsed (MM_COLLAPSE_BOUND2): <= 1e-5 absolute against the margin
+  // (1 - sqrt(0.998)) / 4 = 2.5e-4 of MM_INSIDE_BOUND2, exactly as for the Euclidean skip.  Both arrays are rounded UP from f64
+  // (k_pairvec_reg, k_pack_vectors: 1e-6 relative), and a2w adds the same again for the f32-rounded operands (< 2e-7).
+  // noskip (MM_ISTAGE_NO_BOUND_SKIP): every tile goes through the screening product
+  int ct_first = 0, ct_end = Mp >> 5;
+  bool wave_inside = false;
+  if (coll && !noskip) {
+    const int nctw = Mp >> 5;
+    const float a2w = g2 * 1.000001f;
+    const float* zt = (scaled ? zt2s : zt2) + (size_t)a2 * nctw;
+    int cf = nctw, cl = -1;
+    for (int c0 = 0; c0 < nctw; c0 += 64) {
+      const int c = c0 + lane;
+      const bool outside = c < nctw && a2w * zt[c < nctw ? c : 0] > MM_INSIDE_BOUND2;
+      const unsigned long long bal = __ballot(outside);
+      if (bal) {
+        if (cf == nctw) cf = c0 + (int)__builtin_ctzll(bal);
+        cl = c0 + 63 - (int)__builtin_clzll(bal);
+      }
+    }
+    ct_first = cf & ~1;
+    // (the Euclidean test as it was: to the last tile, and a group is inside by the latent's zmax2)
+    if (scaled) ct_end = (cl + 2) & ~1;
+    // (a collapsed group with every tile inside the collapsed range: nothing to load, nothing to add)
+    wave_inside = scaled ? cf >= nctw : mm_collapse_bound2(__float_as_uint(g2), zmax2[a2]) <= MM_INSIDE_BOUND2;
+  }
   if (row0 < Mp && !wave_inside) {   // Mp % 128 == 0, so a wave's 64 rows are all inside or all outside
     const float* ra = rowO + ((size_t)b * Po + lp) * (size_t)(d + 1) * Mp;   // [d+1][Mp]: A_i, what_i
     const float* wcf = colO + ((size_t)b * Po + lp) * Mp;                    // what'_j
@@ -444,38 +513,22 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
     // two-stage register ping-pong: tile ct + 1 is in flight while tile ct is reduced.  (Issuing the MFMAs
     // of tile ct + 1 interleaved with the v_max3 range check of tile ct -- a second accumulator set,
     // 182 VGPRs -- was measured: 4.27 ms against 4.25 ms; three waves per SIMD already overlap the two.)
-    // A collapsed row group skips, without touching them, the column tiles whose Cauchy-Schwarz bound with ITS rows is inside the
-    // collapsed range: max_i |A_i|^2 (this wave's rows) x max_j |zc'_j|^2 (the tile's 32 points, MMModelLayout::zt2) <=
-    // MM_INSIDE_BOUND2.  The pack's norm order makes those tiles a PREFIX: the sweep starts at the first tile that is not
-    // (BASELINE recipe: two thirds of the screened wave tiles; the screening product + range check was half the sweep's time).
-    int ct_first = 0;
-    if (coll) {
-      const float a2w = g2 * 1.000001f;                     // (gmax2 is rounded up from f64; the f32-rounded operands add < 2e-7)
-      const float* zt = zt2 + (size_t)a2 * nct;
-      int cf = nct;
-      for (int c0 = 0; c0 < nct; c0 += 64) {
-        const int c = c0 + lane;
-        const bool outside = c < nct && a2w * zt[c < nct ? c : 0] > MM_INSIDE_BOUND2;
-        const unsigned long long bal = __ballot(outside);
-        if (bal) { cf = c0 + (int)__builtin_ctzll(bal); break; }
-      }
-      ct_first = cf & ~1;
-    }
+    // (a collapsed row group sweeps [ct_first, ct_end): above)
     auto sweep = [&](auto collc, auto collm) __attribute__((always_inline)) {
       constexpr bool CM = decltype(collc)::value;
       u32x4 zA0[ND8], zB0[ND8], zA1[ND8], zB1[ND8];
       float w0, w1;
       w0 = w1 = 0.0f;
-      const int ct0 = CM ? ct_first : 0;
-      if (ct0 >= nct) return;
+      const int ct0 = CM ? ct_first : 0, cte = CM ? ct_end : nct;
+      if (ct0 >= cte) return;
       load_zA(ct0, zA0);
       if constexpr (!CM) { load_zB(0, zB0); w0 = wcf[l31]; }
-      for (int ct = ct0; ct < nct; ct += 2) {
+      for (int ct = ct0; ct < cte; ct += 2) {
         load_zA(ct + 1, zA1);
         if constexpr (!CM) { load_zB(ct + 1, zB1); w1 = wcf[(ct + 1) * 32 + l31]; }
         float emx0, ewc0, emx1, ewc1;
         process_tile(collc, collm, ct, zA0, zB0, w0, emx0, ewc0);
-        const int cn = ct + 2 < nct ? ct + 2 : ct;               // clamped: the last pass re-reads its own tile
+        const int cn = ct + 2 < cte ? ct + 2 : ct;               // clamped: the last pass re-reads its own tile
         load_zA(cn, zA0);
         if constexpr (!CM) { load_zB(cn, zB0); w0 = wcf[cn * 32 + l31]; }
         process_tile(collc, collm, ct + 1, zA1, zB1, w1, emx1, ewc1);
@@ -525,16 +578,18 @@ __global__ __launch_bounds__(256, (ND8 >= 4 ? 1 : MM_F32_WAVES)) void k_qred_f32
 // LDS and nothing else changed: the same tiles, tiers, per-lane accumulation and estimate, so the two sweeps' slabs agree to the bit
 // (tests/test_gpu_offdiag_persist.py).  (k_qred_f32_mfma keeps its own copy of the body: compiled through this function its register
 // allocation changed and its forced-worst-tier regime lost 1.3 %.)
-// icoll: the item has collapsed row groups (k_qred_f32_mfma's icoll_wg); grp0: the item's first entry of gflag / gmax2.
+// icoll: the item has collapsed row groups (k_qred_f32_mfma's icoll_wg); grp0: the item's first entry of gflag / gmax2 / gmax2s.
 template <int ND8>
 __device__ __forceinline__ void mm_f32_wave_rows(const char* zlds, const float* wlds,
                                                  int row0, int b, int lp, int a2, int Mp, int d, int Po, int force_worst,
                                                  bool icoll, size_t grp0, const unsigned int* __restrict__ amaxc,
                                                  const unsigned char* __restrict__ gflag, const float* __restrict__ gmax2,
                                                  const double* __restrict__ zmax2, const float* __restrict__ zt2,
+                                                 const float* __restrict__ gmax2s, const float* __restrict__ zt2s, int noskip,
                                                  const float* __restrict__ rowO,
                                                  double& sum_out, float& estl_out) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
+  const bool scaled = gmax2s != nullptr && zt2s != nullptr;       // (k_qred_f32_mfma's: the skip bound's metric)
   double sum = 0.0;
   // running estimate of the sweep's own rounding error (mm_common.h: MM_ROUTE_TOL; mm_route.hip): per lane -- one column,
   // the lane's 32 rows -- sum over the reduced tiles of (max|b|^3 what'_j)^2, two tiles per packed instruction; the rows' sum
@@ -545,9 +600,46 @@ __device__ __forceinline__ void mm_f32_wave_rows(const char* zlds, const float* 
   // is not collapsed reduces r(b) - C0 b^3 on every tile.  coll: this wave's 64 rows are a COLLAPSED row group (mm_mono.h:
   // k_pairvec_reg decided, with the Cauchy-Schwarz bound of the group's rows, |b_ij| <= |A_i| |zc_j|); g2: its rows' max |A_i|^2
   const bool coll = icoll && row0 < Mp && gflag[grp0 + (row0 >> 6)] != 0;
-  const float g2 = coll ? gmax2[grp0 + (row0 >> 6)] : 0.0f;
-  // (a collapsed group with every tile inside the collapsed range: nothing to load, nothing to add)
-  const bool wave_inside = coll && mm_collapse_bound2(__float_as_uint(g2), zmax2[a2]) <= MM_INSIDE_BOUND2;
+  // (with the scaled skip bound g2 is the group's max |A_i o l_a'|^2, gmax2s)
+  const float g2 = coll ? (scaled ? gmax2s : gmax2)[grp0 + (row0 >> 6)] : 0.0f;
+  // A collapsed row group visits the column tiles [ct_first, ct_end) alone: it skips, without touching them, the tiles whose
+  // Cauchy-Schwarz bound with ITS rows is inside the collapsed range,
+  //     max_i |A_i o l_a'|^2 (this wave's rows: gmax2s) x max_j |zc'_j / l_a'|^2 (the tile's real points: zt2s) <= MM_INSIDE_BOUND2
+  // (Euclidean norms, gmax2 x zt2, where scaled is false).  zt2s is the pack's sort key, so the tiles inside are a PREFIX of a sorted
+  // pack, then come the tiles to visit, then the tiles of padding alone (zt2s = 0: b = 0 there); whatever the order, every tile
+  // before the first and after the last one outside the bound is inside it.  On the BASELINE recipe at C3 the scaled bound leaves
+  // 8 % of the wave tiles to the screening product that the Euclidean one does (and the product finds 98 % of those inside).
+  // RIGOUR: a skipped tile must be one the screened path leaves without adding anything -- the max |b| of its COMPUTED two-way
+  // product is <= MM_C6_MAX, so that process_tile returns at its first or its second check with (emx, ewc) = 0.  The exact
+  // |b_ij| = |sum_k (A_ik l_k) (zc'_jk / l_k)| <= |A_i o l| |zc'_j / l| <= sqrt(0.998) / 4 by Cauchy-Schwarz in the scaled metric.
+  // What the computed value adds -- the f32 rounding of A_i and zc'_j, the bf16 split product without the terms of its l parts,
+  // the f32 accumulation -- is bounded relative to sum_k |A_ik| |zc'_jk| <= |A_i| |zc'_j| (2^-16 of it and less), and that
+  // EUCLIDEAN product is <= 1/2 because the group is collapsed (MM_COLLAPSE_BOUND2): <= 1e-5 absolute against the margin
+  // (1 - sqrt(0.998)) / 4 = 2.5e-4 of MM_INSIDE_BOUND2, exactly as for the Euclidean skip.  Both arrays are rounded UP from f64
+  // (k_pairvec_reg, k_pack_vectors: 1e-6 relative), and a2w adds the same again for the f32-rounded operands (< 2e-7).
+  // noskip (MM_ISTAGE_NO_BOUND_SKIP): every tile goes through the screening product
+  int ct_first = 0, ct_end = Mp >> 5;
+  bool wave_inside = false;
+  if (coll && !noskip) {
+    const int nctw = Mp >> 5;
+    const float a2w = g2 * 1.000001f;
+    const float* zt = (scaled ? zt2s : zt2) + (size_t)a2 * nctw;
+    int cf = nctw, cl = -1;
+    for (int c0 = 0; c0 < nctw; c0 += 64) {
+      const int c = c0 + lane;
+      const bool outside = c < nctw && a2w * zt[c < nctw ? c : 0] > MM_INSIDE_BOUND2;
+      const unsigned long long bal = __ballot(outside);
+      if (bal) {
+        if (cf == nctw) cf = c0 + (int)__builtin_ctzll(bal);
+        cl = c0 + 63 - (int)__builtin_clzll(bal);
+      }
+    }
+    ct_first = cf & ~1;
+    // (the Euclidean test as it was: to the last tile, and a group is inside by the latent's zmax2)
+    if (scaled) ct_end = (cl + 2) & ~1;
+    // (a collapsed group with every tile inside the collapsed range: nothing to load, nothing to add)
+    wave_inside = scaled ? cf >= nctw : mm_collapse_bound2(__float_as_uint(g2), zmax2[a2]) <= MM_INSIDE_BOUND2;
+  }
   if (row0 < Mp && !wave_inside) {   // Mp % 128 == 0, so a wave's 64 rows are all inside or all outside
     const float* ra = rowO + ((size_t)b * Po + lp) * (size_t)(d + 1) * Mp;   // [d+1][Mp]: A_i, what_i
     // bound2: the bound over all collapsed groups of the item (the screening margin)
@@ -744,38 +836,22 @@ __device__ __forceinline__ void mm_f32_wave_rows(const char* zlds, const float* 
     // two-stage register ping-pong: tile ct + 1 is in flight while tile ct is reduced.  (Issuing the MFMAs
     // of tile ct + 1 interleaved with the v_max3 range check of tile ct -- a second accumulator set,
     // 182 VGPRs -- was measured: 4.27 ms against 4.25 ms; three waves per SIMD already overlap the two.)
-    // A collapsed row group skips, without touching them, the column tiles whose Cauchy-Schwarz bound with ITS rows is inside the
-    // collapsed range: max_i |A_i|^2 (this wave's rows) x max_j |zc'_j|^2 (the tile's 32 points, MMModelLayout::zt2) <=
-    // MM_INSIDE_BOUND2.  The pack's norm order makes those tiles a PREFIX: the sweep starts at the first tile that is not
-    // (BASELINE recipe: two thirds of the screened wave tiles; the screening product + range check was half the sweep's time).
-    int ct_first = 0;
-    if (coll) {
-      const float a2w = g2 * 1.000001f;                     // (gmax2 is rounded up from f64; the f32-rounded operands add < 2e-7)
-      const float* zt = zt2 + (size_t)a2 * nct;
-      int cf = nct;
-      for (int c0 = 0; c0 < nct; c0 += 64) {
-        const int c = c0 + lane;
-        const bool outside = c < nct && a2w * zt[c < nct ? c : 0] > MM_INSIDE_BOUND2;
-        const unsigned long long bal = __ballot(outside);
-        if (bal) { cf = c0 + (int)__builtin_ctzll(bal); break; }
-      }
-      ct_first = cf & ~1;
-    }
+    // (a collapsed row group sweeps [ct_first, ct_end): above)
     auto sweep = [&](auto collc, auto collm) __attribute__((always_inline)) {
       constexpr bool CM = decltype(collc)::value;
       u32x4 zA0[ND8], zB0[ND8], zA1[ND8], zB1[ND8];
       float w0, w1;
       w0 = w1 = 0.0f;
-      const int ct0 = CM ? ct_first : 0;
-      if (ct0 >= nct) return;
+      const int ct0 = CM ? ct_first : 0, cte = CM ? ct_end : nct;
+      if (ct0 >= cte) return;
       load_zA(ct0, zA0);
       if constexpr (!CM) { load_zB(0, zB0); w0 = load_wc(l31); }
-      for (int ct = ct0; ct < nct; ct += 2) {
+      for (int ct = ct0; ct < cte; ct += 2) {
         load_zA(ct + 1, zA1);
         if constexpr (!CM) { load_zB(ct + 1, zB1); w1 = load_wc((ct + 1) * 32 + l31); }
         float emx0, ewc0, emx1, ewc1;
         process_tile(collc, collm, ct, zA0, zB0, w0, emx0, ewc0);
-        const int cn = ct + 2 < nct ? ct + 2 : ct;               // clamped: the last pass re-reads its own tile
+        const int cn = ct + 2 < cte ? ct + 2 : ct;               // clamped: the last pass re-reads its own tile
         load_zA(cn, zA0);
         if constexpr (!CM) { load_zB(cn, zB0); w0 = load_wc(cn * 32 + l31); }
         process_tile(collc, collm, ct + 1, zA1, zB1, w1, emx1, ewc1);
@@ -838,7 +914,8 @@ static inline size_t mm_f32p_lds_bytes(int Mp) {
 __global__ __launch_bounds__(256) void k_offdiag_worklist(int L, int Mp, int P, int Po, int NS, int npanel, int B, int force_worst,
                                                           const unsigned int* __restrict__ amax, const unsigned int* __restrict__ amaxc,
                                                           const unsigned char* __restrict__ gflag, const float* __restrict__ gmax2,
-                                                          const double* __restrict__ zmax2, double* __restrict__ partB,
+                                                          const double* __restrict__ zmax2, const float* __restrict__ gmax2s,
+                                                          const float* __restrict__ zt2s, int noskip, double* __restrict__ partB,
                                                           float* __restrict__ estO, int* __restrict__ plist, int* __restrict__ rcount) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { rcount[0] = 0; rcount[1] = 0; }   // this pass's route list (k_route_decide follows)
   const int item = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -848,16 +925,20 @@ __global__ __launch_bounds__(256) void k_offdiag_worklist(int L, int Mp, int P, 
   mm_decode_pair_o(p, L, a, a2);
   bool work = true, dense = true;
   if (!force_worst) {
-    if (mm_collapse_bound2(amax[item], zmax2[a2]) <= MM_INSIDE_BOUND2) {
+    const bool ic = mm_item_collapsed(amaxc[item]);
+    if (mm_collapse_bound2(amax[item], zmax2[a2]) <= MM_INSIDE_BOUND2 && !(noskip && ic)) {
       work = false;                                           // every |b_ij| inside the collapsed range
-    } else if (mm_item_collapsed(amaxc[item])) {
-      // row groups (k_qred_f32_mfma's need / wave_inside): a collapsed group inside by its own bound has no tile to visit
+    } else if (ic) {
+      // row groups (k_qred_f32_mfma's need / wave_inside): a collapsed group inside by its own bound has no tile to visit -- the
+      // lengthscale-scaled bound where gmax2s / zt2s are given, else the Euclidean one; noskip: every such item is listed
       const int ng = Mp / MM_GROUP_ROWS;
       const size_t grp0 = (size_t)item * ng;
+      const bool scaled = gmax2s != nullptr && zt2s != nullptr;
+      const float zsmax = (scaled && !noskip) ? mm_wave_max_tiles(zt2s + (size_t)a2 * (Mp >> 5), Mp >> 5, lane) : 0.0f;
       bool need = false, dn = false;
       for (int g = lane; g < ng; g += 64) {
         const bool coll = gflag[grp0 + g] != 0;
-        need = need || !(coll && mm_collapse_bound2(__float_as_uint(gmax2[grp0 + g]), zmax2[a2]) <= MM_INSIDE_BOUND2);
+        need = need || noskip || !(coll && mm_group_inside(gmax2, scaled ? gmax2s : nullptr, grp0 + g, zmax2[a2], zsmax));
         dn = dn || !coll;
       }
       work = __any(need);
@@ -886,6 +967,8 @@ __global__ __launch_bounds__(64 * MM_F32P_WAVES, 1) void k_qred_f32_mfma_persist
                                                                                const float* __restrict__ gmax2,
                                                                                const double* __restrict__ zmax2,
                                                                                const float* __restrict__ zt2,
+                                                                               const float* __restrict__ gmax2s,
+                                                                               const float* __restrict__ zt2s, int noskip,
                                                                                const float* __restrict__ rowO,
                                                                                const float* __restrict__ colO,
                                                                                double* __restrict__ partB, float* __restrict__ estO,
@@ -956,8 +1039,8 @@ __global__ __launch_bounds__(64 * MM_F32P_WAVES, 1) void k_qred_f32_mfma_persist
       const int g = ngrp - 1 - gi;
       double sum;
       float estl;
-      mm_f32_wave_rows<1>(zlds, wlds, g * 64, b, lp, a2, Mp, d, Po, force_worst, icoll, grp0, amaxc, gflag, gmax2, zmax2, zt2, rowO,
-                          sum, estl);
+      mm_f32_wave_rows<1>(zlds, wlds, g * 64, b, lp, a2, Mp, d, Po, force_worst, icoll, grp0, amaxc, gflag, gmax2, zmax2, zt2, gmax2s,
+                          zt2s, noskip, rowO, sum, estl);
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) { sum += __shfl_down(sum, off, 64); estl += __shfl_down(estl, off, 64); }
       if (lane == 0) { red[g] = sum; redf[g] = estl; }
@@ -975,6 +1058,42 @@ __global__ __launch_bounds__(64 * MM_F32P_WAVES, 1) void k_qred_f32_mfma_persist
 
 extern "C" int mm_mfma_supported(int d) { return d >= 1 && d <= 32; }
 
+// Diagnostics of the bound-based skipping (include/gpflowpilco_mm.h).
+__global__ void k_worklist_len(const int* __restrict__ plist, int L, int32_t* __restrict__ out) {
+  int n = 0;
+  for (int c = 1; c < L; ++c) n += plist[4 + 2 * c] + plist[5 + 2 * c];
+  out[0] = n;
+}
+
+extern "C" int mm_offdiag_worklist_len(int L, int M, int d, int dtype, int B, int flags, const void* workspace, size_t workspace_bytes,
+                                       int32_t* out, void* stream) {
+  if (!workspace || !out || L <= 0 || M <= 0 || d <= 0 || d > MM_DMAX || B <= 0) return MM_E_ARG;
+  const MMWorkspaceLayout wl = mm_workspace_layout(B, L, M, d, dtype, flags);
+  if (workspace_bytes < wl.total) return MM_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(out, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (dtype != MM_F32 || wl.Po == 0 || d > 8 || wl.Mp > MM_F32P_MAX_MP) return 0;      // (no persistent sweep: no list)
+  hipLaunchKernelGGL(k_worklist_len, dim3(1), dim3(1), 0, s, (const int*)((const char*)workspace + wl.plist), L, out);
+  const hipError_t el = hipGetLastError();
+  return el == hipSuccess ? 0 : (int)el;
+}
+
+extern "C" int mm_offdiag_skip_bounds(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B, int flags,
+                                      const void* workspace, size_t workspace_bytes, float* zt2s_out, float* gmax2s_out, void* stream) {
+  if (!packed || !workspace || !zt2s_out || !gmax2s_out || L <= 0 || M <= 0 || d <= 0 || d > MM_DMAX || B <= 0) return MM_E_ARG;
+  if (dtype != MM_F32 || d > 8) return MM_E_DIM;
+  const MMModelLayout ml = mm_model_layout(L, M, d, dtype, 1);
+  const MMWorkspaceLayout wl = mm_workspace_layout(B, L, M, d, dtype, flags);
+  if (packed_bytes < ml.Cm || workspace_bytes < wl.total) return MM_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(zt2s_out, (const char*)packed + ml.zt2s, (size_t)L * (ml.Mp / 32) * 4, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && wl.Po > 0)
+    e = hipMemcpyAsync(gmax2s_out, (const char*)workspace + wl.gmax2s, (size_t)B * wl.Po * (wl.Mp / MM_GROUP_ROWS) * 4,
+                       hipMemcpyDeviceToDevice, s);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 int mm_mfma_num_slots(int Mp) { return (Mp + MM_PANEL_ROWS - 1) / MM_PANEL_ROWS; }
 
 int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
@@ -983,6 +1102,12 @@ int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, c
   const int force_worst = (flags & MM_FORCE_WORST_TIER) ? 1 : 0;
   const unsigned int* amax = (const unsigned int*)(ws + wl.amax);
   const double* zmax2 = mm_moment_deg(d) >= 4 ? (const double*)(packed + ml.zmax2) : nullptr;
+  // the skip bound's metric: lengthscale-scaled where the row groups exist (d <= 8), unless MM_ISTAGE_OLD_SKIP_BOUND asks for the
+  // Euclidean test at every site (null pointers); MM_ISTAGE_NO_BOUND_SKIP: no bound-based skipping
+  const bool scaled = zmax2 != nullptr && ml.nd8 == 1 && !(flags & MM_ISTAGE_OLD_SKIP_BOUND);
+  const float* gmax2s = scaled ? (const float*)(ws + wl.gmax2s) : nullptr;
+  const float* zt2s = scaled ? (const float*)(packed + ml.zt2s) : nullptr;
+  const int noskip = (flags & MM_ISTAGE_NO_BOUND_SKIP) ? 1 : 0;
   // the (h, m) parts of one latent in LDS when they fit beside a second workgroup (<= 64 KB): d <= 8 and M <= 2048
   const size_t zbytes = (size_t)wl.Mp * 32 * ml.nd8;
   const bool ldsz = ml.nd8 == 1 && zbytes <= 65536;
@@ -1008,7 +1133,7 @@ int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, c
     if (em != hipSuccess) return (int)em;
     hipLaunchKernelGGL(k_offdiag_worklist, dim3((nitem + 3) / 4), dim3(256), 0, stream, L, wl.Mp, wl.P, wl.Po, wl.NS, npanel, B,
                        force_worst, amax, (const unsigned int*)(ws + wl.amaxc), (const unsigned char*)(ws + wl.gflag),
-                       (const float*)(ws + wl.gmax2), zmax2, partB, estO, plist, (int*)(ws + wl.rcount));
+                       (const float*)(ws + wl.gmax2), zmax2, gmax2s, zt2s, noskip, partB, estO, plist, (int*)(ws + wl.rcount));
     const hipError_t el = hipGetLastError();
     if (el != hipSuccess) return (int)el;
     // (raise the dynamic-LDS limit and read the CU count once per device: the calls are slow)
@@ -1032,14 +1157,14 @@ int mm_launch_qred_mfma(const char* packed, const MMModelLayout& ml, char* ws, c
     hipLaunchKernelGGL(k_qred_f32_mfma_persist, dim3(nitem < ncu ? nitem : ncu), dim3(64 * MM_F32P_WAVES), shm, stream, Zs3, L, wl.Mp,
                        d, wl.P, wl.Po, wl.NS, npanel, B, force_worst, (const unsigned int*)(ws + wl.amaxc),
                        (const unsigned char*)(ws + wl.gflag), (const float*)(ws + wl.gmax2), zmax2, (const float*)(packed + ml.zt2),
-                       rowO, colO, partB, estO, plist);
+                       gmax2s, zt2s, noskip, rowO, colO, partB, estO, plist);
     const hipError_t ep = hipGetLastError();
     return ep == hipSuccess ? 0 : (int)ep;
   }
 #define MM_LAUNCH_ND(ND_, LZ_, SH_)                                                                          \
   hipLaunchKernelGGL((k_qred_f32_mfma<ND_, LZ_>), dim3(nwork), dim3(256), SH_, stream, Zs3, L, wl.Mp, d,    \
                      wl.P, wl.Po, wl.NS, npanel, ppw, nwork, force_worst, amax, (const unsigned int*)(ws + wl.amaxc), \
-                     (const unsigned char*)(ws + wl.gflag), (const float*)(ws + wl.gmax2), zmax2, (const float*)(packed + ml.zt2), rowO, colO, partB, estO, (int*)(ws + wl.rcount))
+                     (const unsigned char*)(ws + wl.gflag), (const float*)(ws + wl.gmax2), zmax2, (const float*)(packed + ml.zt2), gmax2s, zt2s, noskip, rowO, colO, partB, estO, (int*)(ws + wl.rcount))
   switch (ml.nd8) {
     case 1: if (ldsz) MM_LAUNCH_ND(1, true, zbytes); else MM_LAUNCH_ND(1, false, 0); break;
     case 2: MM_LAUNCH_ND(2, false, 0); break;

@@ -179,7 +179,8 @@ def moment_match(pm: PackedModel, mu: torch.Tensor, Sigma: torch.Tensor,
                  full_output_cov: bool = True, model_uncertainty: bool = True,
                  jitter: float = 0.0, force_generic: bool = False, extra_flags: int = 0):
   """(mu [B,d], Sigma [B,d,d]) -> f1 [B,L], Sff [B,L,L] | [B,L], Sigma^-1 Cov(x,f) [B,d,L].
-  ``extra_flags``: test / measurement bits of the C ABI (``MM_FORCE_ROUTE``, ``MM_NO_ROUTE``, ``MM_FORCE_WORST_TIER``)."""
+  ``extra_flags``: test / measurement bits of the C ABI (``MM_FORCE_ROUTE``, ``MM_NO_ROUTE``, ``MM_FORCE_WORST_TIER``; the
+  internal A/B bits of csrc/mm_common.h, e.g. ``_lib.MM_ISTAGE_OLD_SKIP_BOUND`` / ``MM_ISTAGE_NO_BOUND_SKIP``)."""
   B, mu, Sigma = _prep_state(pm, mu, Sigma)
   flags = make_flags(full_output_cov, model_uncertainty, force_generic) | int(extra_flags)
   f1 = torch.empty(B, pm.L, dtype=pm.dtype, device=pm.device)
@@ -263,6 +264,34 @@ def offdiag_routed(pm: PackedModel, B: int, flags: int) -> int:
                               ws.data_ptr(), ws.numel(), out.data_ptr(), _stream(pm.device))
   check(rc, "mm_offdiag_stats")
   return int(out[3])
+
+
+def offdiag_worklist_len(pm: PackedModel, B: int, flags: int) -> int:
+  """Items the last ``moment_match`` / ``Q_reduce_forward`` with this B and flags put on the persistent off-diagonal sweep's work
+  list: those with a tile to visit (``mm_offdiag_worklist_len``; float32 packs with d <= 8 and M <= 2048, else 0).  Synchronises."""
+  if pm.dtype != torch.float32 or pm.L < 2 or not (flags & MM_FULL_OUTPUT_COV):
+    return 0
+  ws = pm.workspace(B, flags, peek=True)
+  out = torch.zeros(1, dtype=torch.int32, device=pm.device)
+  rc = lib().mm_offdiag_worklist_len(pm.L, pm.M, pm.d, _dtype_code(pm.dtype), B, flags, ws.data_ptr(), ws.numel(),
+                                     out.data_ptr(), _stream(pm.device))
+  check(rc, "mm_offdiag_worklist_len")
+  return int(out[0])
+
+
+def offdiag_skip_bounds(pm: PackedModel, B: int, flags: int):
+  """(zt2s [L, Mp/32], gmax2s [B, P - L, Mp/64]) float32: the column and row factors of the lengthscale-scaled Cauchy-Schwarz
+  bound the float32 off-diagonal sweep skips tiles by, as the pack and the last ``q_forward`` / ``moment_match`` with this B and
+  flags left them (``mm_offdiag_skip_bounds``; float32 packs with d <= 8)."""
+  Mp = (pm.M + _lib.MM_M_ALIGN - 1) // _lib.MM_M_ALIGN * _lib.MM_M_ALIGN
+  Po = pm.L * (pm.L - 1) // 2 if (flags & MM_FULL_OUTPUT_COV) else 0
+  zt2s = torch.zeros(pm.L, Mp // 32, dtype=torch.float32, device=pm.device)
+  gmax2s = torch.zeros(B, Po, Mp // 64, dtype=torch.float32, device=pm.device)
+  ws = pm.workspace(B, flags, peek=True)
+  rc = lib().mm_offdiag_skip_bounds(pm.buf.data_ptr(), pm.nbytes, pm.L, pm.M, pm.d, _dtype_code(pm.dtype), B, flags,
+                                    ws.data_ptr(), ws.numel(), zt2s.data_ptr(), gmax2s.data_ptr(), _stream(pm.device))
+  check(rc, "mm_offdiag_skip_bounds")
+  return zt2s, gmax2s
 
 
 def route_estimates(pm: PackedModel, B: int, flags: int) -> torch.Tensor:

@@ -179,6 +179,20 @@ int mm_expected_cost(int N, int d, int dtype, const void* mean, const void* cov,
 int mm_offdiag_stats(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B, int flags,
                      const void* workspace, size_t workspace_bytes, int32_t* out, void* stream);
 
+/* Diagnostic: the number of (batch element, off-diagonal pair) items the last mm_moment_match / mm_Q_reduce_forward on this
+ * workspace put on the work list of the persistent f32 off-diagonal sweep (csrc/mm_mfma.hip: the items with a tile to visit; MM_F32
+ * packs with d <= 8 and M <= 2048, else 0).  out: device int32[1]. */
+int mm_offdiag_worklist_len(int L, int M, int d, int dtype, int B, int flags, const void* workspace, size_t workspace_bytes,
+                            int32_t* out, void* stream);
+
+/* Diagnostic: the two factors of the lengthscale-scaled bound by which the f32 off-diagonal sweep skips column tiles
+ * (csrc/mm_mfma.hip; MM_F32 packs with d <= 8, else MM_E_DIM), copied out device to device: zt2s_out [L][Mp/32] f32 from the pack
+ * (per 32-point tile of the packed order max_m sum_k (z_mk - zbar_k)^2 / lengthscale_k^2, rounded up; Mp = M rounded up to
+ * MM_M_ALIGN) and gmax2s_out [B][P-L][Mp/64] f32 from the last mm_q_forward / mm_moment_match on this workspace (per 64-row group
+ * max_i sum_k (A_ik lengthscale_a',k)^2, rounded up). */
+int mm_offdiag_skip_bounds(const void* packed, size_t packed_bytes, int L, int M, int d, int dtype, int B, int flags,
+                           const void* workspace, size_t workspace_bytes, float* zt2s_out, float* gmax2s_out, void* stream);
+
 /* Diagnostic of the f32 pack's accuracy contract (csrc/mm_route.hip): after mm_moment_match / mm_Q_reduce_forward (or the
  * backward) on an MM_F32 pack, out [B][P-L][2] f64 = per (batch element, off-diagonal pair) {the sweep's estimate of its own
  * rounding error, the scale it is compared with}: an item is re-reduced in f64 when est > MM_ROUTE_TOL (3e-4) x scale. */

@@ -7,7 +7,9 @@
   3. row-group collapse: the area of a dense item that stays collapsed when the predicate is taken per 64-row group (rows only,
      columns only, both), and the fraction of all row groups collapsed against the bound;
   4. Cauchy-Schwarz prefix skip: the screened wave tiles a collapsed group can skip from its own rows' norm and the column
-     tiles' norms alone, against what the screening product finds.
+     tiles' norms alone, against what the screening product finds; 4b: the same with the bound in the metric scaled by the
+     column latent's lengthscales beside the Euclidean one (steps 0 / 7 / 23, every 8th batch element): wave tiles visited,
+     items with a tile to visit, and the check that no skipped tile has max|b| > 1/4.
 
   python tools/pack_order_study.py"""
 import itertools, os, sys
@@ -174,3 +176,50 @@ for b in range(0, B, 32):
     skip_act = (bb <= 0.25) & inner[:, None]
     tot += inner.sum() * 62; cs += skip_cs.sum(); act += skip_act.sum()
 print("items swept", n_items, "collapsed-group wave tiles", tot, "skippable by block CS bound %.3f" % (cs / tot), "by the screening product %.3f" % (act / tot))
+
+# ---- 4b. the same skip with the bound in the lengthscale-scaled metric --------------------------------------------------------
+# |A_i . zc'_j| <= |A_i o l'| |zc'_j / l'| with l' the column latent's lengthscales: the column factor is the pack's sort key, so the
+# tile maxima are monotone and the prefix is exact.  The sweep's own logic (mm_mfma.hip) on the padded pack (Mp = 2048: 32 row
+# groups, 64 column tiles), the collapse decision unchanged (Euclidean): a collapsed group visits the tiles from the first to the
+# last one outside the bound (Euclidean: from the first one to the end).  Steps 0 / 7 / 23 of the bench's draws, every 8th element.
+Mp, NG, NT = 2048, 32, 64
+INS = float(np.float32(0.998) * np.float32(0.0625))      # MM_INSIDE_BOUND2
+def padded(v, n, k):    # max over groups of k consecutive entries, zero padded to n groups
+  w = np.zeros(n * k); w[:v.size] = v
+  return w.reshape(n, k).max(1)
+zbars = [Z[a].mean(0) for a in range(L)]
+zt_e = [padded((Zs[a] ** 2).sum(1), NT, 32) for a in range(L)]
+zt_s = [padded(((Zs[a] / ls[a]) ** 2).sum(1), NT, 32) for a in range(L)]
+print("step | wave tiles visited by collapsed groups: Euclidean -> scaled | of those visited now, found inside by the screening | "
+      "items with a tile to visit: Euclidean -> scaled (of items) | skipped tiles with max|b| > 1/4")
+for step in (0, 7, 23):
+  v_e = v_s = v_e_inside = bad = it_e = it_s = nit = 0
+  for b in range(0, B, 8):
+    mu, S = mu_all[step * B + b], S_all[step * B + b]
+    for (a, a2) in pairs:
+      nit += 1
+      La, Lb = ls[a] ** 2, ls[a2] ** 2
+      V = La * Lb / (La + Lb)
+      T = np.diag(V) @ np.linalg.solve(S + np.diag(V), S); T = 0.5 * (T + T.T)
+      G = T / La[:, None] / Lb[None, :]
+      zm2 = zt_e[a2].max()
+      t0 = G.T @ (mu - zbars[a])
+      rec = float(t0 @ t0) * zm2 <= 256.0                # MM_RECENTRE_CMAX: else the rows stay at mu and nothing collapses
+      A = (Zs[a] if rec else Zs[a] + zbars[a] - mu) @ G
+      an = (A * A).sum(1)
+      if rec and an.max() * zm2 <= INS: continue         # wholly inside: no sweep
+      ag = padded(an, NG, 64); ags = padded(((A * ls[a2]) ** 2).sum(1), NG, 64)
+      coll = (ag * zm2 <= 0.25) & rec
+      if not coll.any(): it_e += 1; it_s += 1; continue  # dense groups only
+      bb = np.zeros((Mp, Mp)); bb[:M, :M] = np.abs(A @ Zs[a2].T)
+      bt = bb.reshape(NG, 64, NT, 32).max(axis=(1, 3))
+      need_e = need_s = bool((~coll).any())
+      for g in np.nonzero(coll)[0]:
+        oe = ag[g] * zt_e[a2] > INS; os_ = ags[g] * zt_s[a2] > INS
+        vis_e = np.zeros(NT, bool); vis_s = np.zeros(NT, bool)
+        if oe.any(): vis_e[int(np.argmax(oe)) & ~1:] = True; need_e = True
+        if os_.any(): vis_s[int(np.argmax(os_)) & ~1:((NT - 1 - int(np.argmax(os_[::-1]))) + 2) & ~1] = True; need_s = True
+        v_e += int(vis_e.sum()); v_s += int(vis_s.sum()); v_e_inside += int((vis_e & (bt[g] <= 0.25)).sum())
+        bad += int((~vis_s & (bt[g] > 0.25)).sum()) + int((~vis_e & (bt[g] > 0.25)).sum())
+      it_e += need_e; it_s += need_s
+  print(f"{step:4d} | {v_e} -> {v_s} ({100.0 * v_s / max(v_e, 1):.1f} %) | {v_e_inside} | {it_e} -> {it_s} (of {nit}) | {bad}")
