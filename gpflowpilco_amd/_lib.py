@@ -71,98 +71,16 @@ SIGNATURES = {
     "mm_route_estimates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mm_compose_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "mm_rollout_composed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                      C.c_void_p, C.c_void_p]),
     "mm_compose_nd_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "mm_rollout_composed_nd": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                         C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.c_void_p]),
     "mm_compose_tape_bytes": (C.c_size_t, [C.c_int] * 6),
-    "mm_rollout_composed_taped": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_void_p]),
     "mm_compose_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "mm_policy_grad_bytes": (C.c_size_t, [C.c_int] * 3),
-    "mm_rollout_composed_backward": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                               C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                               C.c_void_p, C.c_void_p]),
-    "mm_rollout_composed_backward_seeded": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                                      C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                      C.c_void_p, C.c_void_p]),
     "mm_compose_tape_bytes_nd": (C.c_size_t, [C.c_int] * 7),
-    "mm_rollout_composed_taped_nd": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                               C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                               C.c_void_p, C.c_void_p]),
     "mm_compose_backward_workspace_bytes_nd": (C.c_size_t, [C.c_int] * 6),
     "mm_policy_grad_bytes_nd": (C.c_size_t, [C.c_int] * 4),
-    "mm_rollout_composed_backward_nd": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                                  C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                                  C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                                  C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_size_t, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                  C.c_void_p, C.c_void_p]),
-    "mm_rollout_composed_backward_nd_seeded": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                                         C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                                         C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                                         C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                         C.c_void_p, C.c_void_p]),
     "mm_compose_nd_mixed_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
-    "mm_rollout_composed_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                               C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm_compose_tape_bytes_nd_mixed": (C.c_size_t, [C.c_int] * 8),
-    "mm_rollout_composed_taped_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                                     C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                                     C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm_compose_backward_workspace_bytes_nd_mixed": (C.c_size_t, [C.c_int] * 7),
-    "mm_rollout_composed_backward_nd_mixed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                                        C.c_void_p, C.c_size_t, C.c_int, C.c_int,
-                                                        C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                                        C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm_bwd_f32_supported": (C.c_int, [C.c_int]),
     "mm_backward_pair_aggregates_bytes": (C.c_size_t, [C.c_int] * 5),
     "mm_backward_pair_aggregates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -254,6 +172,31 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
+
+
+def _composed_rollout_signatures():
+  """The eleven ``mm_rollout_composed*`` entries, from the pieces their argument lists share: prefix, head constants, target and
+  precision, the role's own arguments, and -- the ``_nd_mixed`` entries -- the mixing."""
+  P, Z, I, D = C.c_void_p, C.c_size_t, C.c_int, C.c_double
+  prefix = [P, Z, I, I, I,  P, Z, I, I,  I, I, I, D, I, I, C.POINTER(C.c_int32)]   # drift pack; policy pack; dtype B H dt nx na active
+  heads = {"": [D, D], "_nd": [I, C.POINTER(D), C.POINTER(D)]}                     # scale, shift | nu, scale[nu], shift[nu]
+  buffers = lambda n: [P, Z] * n + [P, P]                                          # n (pointer, bytes) pairs; status, stream
+  roles = {"": [P] * 5 + buffers(3),                          # mx Sxx cost traj_mu traj_S; drift / policy / compose workspaces
+           "_taped": [P] * 3 + buffers(3),                    # mx Sxx cost; drift / policy workspaces, tape
+           "_backward": [P, Z, P] + [P] * 3 + buffers(2),     # tape, g_cost; g_policy g_mx g_Sxx; drift / sweep workspaces
+           "_backward_seeded": [P, Z, P, P, P] + [P] * 3 + buffers(2)}                 # ... g_cost, g_xm, g_xS; ...
+  sigs = {}
+  for role, args in roles.items():
+    stem, seeded, _ = role.partition("_seeded")
+    for nd, head in heads.items():
+      sigs[f"mm_rollout_composed{stem}{nd}{seeded}"] = (I, prefix + head + [P, P] + args)
+  for role, mixing in (("", [P, P]), ("_taped", [P, P]), ("_backward", [P])):        # mix_W, mix_c | mix_W: the one sweep is seeded
+    args = roles["_backward_seeded" if role == "_backward" else role]
+    sigs[f"mm_rollout_composed{role}_nd_mixed"] = (I, prefix + heads["_nd"] + [P, P] + args + mixing)
+  return sigs
+
+
+SIGNATURES.update(_composed_rollout_signatures())
 
 _lib = None
 

@@ -417,118 +417,80 @@ def moment_match_torch(mu, Sigma, Z, ls, var, beta, C=None, mean_c=None, full_ou
   return f1, Sff, cross
 
 
+def _taped_composed_rollout(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
+  """The forward of the two autograd functions below: pack the policy from its packed coordinates, run the taped rollout of
+  ``roll``'s family (``roll.uses_nd``: the ``_nd`` / ``_nd_mixed`` entries), keep what the backward needs on ``ctx``.
+  -> (cost [H, B], tape)."""
+  f64 = torch.float64
+  det = lambda t: t.detach().to(f64)
+  pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
+  taped = roll.taped_nd if roll.uses_nd else roll.taped
+  m_H, S_H, cost, tape = taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
+  ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
+  ctx.save_for_backward(ls)
+  ctx.need_state = mx.requires_grad or Sxx.requires_grad
+  ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+  return cost, tape
+
+
+def _composed_rollout_gradients(ctx, g_cost, seeds=None):
+  """The backward of the two autograd functions below: one reverse sweep (``seeds = (g_xm [H,B,nx], g_xS [H,B,nx,nx])``: the seeded
+  one), its packed gradient summed over the batch and split per input."""
+  (ls,) = ctx.saved_tensors
+  sweep = ctx.roll.backward_nd if ctx.roll.uses_nd else ctx.roll.backward
+  g_pol, g_m, g_S = sweep(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
+                          want_state_grad=ctx.need_state, g_traj=seeds)
+  nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
+  g = g_pol.sum(0).reshape(nu, -1)                                                        # [nu, M d + M + d + 2]
+  zs, lss, vs, bs, ms = ctx.shapes
+  gZ = g[:, :M * d].reshape(zs)
+  gbeta = g[:, M * d:M * d + M].reshape(bs)
+  gls = (2.0 * ls.detach().reshape(nu, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)   # d/d ls = 2 ls d/d ls^2
+  gvar = g[:, M * d + M + d].reshape(vs)
+  gmean = g[:, M * d + M + d + 1].reshape(ms)
+  return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
+
+
 class ComposedRolloutFunction(torch.autograd.Function):
   """The whole moment-matched policy rollout as ONE differentiable op: forward = ``mm_rollout_composed_taped``,
   backward = ``mm_rollout_composed_backward`` (csrc/mm_compose_bwd.hip) -- the native counterpart of differentiating
-  ``policy_loss_closure`` with a gradient tape (gpflow_pilco/utils/optimizers.py:51-56, loops/pilco.py:192-220).
+  ``policy_loss_closure`` with a gradient tape (gpflow_pilco/utils/optimizers.py:51-56, loops/pilco.py:192-220).  A rollout of the
+  ``_nd`` family (``roll.uses_nd``: 2 to 4 actions, or a coregionalised drift) takes ``mm_rollout_composed_taped_nd`` /
+  ``mm_rollout_composed_backward_nd`` (csrc/mm_compose_bwd_nd.hip) or their ``_nd_mixed`` forms.
 
-  Inputs: the initial state (mx [B,nx], Sxx [B,nx,nx]) and the policy in PACKED coordinates -- Z [1,M,d],
-  lengthscales [1,d], variance [1], beta = Kuu^-1 u [1,M], mean_c [1] -- which the caller computes from the trainable
+  Inputs: the initial state (mx [B,nx], Sxx [B,nx,nx]) and the policy in PACKED coordinates with a leading latent axis -- Z [nu,M,d],
+  lengthscales [nu,d], variance [nu], beta = Kuu^-1 u [nu,M], mean_c [nu] -- which the caller computes from the trainable
   parameters with ordinary differentiable torch ops (``SVGP.precompute``: a 30 x 30 Cholesky), so autograd carries the
-  gradient the last step to (q_mu, Z, lengthscales, variance).  The drift is frozen.  Output: cost [B, H]."""
+  gradient the last step to (q_mu, Z, lengthscales, variance); ``g_policy`` comes back per latent, d/d lengthscales =
+  2 ls . d/d ls^2.  The drift and the head's scale / shift are constants.  Output: cost [B, H]."""
 
   @staticmethod
   def forward(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
-    f64 = torch.float64
-    det = lambda t: t.detach().to(f64)
-    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-    m_H, S_H, cost, tape = roll.taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
-    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
-    ctx.save_for_backward(ls)
-    ctx.need_state = mx.requires_grad or Sxx.requires_grad
-    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+    cost, _ = _taped_composed_rollout(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt)
     return cost.T.contiguous()
 
   @staticmethod
   def backward(ctx, g_cost):
-    (ls,) = ctx.saved_tensors
-    g_pol, g_m, g_S = ctx.roll.backward(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
-                                        want_state_grad=ctx.need_state)
-    M, d = ctx.pol.M, ctx.pol.d
-    g = g_pol.sum(0)
-    zs, lss, vs, bs, ms = ctx.shapes
-    gZ = g[:M * d].reshape(zs)
-    gbeta = g[M * d:M * d + M].reshape(bs)
-    gls = (2.0 * ls.detach().reshape(-1) * g[M * d + M:M * d + M + d]).reshape(lss)        # d/d ls = 2 ls d/d ls^2
-    gvar = g[M * d + M + d].reshape(vs)
-    gmean = g[M * d + M + d + 1].reshape(ms)
-    return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
-
-
-class ComposedRolloutNDFunction(torch.autograd.Function):
-  """``ComposedRolloutFunction`` for a policy with nu = 1..4 actions: forward = ``mm_rollout_composed_taped_nd``, backward =
-  ``mm_rollout_composed_backward_nd`` (csrc/mm_compose_bwd_nd.hip).
-
-  The packed coordinates carry a leading latent axis -- Z [nu,M,d], lengthscales [nu,d], variance [nu], beta [nu,M],
-  mean_c [nu] -- and ``g_policy`` comes back per latent; d/d lengthscales = 2 ls . d/d ls^2 per latent.  The drift and the
-  head's scale / shift are constants.  Output: cost [B, H]."""
-
-  @staticmethod
-  def forward(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
-    f64 = torch.float64
-    det = lambda t: t.detach().to(f64)
-    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-    m_H, S_H, cost, tape = roll.taped_nd(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
-    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
-    ctx.save_for_backward(ls)
-    ctx.need_state = mx.requires_grad or Sxx.requires_grad
-    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
-    return cost.T.contiguous()
-
-  @staticmethod
-  def backward(ctx, g_cost):
-    (ls,) = ctx.saved_tensors
-    g_pol, g_m, g_S = ctx.roll.backward_nd(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
-                                           want_state_grad=ctx.need_state)
-    nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
-    g = g_pol.sum(0)                                                                        # [nu, M d + M + d + 2]
-    zs, lss, vs, bs, ms = ctx.shapes
-    gZ = g[:, :M * d].reshape(zs)
-    gbeta = g[:, M * d:M * d + M].reshape(bs)
-    gls = (2.0 * ls.detach().reshape(nu, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)   # d/d ls = 2 ls d/d ls^2
-    gvar = g[:, M * d + M + d].reshape(vs)
-    gmean = g[:, M * d + M + d + 1].reshape(ms)
-    return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
+    return _composed_rollout_gradients(ctx, g_cost)
 
 
 class ComposedTrajectoryFunction(torch.autograd.Function):
-  """The moment-matched policy rollout with its TRAJECTORY as a differentiable output, for one action and for several: the taped
-  forward of ``ComposedRolloutFunction`` / ``ComposedRolloutNDFunction`` (by ``roll.uses_nd``), and the same reverse sweep seeded per step
-  with d loss / d (m_t, S_t) (``mm_rollout_composed_backward_seeded`` / ``_nd_seeded``).  Any torch objective of the states then
+  """The moment-matched policy rollout with its TRAJECTORY as a differentiable output, for every family: the taped forward of
+  ``ComposedRolloutFunction``, and the same reverse sweep seeded per step with d loss / d (m_t, S_t)
+  (``mm_rollout_composed_backward_seeded`` / ``_nd_seeded``).  Any torch objective of the states then
   sits on the native policy -> drift -> Euler chain, and the gradient of its own parameters comes from that torch part.
 
-  Inputs: those of ``ComposedRolloutFunction`` (a leading latent axis on the packed coordinates for nu > 1).  Outputs:
+  Inputs: those of ``ComposedRolloutFunction``.  Outputs:
   (cost [B, H] of the rollout's built-in Gaussian cost, xm [B, H, nx], xS [B, H, nx, nx]) -- the states x_1 .. x_H read off the
   tape.  Only the symmetric part of a seed on the symmetric S_t is determined: the backward uses (G + G^T) / 2."""
 
   @staticmethod
   def forward(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
-    f64 = torch.float64
-    det = lambda t: t.detach().to(f64)
-    pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-    taped = roll.taped_nd if roll.uses_nd else roll.taped
-    m_H, S_H, cost, tape = taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
-    ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
-    ctx.save_for_backward(ls)
-    ctx.need_state = mx.requires_grad or Sxx.requires_grad
-    ctx.shapes = (Z.shape, ls.shape, var.shape, beta.shape, mean_c.shape)
+    cost, tape = _taped_composed_rollout(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt)
     xm, xS = roll.tape_states(tape, ctx.B, ctx.H)
     return cost.T.contiguous(), xm.transpose(0, 1).contiguous(), xS.transpose(0, 1).contiguous()
 
   @staticmethod
   def backward(ctx, g_cost, g_xm, g_xS):
-    (ls,) = ctx.saved_tensors
     g_xS = 0.5 * (g_xS + g_xS.transpose(-1, -2))
-    seeds = (g_xm.transpose(0, 1).contiguous(), g_xS.transpose(0, 1).contiguous())
-    sweep = ctx.roll.backward_nd if ctx.roll.uses_nd else ctx.roll.backward
-    g_pol, g_m, g_S = sweep(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
-                            want_state_grad=ctx.need_state, g_traj=seeds)
-    nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
-    g = g_pol.sum(0).reshape(nu, -1)                                                        # [nu, M d + M + d + 2]
-    zs, lss, vs, bs, ms = ctx.shapes
-    gZ = g[:, :M * d].reshape(zs)
-    gbeta = g[:, M * d:M * d + M].reshape(bs)
-    gls = (2.0 * ls.detach().reshape(nu, d) * g[:, M * d + M:M * d + M + d]).reshape(lss)   # d/d ls = 2 ls d/d ls^2
-    gvar = g[:, M * d + M + d].reshape(vs)
-    gmean = g[:, M * d + M + d + 1].reshape(ms)
-    return g_m, g_S, gZ, gls, gvar, gbeta, gmean, None, None, None
+    return _composed_rollout_gradients(ctx, g_cost, (g_xm.transpose(0, 1).contiguous(), g_xS.transpose(0, 1).contiguous()))

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 from typing import Callable, Optional, Sequence
 
+import functools
 import warnings
 
 import numpy as np
@@ -168,6 +169,43 @@ def _pathwise_mixing_obstacle(drift, paths, grad: bool) -> Optional[str]:
   return None
 
 
+def _objective_uses_trajectory(objective: Callable, native_objective: bool) -> bool:
+  """The objective is evaluated in torch on the native rollout's trajectory (``native_objective``): one that is no
+  ``GaussianObjective``, or one whose target / precision require a gradient while gradients are being taken."""
+  from .cost import GaussianObjective
+  if not native_objective:
+    return False
+  if not isinstance(objective, GaussianObjective):
+    return True
+  return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                         for t in (objective.target, objective.precis))
+
+
+def _constants_grad_obstacle(bj, objective: Callable, native_objective: bool, state: str) -> Optional[str]:
+  """The native reverse sweeps return gradients for the policy SVGP's parameters and the initial state(s) only: the head's Scale /
+  Shift and the objective's target / precision enter as constants (float() / raw pointers).  -> the reason one of them that
+  requires a gradient keeps the sweep out, or None.  ``state``: how the closure names what the sweep does cover ("initial state" /
+  "initial states").  With ``native_objective`` the objective's own parameters are differentiated by the torch part -- and without
+  it only a ``GaussianObjective`` gets this far (``_native_parts``), so .target / .precis exist; an objective of the caller's own
+  has neither and is not asked for them."""
+  outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift}
+  if not native_objective:
+    outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
+  for name, t in outside.items():
+    if isinstance(t, torch.Tensor) and t.requires_grad:
+      return f"{name} requires a gradient (the native reverse sweep covers the policy SVGP's parameters and the {state})"
+  return None
+
+
+def _warn_fallback(warned: list, native: Optional[bool], closure: str, reason: str):
+  """The torch composition is about to run on GPU tensors (60 x slower than the native path at cartpole sizes): say so, once per
+  closure (``warned``: its record).  Bind it with ``functools.partial`` -- no frame of its own, so the warning points where the
+  closures' own helpers always pointed."""
+  if native is not False and not warned:
+    warned.append(reason)
+    warnings.warn(f"{closure}: falling back to the torch composition of the rollout ({reason})", RuntimeWarning, stacklevel=3)
+
+
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
                        why: Optional[list] = None, native_actions: int = 1, native_no_encoder: bool = False,
                        native_objective: bool = False, native_coregionalized: bool = False):
@@ -182,7 +220,7 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
 
   ``native_actions``: the largest number of actions ``with_grad`` may differentiate natively.  The default 1 keeps a policy with
   several actions forward only (``grad_obstacle`` names ``nu > 1``); with ``native_actions >= nu`` its gradient runs through the
-  multi-action tape and reverse sweep (csrc/mm_compose_bwd_nd.hip, ``autodiff.ComposedRolloutNDFunction``) where
+  multi-action tape and reverse sweep (csrc/mm_compose_bwd_nd.hip, ``autodiff.ComposedRolloutFunction``) where
   ``ComposedRollout.backward_nd_refusal`` has no objection.
 
   ``native_no_encoder``: take a system with ``encoder=None`` (or a ``TrigonometricEncoder`` without active dims) too: the native
@@ -196,10 +234,9 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
 
   ``native_coregionalized``: take a drift with a ``LinearCoregionalization`` kernel of Lg <= nx latents too: its mixing f = W g + c
   runs on the device after every drift match (csrc/mm_mix.h) and the rollout -- one action included -- goes through the
-  ``_nd_mixed`` entries, forward and gradient (``ComposedRolloutNDFunction`` / ``ComposedTrajectoryFunction``).  W and the Constant
+  ``_nd_mixed`` entries, forward and gradient (``ComposedRolloutFunction`` / ``ComposedTrajectoryFunction``).  W and the Constant
   mean are constants of the frozen drift, re-read when they change in place."""
   from . import ops
-  from .cost import GaussianObjective
   parts = _native_parts(system, objective, why, moment_solver=True, no_encoder=bool(native_no_encoder),
                         any_objective=bool(native_objective), coregionalized=bool(native_coregionalized))
   if parts is None:
@@ -208,7 +245,6 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
   mixing = _drift_mixing(drift)
   max_native = int(native_actions)
   cache = {}
-  gaussian = isinstance(objective, GaussianObjective)
   zero_cost = {}
 
   def cost_constants(mx, zero):
@@ -222,13 +258,7 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     return zero_cost[key]
 
   def uses_trajectory(mx=None) -> bool:
-    """The objective is evaluated in torch on the native trajectory (``native_objective``)."""
-    if not native_objective:
-      return False
-    if not gaussian:
-      return True
-    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                           for t in (objective.target, objective.precis))
+    return _objective_uses_trajectory(objective, native_objective)
 
   def current_roll(mx: torch.Tensor, fresh_policy: bool = True, zero: bool = False):
     # (fresh_policy=False: the caller brings its own pack of the policy's current parameters -- the differentiable
@@ -279,7 +309,7 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
     the taped native rollout, backward = the native reverse sweep (autodiff.ComposedRolloutFunction); the policy enters
     in packed coordinates computed from its parameters by differentiable torch ops (a 30 x 30 precompute).  The tape and
     the reverse sweep are float64; a float32 state is cast up on the way in and the loss back down (autograd carries both)."""
-    from .autodiff import ComposedRolloutFunction, ComposedRolloutNDFunction, ComposedTrajectoryFunction
+    from .autodiff import ComposedRolloutFunction, ComposedTrajectoryFunction
     out_dtype = mx.dtype
     if mx.dtype != torch.float64:
       mx, Sxx = mx.double(), Sxx.double()
@@ -292,9 +322,8 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       # the objective in torch on the H returned states; the rollout's own (zero-precision) cost is not part of the loss
       _, xm, xS = ComposedTrajectoryFunction.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
       return objective_of_trajectory(xm, xS).to(out_dtype)
-    # (several actions: native_actions >= nu; a coregionalised drift takes the _nd family with one action too)
-    fn = ComposedRolloutNDFunction if roll.uses_nd else ComposedRolloutFunction
-    cost = fn.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
+    # (several actions: native_actions >= nu; a coregionalised drift takes the _nd family with one action too: roll.uses_nd)
+    cost = ComposedRolloutFunction.apply(mx, Sxx, Zp, lsp, varp, betap, mcp, roll, num_steps, dt)
     return cost.sum(1).to(out_dtype)
 
   def run_from_parameters(mx: torch.Tensor, Sxx: torch.Tensor):
@@ -316,14 +345,9 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
               "reverse sweep are one-action)")
     if nu > max(1, max_native):
       return f"the policy has nu = {nu} actions (nu > 1) and native_actions = {max_native}"
-    # the native reverse sweep returns gradients for the policy SVGP's parameters and the initial state only: the head's
-    # Scale / Shift and the objective's target / precision enter as constants (float() / raw pointers)
-    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift}
-    if not native_objective:                  # (with it, the objective's own parameters are differentiated by the torch part)
-      outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
-    for name, t in outside.items():
-      if isinstance(t, torch.Tensor) and t.requires_grad:
-        return f"{name} requires a gradient (the native reverse sweep covers the policy SVGP's parameters and the initial state)"
+    obstacle = _constants_grad_obstacle(bj, objective, native_objective, "initial state")
+    if obstacle is not None:
+      return obstacle
     if any(t.requires_grad for t in drift._parameters()) or (mixing is not None and drift.kernel.W.requires_grad):
       return "the drift is being trained (the native reverse sweep takes a frozen drift)"
     mx64 = mx if mx.dtype == torch.float64 else torch.empty(mx.shape, dtype=torch.float64, device=mx.device)
@@ -362,7 +386,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
 
   ``native_actions``: the largest number of actions whose GRADIENT may run natively (a named parameter, not a solver option).
   The default 1 is the routing described above.  With ``native_actions >= nu`` a gradient of the policy SVGP's parameters and / or
-  the initial state of a policy with 2 to 4 actions runs as one differentiable op too (``autodiff.ComposedRolloutNDFunction``: the
+  the initial state of a policy with 2 to 4 actions runs as one differentiable op too (``autodiff.ComposedRolloutFunction``: the
   multi-action tape and reverse sweep, csrc/mm_compose_bwd_nd.hip) -- frozen drift, constant head and objective, float64 tape
   (a float32 state is cast up), inside the sweep's LDS bound; every other case falls back once and names its reason.
 
@@ -413,14 +437,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       x = moment_matching(x, encoder).y
     return loss + objective(x=x, t=t)
 
-  warned = []
-
-  def _fallback(reason):
-    """The torch composition is about to run on GPU tensors (60 x slower than the native path at cartpole sizes): say so, once."""
-    if native is not False and not warned:
-      warned.append(reason)
-      warnings.warn(f"policy_loss_closure: falling back to the torch composition of the rollout ({reason})", RuntimeWarning,
-                    stacklevel=3)
+  _fallback = functools.partial(_warn_fallback, [], native, "policy_loss_closure")
 
   def _use_native(mx, Sxx):
     if fast is None and mx.is_cuda:
@@ -620,7 +637,6 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   kernels evaluate a SquaredExponential policy; its torch composition is ``SVGP.predict_mean`` with the family's Gram matrix."""
   from . import ops
   from .components import TrigonometricEncoder
-  from .cost import GaussianObjective
   from .linalg import index_tensor
   from .models import LinearCoregionalization
   from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction, PolicyTrajectoryFunction
@@ -633,7 +649,6 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
                                                      no_encoder=bool(native_no_encoder),
                                                      any_objective=bool(native_objective),
                                                      coregionalized=bool(native_coregionalized))
-  gaussian = isinstance(objective, GaussianObjective)
   if native is True and parts is None:
     raise ValueError(f"native=True: {why_not[0] if why_not else 'the system is not the shape the native rollout implements'}")
   max_native = int(native_actions)
@@ -641,13 +656,7 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   if native is True and parts[1].num_latent_gps > max(1, max_native):
     raise ValueError("native=True: the native pathwise rollout is one-action" if max_native <= 1 else
                      f"native=True: the policy has {parts[1].num_latent_gps} actions, native_actions={max_native}")
-  warned = []
-
-  def _fallback(reason):
-    if native is not False and not warned:
-      warned.append(reason)
-      warnings.warn(f"pathwise_policy_loss_closure: falling back to the torch composition of the rollout ({reason})",
-                    RuntimeWarning, stacklevel=3)
+  _fallback = functools.partial(_warn_fallback, [], native, "pathwise_policy_loss_closure")
 
   def _torch_loss(x0, pth):
     times = dt * np.arange(1, 1 + H, dtype=np.float64)
@@ -671,15 +680,6 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     if key not in samplers:
       samplers[key] = PathSampler(drift, x0.shape[0], num_bases, dtype=x0.dtype, device=x0.device)
     return samplers[key].draw(generator=generator)
-
-  def _uses_trajectory() -> bool:
-    """The objective is evaluated in torch on the native rollout's states (``native_objective``)."""
-    if not native_objective:
-      return False
-    if not gaussian:
-      return True
-    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                           for t in (objective.target, objective.precis))
 
   def _encode(xs):
     """``system.encoder(xs)``.  A plain ``TrigonometricEncoder`` is evaluated by its own transform on columns selected with cached
@@ -731,24 +731,17 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     elif nd > 8 or pol_M > 256:
       _fallback(f"drift inputs of dimension nx + na + nu = {nd} > 8 or a policy of more than 256 centres ({pol_M})")
       return _torch_loss(x0, pth)
-    outside = {"the policy head's Scale.scale": bj[0].scale, "the policy head's Shift.shift": bj[1].shift}
-    # (with native_objective the objective's own parameters are differentiated by the torch part.  Without it ``parts`` is only
-    # non-None for a GaussianObjective -- ``_native_parts`` refused every other one above -- so .target / .precis exist here; an
-    # objective of the caller's own has neither and must not be asked for them)
-    if not native_objective:
-      outside.update({"objective.target": objective.target, "objective.precis": objective.precis})
-    traj = _uses_trajectory()
+    traj = _objective_uses_trajectory(objective, native_objective)
     grad = torch.is_grad_enabled()
     if isinstance(drift.kernel, LinearCoregionalization):      # (native_coregionalized: _native_parts refused it otherwise)
       obstacle = _pathwise_mixing_obstacle(drift, pth, grad)
       if obstacle is not None:
         _fallback(obstacle)
         return _torch_loss(x0, pth)
-    if grad:
-      for name, t in outside.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-          _fallback(f"{name} requires a gradient (the native reverse sweep covers the policy SVGP's parameters and the initial states)")
-          return _torch_loss(x0, pth)
+    obstacle = _constants_grad_obstacle(bj, objective, native_objective, "initial states") if grad else None
+    if obstacle is not None:
+      _fallback(obstacle)
+      return _torch_loss(x0, pth)
     scale, shift = head_constants()
     pol_pack = pm_.packed(torch.float64, False, x0.device)
     # (the trajectory route: a zero built-in cost, its output ignored)

@@ -8,7 +8,7 @@ ROCm device.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -399,6 +399,38 @@ class GraphedRollout:
     return (self.mu, self.S, self.tmu, self.tS) if self.tmu is not None else (self.mu, self.S)
 
 
+class _ComposedFamily(NamedTuple):
+  """One family of native composed-rollout entries (include/gpflowpilco_mm.h): its four roles, its three size queries, and what
+  sets its argument lists apart from the other families'."""
+  name: str
+  forward: str
+  taped: str
+  backward: str
+  seeded: str               # the reverse sweep that takes seeds on the taped states after g_cost
+  compose_ws: str           # size queries: all take (B[, H], nx, na, the family's extra dims, ...)
+  tape_bytes: str
+  backward_ws: str
+  head_arrays: bool         # head constants: nu and two arrays of nu doubles (else two doubles by value)
+  mix: bool                 # mix_W, mix_c trail the forward and the taped entry, mix_W the sweep -- which is seeded only
+  latent_axis: bool         # g_policy is [B, nu, npar] and backward_ws also takes the policy's M (else [B, npar])
+  plain: str                # the family without mixing: errors name its entries, and the tape's slots are its compose workspaces
+
+
+_COMPOSED = {
+    "one": _ComposedFamily("one", "mm_rollout_composed", "mm_rollout_composed_taped", "mm_rollout_composed_backward",
+                           "mm_rollout_composed_backward_seeded", "mm_compose_workspace_bytes", "mm_compose_tape_bytes",
+                           "mm_compose_backward_workspace_bytes", head_arrays=False, mix=False, latent_axis=False, plain="one"),
+    "nd": _ComposedFamily("nd", "mm_rollout_composed_nd", "mm_rollout_composed_taped_nd", "mm_rollout_composed_backward_nd",
+                          "mm_rollout_composed_backward_nd_seeded", "mm_compose_nd_workspace_bytes", "mm_compose_tape_bytes_nd",
+                          "mm_compose_backward_workspace_bytes_nd", head_arrays=True, mix=False, latent_axis=True, plain="nd"),
+    "nd_mixed": _ComposedFamily("nd_mixed", "mm_rollout_composed_nd_mixed", "mm_rollout_composed_taped_nd_mixed",
+                                "mm_rollout_composed_backward_nd_mixed", "mm_rollout_composed_backward_nd_mixed",
+                                "mm_compose_nd_mixed_workspace_bytes", "mm_compose_tape_bytes_nd_mixed",
+                                "mm_compose_backward_workspace_bytes_nd_mixed", head_arrays=True, mix=True, latent_axis=True,
+                                plain="nd"),
+}
+
+
 class ComposedRollout:
   """The whole moment-matched policy rollout of the cartpole-shaped system on the device (``mm_rollout_composed``):
   TrigonometricEncoder -> policy (SVGP mean, Chain[Scale, Shift, NormalCDF]) -> drift SVGP with the
@@ -414,6 +446,9 @@ class ComposedRollout:
   mean) and its outputs are f = W g + c, mixed on the device after every drift match (csrc/mm_mix.h).  Such a rollout (``mixed``)
   takes the ``_nd_mixed`` entries for any nu, one action included: ``__call__``, ``taped_nd`` / ``backward_nd`` and the size queries;
   ``taped`` / ``backward`` (the one-action entries) do not take it.
+
+  The three entry families are described once (``_COMPOSED``); every public method picks one and hands it to the one
+  implementation of its role (``_forward``, ``_taped``, ``_sweep``, the size queries: ``_bytes``).
   """
 
   def __init__(self, drift: PackedModel, policy: PackedModel, nx: int, active_dims, head_scale, head_shift,
@@ -430,6 +465,7 @@ class ComposedRollout:
     self.nd = self.ne + self.nu
     if drift.dtype != policy.dtype:
       raise TypeError("drift and policy must be packed with the same dtype")
+    self._mixing = ()                                    # what trails a mixed entry's arguments: (mix_W, mix_c | NULL)
     if self.mixed:
       if mix_W.ndim != 2 or mix_W.shape[0] != self.nx or mix_W.shape[1] != drift.L:
         raise ValueError(f"mix_W must be [nx = {self.nx}, Lg = {drift.L}] (the drift pack's latents), got {tuple(mix_W.shape)}")
@@ -439,6 +475,7 @@ class ComposedRollout:
         raise ValueError(f"mix_c must have nx = {self.nx} entries")
       self.mix_W = mix_W.detach().to(dtype=torch.float64, device=drift.device).contiguous()
       self.mix_c = None if mix_c is None else mix_c.detach().to(dtype=torch.float64, device=drift.device).reshape(-1).contiguous()
+      self._mixing = (self.mix_W.data_ptr(), _ptr(self.mix_c))
     if (not self.mixed and drift.L != self.nx) or drift.d != self.nd or policy.d != self.ne:
       raise ValueError(f"shapes do not compose: drift L={drift.L} d={drift.d} (want {self.nx}, {self.nd}), "
                        f"policy L={policy.L} d={policy.d} (want {self.nu}, {self.ne})")
@@ -446,13 +483,27 @@ class ComposedRollout:
       raise ValueError("the drift is evaluated with model uncertainty: pack it with C")
     if self.nu == 1:
       self.scale, self.shift = float(head_scale), float(head_shift)
+      scales, shifts = (self.scale,), (self.shift,)
     else:
-      self.scale, self.shift = self._per_action(head_scale, "head_scale"), self._per_action(head_shift, "head_shift")
-      self._scale_c = (_lib.C.c_double * self.nu)(*self.scale)
-      self._shift_c = (_lib.C.c_double * self.nu)(*self.shift)
+      self.scale, self.shift = scales, shifts = self._per_action(head_scale, "head_scale"), self._per_action(head_shift, "head_shift")
     self.target = target.to(dtype=drift.dtype, device=drift.device).contiguous()
     self.precis = precis.to(dtype=drift.dtype, device=drift.device).contiguous()
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
+    # what of an entry's argument list never changes, built once (``drift``, ``target``, ``precis``, ``mix_W`` / ``mix_c`` and the head
+    # constants are fixed after construction: their device pointers are read here, and a later reassignment would go unseen --
+    # build a new rollout instead, as ``loops.current_roll`` does): the drift pack, and (nx, na, active dims, head, target, precision)
+    # with the head constants in the two forms the entries take them -- ``head_arrays``: nu and two arrays, else (one action) two floats
+    self._drift_args = (drift.buf.data_ptr(), drift.nbytes, drift.L, drift.M, drift.d)
+    cost_args = (self.target.data_ptr(), self.precis.data_ptr())
+    heads = {True: (self.nu, (_lib.C.c_double * self.nu)(*scales), (_lib.C.c_double * self.nu)(*shifts))}
+    if self.nu == 1:
+      heads[False] = (self.scale, self.shift)
+    self._consts = {arrays: (self.nx, self.na, self._act, *head, *cost_args) for arrays, head in heads.items()}
+    # the dims a family's size queries take after (nx, na), by family name; the family this rollout runs in, and the one its
+    # _nd methods take
+    self._dims = {"one": (), "nd": (self.nu,), "nd_mixed": (self.nu, int(drift.L))}
+    self._nd_family = _COMPOSED["nd_mixed" if self.mixed else "nd"]
+    self._family = self._nd_family if self.uses_nd else _COMPOSED["one"]
     self._wsc = {}
 
   def _per_action(self, v, name):
@@ -464,19 +515,59 @@ class ComposedRollout:
       raise ValueError(f"{name}: expected a float or {self.nu} values (one per action), got {len(vals)}")
     return vals
 
-  def _compose_ws(self, B):
-    ws = self._wsc.get(B)
+  @property
+  def uses_nd(self) -> bool:
+    """The rollout runs in the ``_nd`` family (several actions, or a coregionalised drift with any number of actions)."""
+    return self.nu > 1 or self.mixed
+
+  # ---- the size queries and the argument lists of the three families ---------------------------------------------------------
+  def _bytes(self, fam: _ComposedFamily, query: str, lead: tuple, tail: tuple) -> int:
+    """``query`` (compose_ws / tape_bytes / backward_ws) of ``fam``: (lead.., nx, na, the family's extra dims, tail..) -> bytes;
+    0: the shape is refused."""
+    return getattr(lib(), getattr(fam, query))(*lead, self.nx, self.na, *self._dims[fam.name], *tail)
+
+  def _tape_bytes(self, fam, B, H, code):
+    return self._bytes(fam, "tape_bytes", (B, H), (self.drift.M, code))
+
+  def _backward_ws_bytes(self, fam, B, policy_M):
+    return self._bytes(fam, "backward_ws", (B,), (self.drift.M, policy_M) if fam.latent_axis else (self.drift.M,))
+
+  def _prefix(self, fam, pol, B, H, dt):
+    """What every entry's argument list begins with: the drift and policy packs, the dims, the head and the cost constants."""
+    return (*self._drift_args, pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H, float(dt),
+            *self._consts[fam.head_arrays])
+
+  def _forward_call(self, fam, pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, status, stream):
+    """(entry name, arguments) of the forward rollout on prepared buffers; so ``_taped_call`` / ``_sweep_call`` for their roles."""
+    return fam.forward, (*self._prefix(fam, pol, B, H, dt), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
+                         wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
+                         status.data_ptr(), stream, *(self._mixing if fam.mix else ()))
+
+  def _taped_call(self, fam, pol, B, H, dt, mx, Sxx, cost, wd, wp, tape, status, stream):
+    return fam.taped, (*self._prefix(fam, pol, B, H, dt), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
+                       wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
+                       status.data_ptr(), stream, *(self._mixing if fam.mix else ()))
+
+  def _sweep_call(self, fam, pol, B, H, dt, tape, g_cost, seeds, g_pol, g_m, g_S, wd, wb, status, stream):
+    """``seeds``: None (the unseeded entry) or (g_xm | None, g_xS | None).  The mixed sweep always takes the seeded signature."""
+    if fam.mix and seeds is None:
+      seeds = (None, None)
+    return (fam.backward if seeds is None else fam.seeded,
+            (*self._prefix(fam, pol, B, H, dt), tape.data_ptr(), tape.numel(), g_cost.data_ptr(),
+             *(() if seeds is None else (_ptr(seeds[0]), _ptr(seeds[1]))), g_pol.data_ptr(), _ptr(g_m), _ptr(g_S),
+             wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(), status.data_ptr(), stream, *(self._mixing[:1] if fam.mix else ())))
+
+  # ---- one implementation per role ------------------------------------------------------------------------------------------
+  def _compose_ws(self, fam, B, fresh=False):
+    """The compose workspace of ``fam``: the one this rollout keeps per B for its own family, or a ``fresh`` one."""
+    ws = None if fresh else self._wsc.get(B)
     if ws is None:
-      if self.mixed:
-        n = lib().mm_compose_nd_mixed_workspace_bytes(B, self.nx, self.na, self.nu, self.drift.L, _dtype_code(self.drift.dtype))
-      elif self.nu == 1:
-        n = lib().mm_compose_workspace_bytes(B, self.nx, self.na, _dtype_code(self.drift.dtype))
-      else:
-        n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(self.drift.dtype))
+      n = self._bytes(fam, "compose_ws", (B,), (_dtype_code(self.drift.dtype),))
       if n == 0:
-        raise ValueError("mm_compose_workspace_bytes rejected the shape")
+        raise ValueError(f"{_COMPOSED[fam.plain].compose_ws if fresh else 'mm_compose_workspace_bytes'} rejected the shape")
       ws = torch.empty(n, dtype=torch.uint8, device=self.drift.device)
-      self._wsc[B] = ws
+      if not fresh:
+        self._wsc[B] = ws
     return ws
 
   def _policy_pack(self, policy: Optional[PackedModel]) -> PackedModel:
@@ -497,11 +588,9 @@ class ComposedRollout:
       raise ValueError(f"expected mx [B,{self.nx}], Sxx [B,{self.nx},{self.nx}]")
     return B
 
-  def __call__(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, keep_trajectory: bool = False,
-               policy: Optional[PackedModel] = None):
-    """``policy``: another pack of the same shape to evaluate instead of ``self.policy`` (the current parameters of a
-    trainable policy, packed by the caller)."""
-    pol = self._policy_pack(policy)
+  def _forward(self, fam, pol, mx, Sxx, num_steps, dt, keep_trajectory, fresh_ws=False):
+    """The forward rollout through ``fam``.  ``fresh_ws`` (``call_nd_entry``: ``fam`` need not be the family this rollout runs in):
+    on a compose workspace of its own -- the kept one may be the other family's -- and reported under the plain family's name."""
     B = self._check_state(mx, Sxx)
     dt_ = self.drift.dtype
     mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
@@ -511,116 +600,33 @@ class ComposedRollout:
     tS = torch.empty(H, B, self.nx, self.nx, dtype=dt_, device=mx.device) if keep_trajectory else None
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
-    wc = self._compose_ws(B)
-    if self.uses_nd:
-      scale, shift = self._head_arrays()
-      rc = self._call_nd(pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, scale, shift)
-      check(rc, "mm_rollout_composed_nd_mixed" if self.mixed else "mm_rollout_composed_nd")
-      out = (mx, Sxx, cost.T.contiguous())
-      return out + (tmu, tS) if keep_trajectory else out
-    rc = lib().mm_rollout_composed(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                   pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
-                                   _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act,
-                                   self.scale, self.shift, self.target.data_ptr(), self.precis.data_ptr(),
-                                   mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
-                                   wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
-                                   self.drift.status().data_ptr(), _stream(mx.device))
-    check(rc, "mm_rollout_composed")
+    wc = self._compose_ws(fam, B, fresh=fresh_ws)
+    entry, args = self._forward_call(fam, pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, self.drift.status(),
+                                     _stream(mx.device))
+    check(getattr(lib(), entry)(*args), _COMPOSED[fam.plain].forward if fresh_ws else entry)
     out = (mx, Sxx, cost.T.contiguous())
     return out + (tmu, tS) if keep_trajectory else out
 
-
-  def _call_nd(self, pol, B, H, dt, mx, Sxx, cost, tmu, tS, wd, wp, wc, scale=None, shift=None):
-    """``mm_rollout_composed_nd`` (``mixed``: ``mm_rollout_composed_nd_mixed``) on prepared buffers (``scale`` / ``shift``: ctypes
-    arrays of nu doubles)."""
-    dt_ = self.drift.dtype
-    if self.mixed:
-      return lib().mm_rollout_composed_nd_mixed(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                                pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
-                                                _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act, self.nu,
-                                                self._scale_c if scale is None else scale, self._shift_c if shift is None else shift,
-                                                self.target.data_ptr(), self.precis.data_ptr(),
-                                                mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
-                                                wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
-                                                self.drift.status().data_ptr(), _stream(mx.device),
-                                                self.mix_W.data_ptr(), _ptr(self.mix_c))
-    return lib().mm_rollout_composed_nd(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                        pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d,
-                                        _dtype_code(dt_), B, H, float(dt), self.nx, self.na, self._act, self.nu,
-                                        self._scale_c if scale is None else scale, self._shift_c if shift is None else shift,
-                                        self.target.data_ptr(), self.precis.data_ptr(),
-                                        mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(), _ptr(tmu), _ptr(tS),
-                                        wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), wc.data_ptr(), wc.numel(),
-                                        self.drift.status().data_ptr(), _stream(mx.device))
-
-  @property
-  def uses_nd(self) -> bool:
-    """The rollout runs in the ``_nd`` family (several actions, or a coregionalised drift with any number of actions)."""
-    return self.nu > 1 or self.mixed
-
-  def call_nd_entry(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0):
-    """The same rollout through ``mm_rollout_composed_nd`` whatever nu is (a one-action rollout normally takes
-    ``mm_rollout_composed``): -> (mx_H, Sxx_H, cost [B, H]).  The two entries must agree for nu == 1."""
-    B = self._check_state(mx, Sxx)
-    dt_ = self.drift.dtype
-    mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
-    H = int(num_steps)
-    cost = torch.empty(H, B, dtype=dt_, device=mx.device)
-    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
-    wp = self.policy.workspace(B, MM_FULL_OUTPUT_COV)
-    if self.mixed:
-      n = lib().mm_compose_nd_mixed_workspace_bytes(B, self.nx, self.na, self.nu, self.drift.L, _dtype_code(dt_))
-    else:
-      n = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, _dtype_code(dt_))
-    if n == 0:
-      raise ValueError("mm_compose_nd_workspace_bytes rejected the shape")
-    wc = torch.empty(n, dtype=torch.uint8, device=mx.device)
-    as_c = lambda v: (_lib.C.c_double * self.nu)(*((v,) if self.nu == 1 else v))
-    rc = self._call_nd(self.policy, B, H, dt, mx, Sxx, cost, None, None, wd, wp, wc, as_c(self.scale), as_c(self.shift))
-    check(rc, "mm_rollout_composed_nd")
-    return mx, Sxx, cost.T.contiguous()
-
-  # ---- differentiable form: tape + reverse sweep (csrc/mm_compose_bwd.hip) -------------------------------------------
-  BACKWARD_MAX_POLICY_M = 256
-
-  def supports_backward(self) -> bool:
-    """The native reverse sweep exists for one-action f64 rollouts whose policy has M <= 256 centres on ne <= 8 encoded
-    dims (one workgroup per batch element sweeps the policy's M x M block from LDS: 120 KB at M = 256, ne = 8)."""
-    return (self.nu == 1 and not self.mixed and self.drift.dtype == torch.float64
-            and self.policy.M <= self.BACKWARD_MAX_POLICY_M and self.ne <= 8)
-
-  def taped(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
-    """``mm_rollout_composed_taped``: -> (mx_H, Sxx_H, cost [H, B], tape).  ``policy``: another pack of the same shape
-    (the current parameters of a trainable policy)."""
-    if self.nu != 1:
-      raise NotImplementedError("the tape and the native reverse sweep are one-action (supports_backward() is False)")
-    if self.mixed:
-      raise NotImplementedError("a coregionalised drift takes taped_nd / backward_nd (the one-action entries do not mix)")
+  def _taped(self, fam, mx, Sxx, num_steps, dt, policy):
+    """The taped forward through ``fam``: -> (mx_H, Sxx_H, cost [H, B], tape)."""
     pol = self._policy_pack(policy)
     dt_ = self.drift.dtype
     B, H = self._check_state(mx, Sxx), int(num_steps)
+    if fam.latent_axis:
+      why = self.backward_nd_refusal()
+      if why is not None:
+        raise ValueError(why)
     mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
     cost = torch.empty(H, B, dtype=dt_, device=mx.device)
-    n = lib().mm_compose_tape_bytes(B, H, self.nx, self.na, self.drift.M, _dtype_code(dt_))
-    tape = torch.empty(n, dtype=torch.uint8, device=mx.device)
+    tape = torch.empty(self._tape_bytes(fam, B, H, _dtype_code(dt_)), dtype=torch.uint8, device=mx.device)
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
-    rc = lib().mm_rollout_composed_taped(self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-                                         pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(dt_), B, H, float(dt),
-                                         self.nx, self.na, self._act, self.scale, self.shift, self.target.data_ptr(),
-                                         self.precis.data_ptr(), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
-                                         wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
-                                         self.drift.status().data_ptr(), _stream(mx.device))
-    check(rc, "mm_rollout_composed_taped")
+    entry, args = self._taped_call(fam, pol, B, H, dt, mx, Sxx, cost, wd, wp, tape, self.drift.status(), _stream(mx.device))
+    check(getattr(lib(), entry)(*args), _COMPOSED[fam.plain].taped)
     return mx, Sxx, cost, tape
 
-  def backward(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
-               policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
-    """``mm_rollout_composed_backward``: g_cost [H, B] -> (g_policy [B, M d + M + d + 2], g_mx0 [B,nx] | None,
-    g_Sxx0 [B,nx,nx] | None): the gradient w.r.t. the packed policy (Z, beta, lengthscales^2, variance, mean) per batch
-    element and w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with (``taped(policy=...)``).
-    ``g_traj = (g_xm [H,B,nx], g_xS [H,B,nx,nx])``: seeds d loss / d (m_{h+1}, S_{h+1}) on the taped states, added to the sweep's
-    carry beside the built-in cost's adjoint (``mm_rollout_composed_backward_seeded``)."""
+  def _sweep(self, fam, tape, g_cost, B, num_steps, dt, policy, want_state_grad, g_traj):
+    """The reverse sweep through ``fam``, seeded with ``g_traj`` or not: -> (g_policy, g_mx0 | None, g_Sxx0 | None)."""
     pol = self._policy_pack(policy)
     dev = tape.device
     H = int(num_steps)
@@ -628,38 +634,29 @@ class ComposedRollout:
     g_cost = g_cost.to(f64).contiguous()
     if g_cost.shape != (H, B):
       raise ValueError(f"g_cost must be [H={H}, B={B}]")
-    g_xm, g_xS = self._seeds(g_traj, H, B)
+    seeds = None if g_traj is None else self._seeds(g_traj, H, B)
     npar = pol.M * pol.d + pol.M + pol.d + 2
-    g_pol = torch.empty(B, npar, dtype=f64, device=dev)
+    g_pol = torch.empty((B, self.nu, npar) if fam.latent_axis else (B, npar), dtype=f64, device=dev)
     g_m = torch.empty(B, self.nx, dtype=f64, device=dev) if want_state_grad else None
     g_S = torch.empty(B, self.nx, self.nx, dtype=f64, device=dev) if want_state_grad else None
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
-    key = ("bwd", B)
+    plain = _COMPOSED[fam.plain]
+    key = ("bwd_nd" if fam.latent_axis else "bwd", B)
     wb = self._wsc.get(key)
     if wb is None:
-      n = lib().mm_compose_backward_workspace_bytes(B, self.nx, self.na, self.drift.M)
+      n = self._backward_ws_bytes(fam, B, pol.M)
       if n == 0:
-        raise ValueError("mm_compose_backward_workspace_bytes rejected the shape")
+        raise ValueError(f"{plain.backward_ws} rejected the shape")
       wb = torch.empty(n, dtype=torch.uint8, device=dev)
       self._wsc[key] = wb
-    head = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
-            float(dt), self.nx, self.na, self._act, self.scale, self.shift,
-            self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), g_cost.data_ptr())
-    tail = (g_pol.data_ptr(), _ptr(g_m), _ptr(g_S), wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
-            self.drift.status().data_ptr(), _stream(dev))
-    if g_traj is None:
-      rc = lib().mm_rollout_composed_backward(*head, *tail)
-    else:
-      rc = lib().mm_rollout_composed_backward_seeded(*head, _ptr(g_xm), _ptr(g_xS), *tail)
-    check(rc, "mm_rollout_composed_backward")
+    entry, args = self._sweep_call(fam, pol, B, H, dt, tape, g_cost, seeds, g_pol, g_m, g_S, wd, wb, self.drift.status(),
+                                   _stream(dev))
+    check(getattr(lib(), entry)(*args), plain.backward)
     return g_pol, g_m, g_S
 
   def _seeds(self, g_traj, H, B):
     """``g_traj`` of ``backward`` / ``backward_nd`` as contiguous f64 tensors of the tape's shapes (``(None, None)`` passes the
     seeded entry null seeds)."""
-    if g_traj is None:
-      return None, None
     g_xm, g_xS = g_traj
     if (g_xm is None) != (g_xS is None):
       raise ValueError("g_traj: both seeds or neither")
@@ -670,18 +667,53 @@ class ComposedRollout:
       raise ValueError(f"g_traj must be (g_xm [H={H}, B={B}, {self.nx}], g_xS [H, B, {self.nx}, {self.nx}])")
     return g_xm, g_xS
 
+  # ---- forward -------------------------------------------------------------------------------------------------------------
+  def __call__(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, keep_trajectory: bool = False,
+               policy: Optional[PackedModel] = None):
+    """``policy``: another pack of the same shape to evaluate instead of ``self.policy`` (the current parameters of a
+    trainable policy, packed by the caller)."""
+    return self._forward(self._family, self._policy_pack(policy), mx, Sxx, num_steps, dt, keep_trajectory)
+
+  def call_nd_entry(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0):
+    """The same rollout through ``mm_rollout_composed_nd`` whatever nu is (a one-action rollout normally takes
+    ``mm_rollout_composed``): -> (mx_H, Sxx_H, cost [B, H]).  The two entries must agree for nu == 1."""
+    return self._forward(self._nd_family, self.policy, mx, Sxx, num_steps, dt, False, fresh_ws=True)
+
+  # ---- differentiable form: tape + reverse sweep (csrc/mm_compose_bwd.hip) -------------------------------------------
+  BACKWARD_MAX_POLICY_M = 256
+
+  def supports_backward(self) -> bool:
+    """The native reverse sweep exists for one-action f64 rollouts whose policy has M <= 256 centres on ne <= 8 encoded
+    dims (one workgroup per batch element sweeps the policy's M x M block from LDS: 120 KB at M = 256, ne = 8)."""
+    return (self.nu == 1 and not self.mixed and self.drift.dtype == torch.float64
+            and self.policy.M <= self.BACKWARD_MAX_POLICY_M and self.ne <= 8)
+
+  def _one_action_family(self):
+    if self.nu != 1:
+      raise NotImplementedError("the tape and the native reverse sweep are one-action (supports_backward() is False)")
+    if self.mixed:
+      raise NotImplementedError("a coregionalised drift takes taped_nd / backward_nd (the one-action entries do not mix)")
+    return _COMPOSED["one"]
+
+  def taped(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
+    """``mm_rollout_composed_taped``: -> (mx_H, Sxx_H, cost [H, B], tape).  ``policy``: another pack of the same shape
+    (the current parameters of a trainable policy)."""
+    return self._taped(self._one_action_family(), mx, Sxx, num_steps, dt, policy)
+
+  def backward(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
+               policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
+    """``mm_rollout_composed_backward``: g_cost [H, B] -> (g_policy [B, M d + M + d + 2], g_mx0 [B,nx] | None,
+    g_Sxx0 [B,nx,nx] | None): the gradient w.r.t. the packed policy (Z, beta, lengthscales^2, variance, mean) per batch
+    element and w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with (``taped(policy=...)``).
+    ``g_traj = (g_xm [H,B,nx], g_xS [H,B,nx,nx])``: seeds d loss / d (m_{h+1}, S_{h+1}) on the taped states, added to the sweep's
+    carry beside the built-in cost's adjoint (``mm_rollout_composed_backward_seeded``)."""
+    return self._sweep(self._one_action_family(), tape, g_cost, B, num_steps, dt, policy, want_state_grad, g_traj)
+
   def tape_states(self, tape: torch.Tensor, B: int, num_steps: int):
     """The states x_1 .. x_H a taped rollout left on its tape: -> (xm [H, B, nx], xS [H, B, nx, nx]), float64 copies."""
     H = int(num_steps)
-    if self.mixed:
-      n = lib().mm_compose_tape_bytes_nd_mixed(B, H, self.nx, self.na, self.nu, self.drift.L, self.drift.M, MM_F64)
-      slot = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, MM_F64)        # (the slots are the _nd ones)
-    elif self.nu == 1:
-      n = lib().mm_compose_tape_bytes(B, H, self.nx, self.na, self.drift.M, MM_F64)
-      slot = lib().mm_compose_workspace_bytes(B, self.nx, self.na, MM_F64)
-    else:
-      n = lib().mm_compose_tape_bytes_nd(B, H, self.nx, self.na, self.nu, self.drift.M, MM_F64)
-      slot = lib().mm_compose_nd_workspace_bytes(B, self.nx, self.na, self.nu, MM_F64)
+    n = self._tape_bytes(self._family, B, H, MM_F64)
+    slot = self._bytes(_COMPOSED[self._family.plain], "compose_ws", (B,), (MM_F64,))
     if n == 0 or tape.numel() < n or tape.dtype != torch.uint8:
       raise ValueError("not a tape of this rollout")
     # MMTapeLayout (csrc/mm_compose.h): H + 1 slots, then x_0 .. x_H means and covariances, each block aligned to 256 bytes
@@ -693,21 +725,11 @@ class ComposedRollout:
     return xm[1:].clone(), xS[1:].clone()
 
   # ---- the same for 1 to 4 actions (csrc/mm_compose_nd.hip, csrc/mm_compose_bwd_nd.hip) -----------------------------------
-  def _head_arrays(self):
-    """(scale, shift) as ctypes arrays of nu doubles (a one-action rollout keeps them as floats)."""
-    if self.nu > 1:
-      return self._scale_c, self._shift_c
-    return (_lib.C.c_double * 1)(self.scale), (_lib.C.c_double * 1)(self.shift)
-
   def backward_nd_refusal(self) -> Optional[str]:
     """Why ``taped_nd`` / ``backward_nd`` do not take this rollout (None: they do)."""
     if self.drift.dtype != torch.float64:
       return "the multi-action tape and reverse sweep are float64 only"
-    if self.mixed:
-      n = lib().mm_compose_backward_workspace_bytes_nd_mixed(1, self.nx, self.na, self.nu, self.drift.L, self.drift.M, self.policy.M)
-    else:
-      n = lib().mm_compose_backward_workspace_bytes_nd(1, self.nx, self.na, self.nu, self.drift.M, self.policy.M)
-    if n == 0:
+    if self._backward_ws_bytes(self._nd_family, 1, self.policy.M) == 0:
       return (f"the policy (M = {self.policy.M} centres on ne = {self.ne} dims, {self.nu} actions) is past the LDS bound of the "
               "multi-action reverse sweep (M <= 256, ne <= 8 and 160 KB of LDS per workgroup: M <= 166 at ne = 8)")
     return None
@@ -719,38 +741,11 @@ class ComposedRollout:
 
   def tape_bytes_nd(self, B: int, num_steps: int) -> int:
     """Size of the tape ``taped_nd`` records (``mm_compose_tape_bytes_nd`` / ``_nd_mixed``; 0: shape refused)."""
-    if self.mixed:
-      return lib().mm_compose_tape_bytes_nd_mixed(B, int(num_steps), self.nx, self.na, self.nu, self.drift.L, self.drift.M,
-                                                  _dtype_code(self.drift.dtype))
-    return lib().mm_compose_tape_bytes_nd(B, int(num_steps), self.nx, self.na, self.nu, self.drift.M, _dtype_code(self.drift.dtype))
+    return self._tape_bytes(self._nd_family, B, int(num_steps), _dtype_code(self.drift.dtype))
 
   def taped_nd(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
     """``mm_rollout_composed_taped_nd``: -> (mx_H, Sxx_H, cost [H, B], tape), for any nu in 1..4."""
-    pol = self._policy_pack(policy)
-    dt_ = self.drift.dtype
-    B, H = self._check_state(mx, Sxx), int(num_steps)
-    why = self.backward_nd_refusal()
-    if why is not None:
-      raise ValueError(why)
-    mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
-    cost = torch.empty(H, B, dtype=dt_, device=mx.device)
-    n = self.tape_bytes_nd(B, H)
-    tape = torch.empty(n, dtype=torch.uint8, device=mx.device)
-    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
-    wp = pol.workspace(B, MM_FULL_OUTPUT_COV)
-    scale, shift = self._head_arrays()
-    args = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(dt_), B, H, float(dt),
-            self.nx, self.na, self._act, self.nu, scale, shift, self.target.data_ptr(),
-            self.precis.data_ptr(), mx.data_ptr(), Sxx.data_ptr(), cost.data_ptr(),
-            wd.data_ptr(), wd.numel(), wp.data_ptr(), wp.numel(), tape.data_ptr(), tape.numel(),
-            self.drift.status().data_ptr(), _stream(mx.device))
-    if self.mixed:
-      rc = lib().mm_rollout_composed_taped_nd_mixed(*args, self.mix_W.data_ptr(), _ptr(self.mix_c))
-    else:
-      rc = lib().mm_rollout_composed_taped_nd(*args)
-    check(rc, "mm_rollout_composed_taped_nd")
-    return mx, Sxx, cost, tape
+    return self._taped(self._nd_family, mx, Sxx, num_steps, dt, policy)
 
   def backward_nd(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
                   policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
@@ -758,45 +753,7 @@ class ComposedRollout:
     g_Sxx0 [B,nx,nx] | None): per batch element and latent the gradient w.r.t. the packed policy (Z, beta, lengthscales^2,
     variance, mean), and the gradient w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with.
     ``g_traj``: seeds on the taped states as in ``backward`` (``mm_rollout_composed_backward_nd_seeded``)."""
-    pol = self._policy_pack(policy)
-    dev = tape.device
-    H = int(num_steps)
-    f64 = torch.float64
-    g_cost = g_cost.to(f64).contiguous()
-    if g_cost.shape != (H, B):
-      raise ValueError(f"g_cost must be [H={H}, B={B}]")
-    g_xm, g_xS = self._seeds(g_traj, H, B)
-    npar = pol.M * pol.d + pol.M + pol.d + 2
-    g_pol = torch.empty(B, self.nu, npar, dtype=f64, device=dev)
-    g_m = torch.empty(B, self.nx, dtype=f64, device=dev) if want_state_grad else None
-    g_S = torch.empty(B, self.nx, self.nx, dtype=f64, device=dev) if want_state_grad else None
-    wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
-    key = ("bwd_nd", B)
-    wb = self._wsc.get(key)
-    if wb is None:
-      if self.mixed:
-        n = lib().mm_compose_backward_workspace_bytes_nd_mixed(B, self.nx, self.na, self.nu, self.drift.L, self.drift.M, pol.M)
-      else:
-        n = lib().mm_compose_backward_workspace_bytes_nd(B, self.nx, self.na, self.nu, self.drift.M, pol.M)
-      if n == 0:
-        raise ValueError("mm_compose_backward_workspace_bytes_nd rejected the shape")
-      wb = torch.empty(n, dtype=torch.uint8, device=dev)
-      self._wsc[key] = wb
-    scale, shift = self._head_arrays()
-    head = (self.drift.buf.data_ptr(), self.drift.nbytes, self.drift.L, self.drift.M, self.drift.d,
-            pol.buf.data_ptr(), pol.nbytes, pol.M, pol.d, _dtype_code(self.drift.dtype), B, H,
-            float(dt), self.nx, self.na, self._act, self.nu, scale, shift,
-            self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), g_cost.data_ptr())
-    tail = (g_pol.data_ptr(), _ptr(g_m), _ptr(g_S), wd.data_ptr(), wd.numel(), wb.data_ptr(), wb.numel(),
-            self.drift.status().data_ptr(), _stream(dev))
-    if self.mixed:
-      rc = lib().mm_rollout_composed_backward_nd_mixed(*head, _ptr(g_xm), _ptr(g_xS), *tail, self.mix_W.data_ptr())
-    elif g_traj is None:
-      rc = lib().mm_rollout_composed_backward_nd(*head, *tail)
-    else:
-      rc = lib().mm_rollout_composed_backward_nd_seeded(*head, _ptr(g_xm), _ptr(g_xS), *tail)
-    check(rc, "mm_rollout_composed_backward_nd")
-    return g_pol, g_m, g_S
+    return self._sweep(self._nd_family, tape, g_cost, B, num_steps, dt, policy, want_state_grad, g_traj)
 
 
 class GraphedComposedRollout:
