@@ -165,6 +165,12 @@ SIGNATURES = {
                                         + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
                                         + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
                                         + [C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "mm_pathwise_mean_eval": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 10 + [C.c_int]),
+    "mm_pathwise_policy_rollout_mean": (C.c_int, [C.c_int] * 4 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int]
+                                        + [C.c_void_p] * 6
+                                        + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+                                        + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+                                        + [C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "mm_pathwise_basis": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 9),
     "mm_pathwise_pack_stream": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 4),
     "mm_rollout_closed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -25,7 +25,9 @@
 // two angles, one force: nd 9; a three-link arm: nd 13), the _kern entry (a drift of any kernel family), and
 // the _mixed entries (nd <= 16), which take a COREGIONALISED drift f = W g + c: the stream pass runs with the Lg <= nx
 // latents into a latent-sized tape (sample slot [S][Lg], Jacobians [H][S][Lg][nd]) and both kernels mix in place of a launch of
-// its own (bool MIXED: the head steps x += dt (c + W g), the sweep takes g d = dt J_g^T (W^T g x)).
+// its own (bool MIXED: the head steps x += dt (c + W g), the sweep takes g d = dt J_g^T (W^T g x)).  The _mean entry is the same
+// function with the per-step stream pass replaced by the shared-weight mean pass (mm_pathwise_mean.hip): the drift of every
+// sample is the posterior mean, nothing is streamed; tape and sweeps do not know the difference.
 //
 // Both kernels are templates in the action count: the loops over the latents unroll and the per-latent constants sit in
 // registers.
@@ -295,7 +297,9 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
                             const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
                             int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
                             char* tape, const MMPwTapeLayout& tl, int Lg, const double* mix_W, const double* mix_c,
-                            hipStream_t s, int kernel) {
+                            hipStream_t s, int kernel, const double* beta) {
+  // beta != NULL: the _mean entry -- the drift is its posterior MEAN, one shared weight vector per latent in place of the stream
+  // (mm_pathwise_mean.hip: same f and Jacobian slots); omega_t, phase, prior_scale, wb and K are then not read
   // Lg > 0: the _mixed entries -- the stream pass runs with Lg latents and no latent mean straight into the tape's (latent-sized)
   // f and Jacobian slots, the head kernel mixes
   const int nx = D.nx, ne = D.ne, nd = D.nd, Lf = Lg > 0 ? Lg : nx;
@@ -324,9 +328,11 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (h == H) break;
-    const int rc = mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
-                                      prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f,
-                                      jac ? jac + (size_t)h * S * Lf * nd : nullptr, s, kernel);
+    T* jh = jac ? jac + (size_t)h * S * Lf * nd : nullptr;
+    const int rc = beta ? mm_pathwise_mean_launch(S, Lf, M, nd, dtype, dins + (size_t)h * S * nd, zs_t, hz, x_scale, variance,
+                                                  Lg > 0 ? nullptr : mean_c, beta, f, jh, s, kernel)
+                        : mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
+                                             prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f, jh, s, kernel);
     if (rc) return rc;
   }
   return 0;
@@ -349,15 +355,16 @@ static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, c
                           const void* policy_packed, size_t policy_bytes, int policy_M,
                           const double* head_scale, const double* head_shift, const void* target,
                           const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
-                          int with_jacobians, void* stream, int kernel = 0, bool one_action = false) {
+                          int with_jacobians, void* stream, int kernel = 0, bool one_action = false,
+                          const double* beta = nullptr) {
   if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;             // the drift's kernel family (mm_pathwise_eval_kern)
   MMComposeDims D;
   int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, one_action, D);
   if (rc) return rc;
   if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
   if (!mixed) Lg = 0;                                        // (what the launches below take for "no mixing")
-  if (!omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !policy_packed || !head_scale ||
-      !head_shift || !target || !precis || !x0 || !cost || !tape || (mixed && !mix_W)) return MM_E_ARG;
+  if ((!beta && (!omega_t || !phase || !prior_scale || !wb)) || !zs_t || !hz || !x_scale || !variance || !policy_packed ||
+      !head_scale || !head_shift || !target || !precis || !x0 || !cost || !tape || (mixed && !mix_W)) return MM_E_ARG;
   const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, with_jacobians);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
@@ -368,10 +375,10 @@ static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, c
   if (dtype == MM_F64)
     return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
                                     wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
-                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
+                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s, kernel, beta);
   return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
                                  pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
-                                 (char*)tape, tl, Lg, mix_W, mix_c, s, kernel);
+                                 (char*)tape, tl, Lg, mix_W, mix_c, s, kernel, beta);
 }
 
 #define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
@@ -434,6 +441,25 @@ extern "C" int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, i
   return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t,
                         phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,
                         head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel);
+}
+
+// the MEAN of the drift in place of its sample paths (the reference's model_uncertainty=False: the drift in a KernelRegressor):
+// the _kern entry's argument list without (K, omega_t, phase, prior_scale, wb) and with beta [L][M] f64 = Kuu^-1 u after mean_c
+// (L = nx, or Lg with mixing).  Same tape, same reverse sweeps; M needs no padding.
+extern "C" int mm_pathwise_policy_rollout_mean(int S, int M, int dtype, int H, double dt, int nx, int na,
+                                               const int32_t* active_dims, int nu, const void* zs_t, const void* hz,
+                                               const double* x_scale, const double* variance, const double* mean_c,
+                                               const double* beta, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                               const double* head_scale, const double* head_shift, const void* target,
+                                               const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
+                                               int with_jacobians, void* stream, int Lg, const double* mix_W,
+                                               const double* mix_c, int kernel) {
+  if (kernel < 0 || kernel >= MM_PW_KERNELS || !beta) return MM_E_ARG;
+  const bool mixed = Lg != 0 || mix_W != nullptr;
+  return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, 1, dtype, H, dt, nx, na, active_dims, nu, nullptr,
+                        nullptr, zs_t, hz, x_scale, nullptr, variance, mean_c, nullptr, policy_packed, policy_bytes, policy_M,
+                        head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel, false,
+                        beta);
 }
 
 // 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)

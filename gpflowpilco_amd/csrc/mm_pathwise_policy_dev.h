@@ -9,6 +9,10 @@
 int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
                        const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
                        const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel = 0);
+// the same outputs from the MEAN of the drift (shared weights beta [L,M] f64 in place of the stream; mm_pathwise_mean.hip, d <= 16)
+int mm_pathwise_mean_launch(int S, int L, int M, int d, int dtype, const void* x, const void* zs_t, const void* hz,
+                            const double* x_scale, const double* variance, const double* mean_c, const double* beta, void* f_out,
+                            void* jac, hipStream_t s, int kernel);
 
 #define MMP_NE 24            // largest encoded dimension (2 na + nb, na <= 8, nx <= 16)
 #define MMP_POLICY_MMAX 256

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 from typing import Callable, Optional, Sequence
 
+import contextlib
 import functools
 import warnings
 
@@ -35,12 +36,18 @@ def _native_parts(system: DynamicalSystem, objective: Callable, why: Optional[li
   na = 0: the encoding is the identity); the encoder returned is then one without active dims.  ``any_objective``: also take an
   objective that is no ``GaussianObjective`` (the caller evaluates it on the native rollout's trajectory).  ``coregionalized``: also
   take a drift with a ``LinearCoregionalization`` kernel of no more latents than outputs (the caller mixes: ``_drift_mixing``); a
-  coregionalised policy stays refused."""
+  coregionalised policy stays refused.  Without ``moment_solver`` a drift wrapped in a ``KernelRegressor`` (a mean-only drift)
+  is looked through: the drift returned is the model inside."""
   from . import bijectors as tfb
   from .components import TrigonometricEncoder
   from .cost import GaussianObjective
   from .models import SVGP, InverseLinkWrapper, KernelRegressor, LinearCoregionalization, kernel_family
   enc, pol, drift = system.encoder, system.policy, system.drift
+  if not moment_solver and isinstance(drift, KernelRegressor):
+    # a mean-only drift under the Euler solver (the reference's model_uncertainty=False): the parts are those of the model
+    # inside; the pathwise closure evaluates its mean (pathwise.MeanDrift).  The moment-matching closures keep refusing it below:
+    # their native rollouts carry the model's uncertainty
+    drift = drift.model
 
   def no(reason):
     if why is not None:
@@ -634,14 +641,27 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
   options, with no flag of its own: its paths carry ``Paths.kernel`` and ``PolicyRollout`` calls
   ``mm_pathwise_policy_rollout_kern`` for every shape; the torch composition (``native=False``) works too, because
   ``Paths.__call__`` routes on the family.  A Matern POLICY falls back once, by name (``native=True`` raises): the native head
-  kernels evaluate a SquaredExponential policy; its torch composition is ``SVGP.predict_mean`` with the family's Gram matrix."""
+  kernels evaluate a SquaredExponential policy; its torch composition is ``SVGP.predict_mean`` with the family's Gram matrix.
+
+  A MEAN-ONLY drift -- ``system.drift`` a ``KernelRegressor`` around an ``SVGP`` / ``PathwiseSVGP``, what the reference's
+  ``build_dynamics(..., model_uncertainty=False)`` builds (pilco.py:45-79) -- steps every sample with the posterior mean.  Nothing
+  is drawn: ``paths``, ``num_bases``, ``generator`` and ``native_sampler`` are ignored, as ``KernelRegressor.__call__`` ignores the
+  paths.  The torch composition is the same Euler fold (``drift(eu)`` is ``predict_mean``); on the GPU the native route runs under
+  the rules and options above, with no flag of its own, on a ``pathwise.MeanDrift`` of the model (cached per version of its
+  parameters; ``mm_pathwise_policy_rollout_mean``: the shared weights through LDS instead of a weight stream).  A drift whose
+  parameters require a gradient falls back once, by name: the torch composition differentiates ``predict_mean``.  With
+  ``native=True`` an obstacle met at a call (nd > 16, more actions than ``native_actions``, a trainable drift, ...) raises with the
+  reason the fallback would have named."""
   from . import ops
   from .components import TrigonometricEncoder
   from .linalg import index_tensor
-  from .models import LinearCoregionalization
-  from .pathwise import PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction, PolicyTrajectoryFunction
+  from .models import SVGP, KernelRegressor, LinearCoregionalization
+  from .pathwise import MeanDrift, PathSampler, PathwiseSVGP, PolicyRollout, PolicyRolloutFunction, PolicyTrajectoryFunction
   drift = system.drift
-  if not isinstance(drift, PathwiseSVGP):
+  mean_only = isinstance(drift, KernelRegressor) and isinstance(drift.model, SVGP)
+  if mean_only:
+    drift = drift.model                                        # (system.drift keeps the wrapper: system.forward evaluates the mean)
+  elif not isinstance(drift, PathwiseSVGP):
     raise TypeError("pathwise_policy_loss_closure needs a PathwiseSVGP drift (gpflow_pilco/loops/pilco.py:230-236)")
   H = int(num_steps)
   why_not: list = []
@@ -657,6 +677,10 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     raise ValueError("native=True: the native pathwise rollout is one-action" if max_native <= 1 else
                      f"native=True: the policy has {parts[1].num_latent_gps} actions, native_actions={max_native}")
   _fallback = functools.partial(_warn_fallback, [], native, "pathwise_policy_loss_closure")
+  if mean_only and native is True:
+    # a mean-only drift had no route before this one: native=True holds at every call too (a sampled drift keeps its warning)
+    def _fallback(reason):
+      raise ValueError(f"native=True: {reason}")
 
   def _torch_loss(x0, pth):
     times = dt * np.arange(1, 1 + H, dtype=np.float64)
@@ -666,7 +690,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       return loss + objective(x=state if enc is None else enc(state), t=t)
     loss0 = torch.zeros(x0.shape[:-1], dtype=x0.dtype, device=x0.device)
     solver = Euler()
-    with drift.set_temporary_paths(pth):
+    # (a mean-only drift reads no paths: system.drift(eu) is KernelRegressor.__call__ = predict_mean)
+    with (contextlib.nullcontext() if mean_only else drift.set_temporary_paths(pth)):
       _, loss = solver(func=system.forward, initial_time=0.0, initial_state=x0, solution_times=times,
                        callbacks_and_initializers=((_accumulate_loss, loss0),), iterator="foldl")
     return loss
@@ -706,7 +731,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
 
   def _closure():
     x0 = state_initializer()
-    pth = paths if paths is not None else _new_paths(x0)
+    # (a mean-only drift: nothing is drawn and given paths are not read, as KernelRegressor.__call__ ignores them)
+    pth = None if mean_only else paths if paths is not None else _new_paths(x0)
     if parts is None or not x0.is_cuda or x0.ndim != 2:
       if x0.is_cuda and native is not False:
         _fallback(why_not[0] if why_not else f"state of rank {x0.ndim}")
@@ -733,6 +759,13 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
       return _torch_loss(x0, pth)
     traj = _objective_uses_trajectory(objective, native_objective)
     grad = torch.is_grad_enabled()
+    if mean_only:
+      frozen = list(drift._parameters()) + ([drift.kernel.W] if isinstance(drift.kernel, LinearCoregionalization) else [])
+      if grad and any(isinstance(t, torch.Tensor) and t.requires_grad for t in frozen):
+        _fallback("the mean-only drift's parameters require a gradient (the native rollout takes a frozen drift; the torch "
+                  "composition differentiates predict_mean)")
+        return _torch_loss(x0, pth)
+      pth = MeanDrift.from_model(drift, x0.dtype, x0.device)   # cached per version of the drift's parameters
     if isinstance(drift.kernel, LinearCoregionalization):      # (native_coregionalized: _native_parts refused it otherwise)
       obstacle = _pathwise_mixing_obstacle(drift, pth, grad)
       if obstacle is not None:
@@ -747,7 +780,8 @@ def pathwise_policy_loss_closure(system: DynamicalSystem, objective: Callable, s
     # (the trajectory route: a zero built-in cost, its output ignored)
     # (a Matern drift: PolicyRollout routes on pth.kernel -- the one _kern entry, for every shape admitted above)
     roll = PolicyRollout(pth, pol_pack, nx=nx, active_dims=enc.active_dims, head_scale=scale, head_shift=shift,
-                         target=None if traj else objective.target, precis=None if traj else objective.precis, wide=nd > 8)
+                         target=None if traj else objective.target, precis=None if traj else objective.precis, wide=nd > 8,
+                         num_samples=x0.shape[0] if mean_only else None)
     needs = grad and (x0.requires_grad or any(t.requires_grad for t in pm_._parameters()))
     if needs and not roll.supports_backward():
       _fallback(f"the native reverse sweep does not take nu = {nu} actions with {pol_M} centres on {nx + na} inputs (its LDS bound)")

@@ -302,6 +302,127 @@ def _mean_and_mixing(model: SVGP, L: int, device):
   return None, W, (None if c is None else c.expand(W.shape[0]).clone().contiguous())
 
 
+@dataclass
+class MeanDrift:
+  """The posterior MEAN of a frozen model as the native entries take it: what a drift wrapped in a ``KernelRegressor`` (the
+  reference's ``build_dynamics(..., model_uncertainty=False)``, gpflow_pilco/loops/pilco.py:45-79) evaluates for every sample
+  under the Euler solver.  The operands are ``Paths``' update half with ONE weight vector per latent, beta = Kuu^-1 u
+  (``SVGP._mean_weights``), in place of the per-sample stream: no prior half, no sample axis -- ``__call__`` and ``eval_jac`` take
+  any number of rows.  ``mix_W`` / ``mix_c`` as in ``Paths``: the mean of a coregionalised model, W g + c.  Evaluation runs in
+  ``mm_pathwise_mean_eval`` (csrc/mm_pathwise_mean.hip: the operands staged through LDS, nothing of size S M in memory);
+  ``PolicyRollout`` takes a ``MeanDrift`` in place of ``Paths``."""
+  zs: torch.Tensor             # [L, d, Mp]   (Z * x_scale)^T, x_scale = sqrt(log2 e) / lengthscales
+  hz: torch.Tensor             # [L, Mp]      |zs|^2 / 2
+  beta: torch.Tensor           # [L, Mp] f64  Kuu^-1 u, zero beyond M
+  lengthscales: torch.Tensor   # [L, d] f64: x_scale, as in Paths
+  variance: torch.Tensor       # [L] f64
+  mean_c: Optional[torch.Tensor]  # [L] f64 or None
+  mix_W: Optional[torch.Tensor] = None   # [nx, Lg] f64
+  mix_c: Optional[torch.Tensor] = None   # [nx] f64 or None
+  kernel: int = 0
+  num_centres: int = 0                   # M: the centres before padding
+
+  PAD = 32                               # Mp is a multiple of it (the entry itself takes any M)
+
+  @property
+  def dtype(self):
+    return self.zs.dtype
+
+  @property
+  def device(self):
+    return self.zs.device
+
+  def _dims(self):
+    L, d, Mp = self.zs.shape
+    return L, Mp, d
+
+  @classmethod
+  def from_arrays(cls, Z, lengthscales, variance, beta, mean_c=None, dtype=torch.float32, device="cuda", mix_W=None, mix_c=None,
+                  kernel="se") -> "MeanDrift":
+    """Z [L, M, d], lengthscales [L, d], variance [L], beta [L, M] (and mean_c [L], or the mixing of a coregionalised model):
+    the expressions of ``paths_from_arrays`` for the operands the two share."""
+    kernel = _kernel_code(kernel)
+    t64 = lambda a: torch.as_tensor(a, dtype=DEFAULT_FLOAT, device=device).detach()
+    if mix_W is None and mix_c is not None:
+      raise ValueError("mix_c without mix_W")
+    if mix_W is not None and mean_c is not None:
+      raise ValueError("a mixed mean carries no latent mean: the constant is mix_c, added after the mixing")
+    xscale = math.sqrt(math.log2(math.e)) / t64(lengthscales)
+    zs = t64(Z) * xscale[:, None, :]
+    hz = 0.5 * (zs * zs).sum(-1)
+    tt = lambda a: a.to(dtype).contiguous()
+    beta = t64(beta)
+    if beta.shape != zs.shape[:2]:
+      raise ValueError(f"beta must be [L, M] = {tuple(zs.shape[:2])}, got {tuple(beta.shape)}")
+    return cls(zs=tt(_pad_last(zs.transpose(1, 2), cls.PAD)), hz=tt(_pad_last(hz, cls.PAD)),
+               beta=_pad_last(beta, cls.PAD).contiguous(), lengthscales=xscale.contiguous(), variance=t64(variance).contiguous(),
+               mean_c=None if mean_c is None else t64(mean_c).contiguous(),
+               mix_W=None if mix_W is None else t64(mix_W).contiguous(),
+               mix_c=None if mix_c is None else t64(mix_c).reshape(-1).contiguous(), kernel=kernel, num_centres=int(Z.shape[1]))
+
+  @classmethod
+  def from_model(cls, model, dtype=torch.float32, device="cuda") -> "MeanDrift":
+    """The mean of an ``SVGP`` / ``PathwiseSVGP`` (or of a ``KernelRegressor`` around one), SquaredExponential or Matern.  Cached
+    on the model per (dtype, device) and per version of its parameters, like its packs: an in-place update makes the next call
+    rebuild it; a cache hit reads nothing from the device (a HIP-graph capture of a closure that calls this is fine once warm)."""
+    from .models import GPModelWrapper
+    while isinstance(model, GPModelWrapper):
+      model = model.model
+    if not isinstance(model, SVGP):
+      raise TypeError(f"MeanDrift.from_model takes an SVGP (or a KernelRegressor around one), got {type(model).__name__}")
+    device = torch.device(device)
+    params = list(model._parameters())
+    if isinstance(model.kernel, LinearCoregionalization):
+      params.append(model.kernel.W)
+    family = kernel_family(model.latent_kernels)
+    key = tuple((id(t), t._version, t.device) for t in params) + (family,)
+    cache = model.__dict__.setdefault("_mean_drift_cache", {})
+    slot = (dtype, str(device))
+    hit = cache.get(slot)
+    if hit is not None and hit[0] == key:
+      return hit[1]
+    with torch.no_grad():
+      Z, ls, var, beta, _ = model._mean_weights(device, family)
+      mean_c, mix_W, mix_c = _mean_and_mixing(model, Z.shape[0], device)
+      out = cls.from_arrays(Z, ls, var, beta, mean_c, dtype=dtype, device=device, mix_W=mix_W, mix_c=mix_c, kernel=family)
+    cache[slot] = (key, out)
+    return out
+
+  def _mixed_values(self, g: torch.Tensor) -> torch.Tensor:
+    f = g.to(DEFAULT_FLOAT) @ self.mix_W.T
+    return (f if self.mix_c is None else f + self.mix_c).to(self.dtype)
+
+  def _eval(self, x: torch.Tensor, jac: bool):
+    _require_device(x, self.zs)
+    L, Mp, d = self._dims()
+    if x.ndim != 2 or x.shape[1] != d or x.dtype != self.dtype:
+      raise ValueError(f"expected x [S,{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    S = x.shape[0]
+    out = torch.empty(S, L, dtype=self.dtype, device=x.device)
+    J = torch.empty(S, L, d, dtype=self.dtype, device=x.device) if jac else None
+    rc = _lib.lib().mm_pathwise_mean_eval(S, L, Mp, d, _dtype_code(self.dtype), x.data_ptr(), self.zs.data_ptr(),
+                                          self.hz.data_ptr(), self.lengthscales.data_ptr(), self.variance.data_ptr(),
+                                          _ptr(self.mean_c), self.beta.data_ptr(), out.data_ptr(), _ptr(J), _stream(x.device),
+                                          int(self.kernel))
+    check(rc, "mm_pathwise_mean_eval")
+    return out, J
+
+  def __call__(self, x: torch.Tensor) -> torch.Tensor:
+    """x [S, d] -> the mean [S, L] (mixed: [S, nx]); differentiable in x through the Jacobian of the same pass."""
+    if torch.is_grad_enabled() and x.requires_grad:
+      return _PathsEval.apply(x, self)
+    g = self._eval(x, False)[0]
+    return g if self.mix_W is None else self._mixed_values(g)
+
+  def eval_jac(self, x: torch.Tensor):
+    """-> (f [S, L], d f / d x [S, L, d]) from one pass; mixed: (W g + c, W J_g).  f is bit-equal to ``__call__``'s."""
+    g, jac = self._eval(x, True)
+    if self.mix_W is None:
+      return g, jac
+    return self._mixed_values(g), torch.einsum('il,sld->sid', self.mix_W, jac.to(DEFAULT_FLOAT)).to(self.dtype)
+
+
 def generate_paths(model: SVGP, num_samples: int, num_bases: int = 1024, dtype=torch.float32,
                    device="cuda", generator: Optional[torch.Generator] = None) -> Paths:
   """Draw S decoupled sample paths of an SVGP: random-Fourier prior + inducing-point update
@@ -516,12 +637,27 @@ class PolicyRollout:
 
   Paths of a Matern drift (``paths.kernel`` 1 or 2) run the one forward entry ``mm_pathwise_policy_rollout_kern`` for every shape --
   one action included -- with the ``_wide`` signatures, tape and reverse sweeps (mixed paths: the ``_mixed`` ones): ``wide`` and
-  ``nd_entries`` are then ignored and ``g_policy`` has the ``_nd`` shape.  The policy stays SquaredExponential."""
+  ``nd_entries`` are then ignored and ``g_policy`` has the ``_nd`` shape.  The policy stays SquaredExponential.
 
-  def __init__(self, paths: Paths, policy, nx: int, active_dims, head_scale, head_shift,
+  A ``MeanDrift`` in place of ``paths`` (a mean-only drift: every sample steps with the posterior mean) runs the one forward entry
+  ``mm_pathwise_policy_rollout_mean`` under the same rules as a Matern drift -- the ``_wide`` / ``_mixed`` tape and sweeps, the
+  ``_nd`` shape of ``g_policy``, any family, with or without mixing.  It has no sample axis: ``num_samples`` (the rows of the x0
+  this rollout will be called with) is then required."""
+
+  def __init__(self, paths, policy, nx: int, active_dims, head_scale, head_shift,
                target: Optional[torch.Tensor] = None, precis: Optional[torch.Tensor] = None, nd_entries: Optional[bool] = None,
-               wide: bool = False):
-    S, L, Mp, Kp, d = paths._dims()
+               wide: bool = False, num_samples: Optional[int] = None):
+    self.mean = isinstance(paths, MeanDrift)
+    if self.mean:
+      if num_samples is None or int(num_samples) < 1:
+        raise ValueError("a MeanDrift has no sample axis: pass num_samples (the rows of x0)")
+      (L, Mp, d), S = paths._dims(), int(num_samples)
+      wide, nd_entries = True, True
+    else:
+      S, L, Mp, Kp, d = paths._dims()
+      if num_samples is not None and int(num_samples) != S:
+        raise ValueError(f"num_samples = {num_samples}, but the paths hold {S} samples")
+    self.S = int(S)
     self.paths, self.policy = paths, policy
     self.nx, self.active = int(nx), tuple(int(i) for i in active_dims)
     self.na = len(self.active)
@@ -573,7 +709,7 @@ class PolicyRollout:
       self._scale_c, self._shift_c = (_lib.C.c_double * self.nu)(*scales), (_lib.C.c_double * self.nu)(*shifts)
     else:
       self.scale, self.shift = scales[0], shifts[0]
-    dev = paths.wb.device
+    dev = paths.zs.device
     self.target = (torch.zeros(self.ne, dtype=paths.dtype, device=dev) if target is None else
                    target.to(dtype=paths.dtype, device=dev).contiguous())
     self.precis = (torch.zeros(self.ne, self.ne, dtype=paths.dtype, device=dev) if precis is None else
@@ -593,13 +729,13 @@ class PolicyRollout:
   def supports_backward(self) -> bool:
     """False where the reverse sweep's per-workgroup LDS (the nu policy blocks + four gradient slabs) exceeds 160 KiB."""
     query = getattr(_lib.lib(), f"mm_pathwise_backward_scratch_bytes_{self._sfx}")
-    return query(self.paths.num_samples, self.policy.M, self.ne, self.nu) > 0
+    return query(self.S, self.policy.M, self.ne, self.nu) > 0
 
   def __call__(self, x0: torch.Tensor, num_steps: int, dt: float = 1.0, with_jacobians: bool = False, policy=None):
     pol = self._policy(policy)
     P = self.paths
-    S, L, Mp, Kp, d = P._dims()
-    _require_device(x0, P.wb)
+    S, Mp = self.S, P.zs.shape[-1]
+    _require_device(x0, P.zs)
     if x0.shape != (S, self.nx) or x0.dtype != P.dtype:
       raise ValueError(f"expected x0 [{S},{self.nx}] of {P.dtype}, got {tuple(x0.shape)} {x0.dtype}")
     H, code = int(num_steps), _dtype_code(P.dtype)
@@ -618,16 +754,23 @@ class PolicyRollout:
     # the one-action entry takes no action count and its head constants by value; the others the count and one array each
     mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
     if self.nd_entries:
-      entry = "mm_pathwise_policy_rollout_" + ("kern" if self.kernel else "mixed" if self.mixed else self._sfx)
-      if self.kernel:
+      entry = "mm_pathwise_policy_rollout_" + ("mean" if self.mean else "kern" if self.kernel else
+                                               "mixed" if self.mixed else self._sfx)
+      if self.kernel or self.mean:
         mixing = (mixing or (0, None, None)) + (self.kernel,)
       nu, head = (self.nu,), (self._scale_c, self._shift_c)
     else:
       entry, nu, head = "mm_pathwise_policy_rollout", (), (self.scale, self.shift)
-    rc = getattr(lib, entry)(S, Mp, Kp, code, H, float(dt), self.nx, self.na, self._act, *nu,
-                             P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(),
-                             P.lengthscales.data_ptr(), P.prior_scale.data_ptr(), P.variance.data_ptr(),
-                             _ptr(P.mean_c), P.wb.data_ptr(), pol.buf.data_ptr(), pol.nbytes, pol.M,
+    if self.mean:                                              # shared weights: no K, no prior half, beta in the stream's place
+      sizes = (S, Mp)
+      drift = (P.zs.data_ptr(), P.hz.data_ptr(), P.lengthscales.data_ptr(), P.variance.data_ptr(), _ptr(P.mean_c),
+               P.beta.data_ptr())
+    else:
+      sizes = (S, Mp, P.omega.shape[-1])
+      drift = (P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(), P.lengthscales.data_ptr(),
+               P.prior_scale.data_ptr(), P.variance.data_ptr(), _ptr(P.mean_c), P.wb.data_ptr())
+    rc = getattr(lib, entry)(*sizes, code, H, float(dt), self.nx, self.na, self._act, *nu, *drift,
+                             pol.buf.data_ptr(), pol.nbytes, pol.M,
                              *head, self.target.data_ptr(), self.precis.data_ptr(),
                              x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
                              int(with_jacobians), _stream(x0.device), *mixing)
@@ -636,7 +779,7 @@ class PolicyRollout:
 
   def states(self, tape: torch.Tensor, num_steps: int) -> torch.Tensor:
     """x_0 .. x_H [H + 1, S, nx] (a view of the tape)."""
-    S = self.paths.num_samples
+    S = self.S
     es = 8 if self.paths.dtype == torch.float64 else 4
     n = (num_steps + 1) * S * self.nx
     return tape[:n * es].view(self.paths.dtype).view(num_steps + 1, S, self.nx)
@@ -651,7 +794,7 @@ class PolicyRollout:
     ``_seeded`` entries; ``g_cost`` may then be None (the built-in cost is not part of the loss).  Without ``g_states``: the
     unseeded entries."""
     pol = self._policy(policy)
-    S, H = self.paths.num_samples, int(num_steps)
+    S, H = self.S, int(num_steps)
     if g_cost is None and g_states is None:
       raise ValueError("g_cost may be None only when g_states is given")
     if g_cost is not None:
@@ -669,7 +812,7 @@ class PolicyRollout:
     """One reverse sweep: the unseeded entry of this rollout's family (one action, ``_nd``, ``_wide``), or -- ``seeded`` -- its
     ``_seeded`` sibling, which takes ``g_x`` after ``g_cost`` (either may be None -> NULL).  g_cost [H, S], g_states [H, S, nx]:
     contiguous f64.  Mixed paths: the one ``_mixed`` entry, which has the seeded signature."""
-    S, code, dev = self.paths.num_samples, _dtype_code(self.paths.dtype), tape.device
+    S, code, dev = self.S, _dtype_code(self.paths.dtype), tape.device
     npar = pol.M * self.ne + pol.M + self.ne + 2
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
     seeded = seeded or self.mixed

@@ -675,6 +675,36 @@ int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, int H, doubl
                                     void* tape, size_t tape_bytes, int with_jacobians, void* stream,
                                     int Lg, const double* mix_W, const double* mix_c, int kernel);
 
+/* ---- a MEAN-ONLY drift: shared weights instead of a stream (csrc/mm_pathwise_mean.hip) --------------------------------------
+ * The reference's build_dynamics(..., model_uncertainty=False) wraps the drift in a KernelRegressor: under the Euler solver the
+ * drift of EVERY sample is then the posterior mean K(x, Z) Kuu^-1 u + c, and the sample paths are never read.  That function has
+ * no per-sample weights: with beta [L][M] f64 = Kuu^-1 u (zero on padded centres, which then add exactly 0),
+ *   f[s][a]    = variance[a] sum_m beta[a][m] e_m + mean_c[a]                  (e_m, g_m): the family's basis value and slope at
+ *   J[s][a][k] = ln2 variance[a] sum_m beta[a][m] g_m (zs_t[a][k][m] x_scale[a][k] - x_scale[a][k]^2 x[s][k])    zs_t . xs - hz - hx
+ * -- the update half of mm_pathwise_eval_jac_kern with v[s][a][m] = beta[a][m] for every s.  x [S][d], zs_t [L][d][M], hz [L][M]
+ * of dtype; x_scale [L][d], variance [L], mean_c [L] (or NULL), beta [L][M] f64; kernel as in the _kern entries.  M is any
+ * positive number (no block size: nothing is streamed), d <= 16 (MM_E_DIM beyond).  Nothing of size S M is read or written: a
+ * latent's operands go through LDS in chunks and serve every sample of the workgroup.  Values accumulate in f64 in both modes, the
+ * partial sums of a sample are added in a fixed order: bitwise reproducible.
+ *
+ * mm_pathwise_mean_eval: f_out [S][L] and, jac_out != NULL, jac_out [S][L][d] (the layouts of mm_pathwise_eval_jac).
+ * mm_pathwise_policy_rollout_mean: mm_pathwise_policy_rollout_kern with the mean in place of the paths -- its argument list without
+ * (K, omega_t, phase, prior_scale, wb) and with beta after mean_c; nd <= 16, 1 <= nu <= 4, Lg / mix_W / mix_c as there (0 / NULL:
+ * no mixing; beta is then [nx][M], else [Lg][M]).  The tape is that of mm_pathwise_tape_bytes_nd resp. _mixed and the gradients
+ * come from mm_pathwise_policy_rollout_backward_wide[_seeded] resp. _backward_mixed, as they are.
+ * Both validate before any HIP call and return the codes above (MM_E_ARG: a size <= 0, a missing pointer, an unknown kernel). */
+int mm_pathwise_mean_eval(int S, int L, int M, int d, int dtype,
+                          const void* x, const void* zs_t, const void* hz, const double* x_scale, const double* variance,
+                          const double* mean_c, const double* beta, void* f_out, void* jac_out, void* stream, int kernel);
+int mm_pathwise_policy_rollout_mean(int S, int M, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                    int nu, const void* zs_t, const void* hz, const double* x_scale, const double* variance,
+                                    const double* mean_c, const double* beta,
+                                    const void* policy_packed, size_t policy_bytes, int policy_M,
+                                    const double* head_scale, const double* head_shift,
+                                    const void* target, const void* precis, const void* x0, void* cost,
+                                    void* tape, size_t tape_bytes, int with_jacobians, void* stream,
+                                    int Lg, const double* mix_W, const double* mix_c, int kernel);
+
 /* ---- path GENERATION: the two reformatting steps of a draw (csrc/mm_pathwise_sample.hip) -----------------------------------
  * PathwisePILCO draws new paths on every optimiser step (loops/pilco.py:281-284).  Between the random draws, two GEMMs and two
  * triangular solves (the caller's: pathwise.PathSampler keeps them on torch's BLAS with a cached Kuu factor) a draw is
