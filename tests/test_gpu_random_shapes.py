@@ -3,7 +3,10 @@
 Complements the hand-picked cases of test_gpu_parity.py: every draw combines a shape (L, M, d, B -- M and B not
 multiples of anything, d on both sides of the d <= 8 / d > 8 kernel families), a dtype, the two flags of the handler
 (full_output_cov, model_uncertainty), whitening, a Constant mean, an optional LinearCoregionalization mixing and an
-input width.  Tolerances as in test_gpu_parity.py (max abs error / max abs value per tensor)."""
+input width.  Tolerances as in test_gpu_parity.py (max abs error / max abs value per tensor).
+
+Beside the seeded list, fixed draws with MANY latents on wide inputs (``WIDE``: the drift shapes of the wide composed rollouts,
+tests/test_gpu_compose_wide.py -- the seeded list reaches d = 17 with L <= 4 only), and one closed rollout at L = d = 12."""
 import dataclasses
 
 import numpy as np
@@ -49,8 +52,26 @@ def _draws(n):
 DRAWS = _draws(24)
 
 
-@pytest.mark.parametrize("c", DRAWS, ids=[f"{i}-L{c['L']}M{c['M']}d{c['d']}B{c['B']}{'f32' if c['f32'] else 'f64'}" for i, c in enumerate(DRAWS)])
+def _ids(draws):
+  return [f"{i}-L{c['L']}M{c['M']}d{c['d']}B{c['B']}{'f32' if c['f32'] else 'f64'}" for i, c in enumerate(draws)]
+
+
+# (L, M, d, B): 136 and 78 pairs on the d > 8 kernel families, full covariance, with model uncertainty, both dtypes
+WIDE = [dict(seed=2000 + i, L=L, M=M, d=d, B=B, f32=f32, full=True, unc=True, whiten=True, mean=True, mix=False, scale=0.1)
+        for i, (L, M, d, B) in enumerate([(16, 40, 25, 3), (12, 40, 17, 2)]) for f32 in (False, True)]
+
+
+@pytest.mark.parametrize("c", DRAWS, ids=_ids(DRAWS))
 def test_random_shape_and_flags(c, device):
+  _check_draw(c, device)
+
+
+@pytest.mark.parametrize("c", WIDE, ids=_ids(WIDE))
+def test_many_latents_on_wide_inputs(c, device):
+  _check_draw(c, device)
+
+
+def _check_draw(c, device):
   dtype = torch.float32 if c["f32"] else torch.float64
   # lengthscales grow with d so that the kernel expectations stay away from underflow (tests/test_kernel_expectation.py:61-62)
   # (and short in one or two dimensions, where long lengthscales make Kuu numerically rank-deficient)
@@ -75,3 +96,28 @@ def test_random_shape_and_flags(c, device):
   cov = cov.diag_part() if not c["full"] else cov
   errs = dict(f1=scale_err(m.y.mean(), f1o), Sff=scale_err(cov, Sffo), cross=scale_err(m.cross[0], cro))
   assert all(errs[k] < tol[k] for k in tol), (c, errs)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+def test_closed_rollout_at_twelve_dims(dtype, device):
+  """``ops.rollout_closed`` at L = d = 12 (M = 40, B = 3, H = 3) against ``mo.rollout_closed``, bars of
+  tests/test_gpu_parity.py::test_euler_and_rollout: k_euler's loops over d * d = 144 entries make three trips (every other test
+  of it has d * d <= 64)."""
+  from gpflowpilco_amd import ops
+  from gpflowpilco_amd.synthetic import make_inputs, make_svgp
+  from tests.helpers import oracle_params
+  L = d = 12
+  H, B = 3, 3
+  lo = 0.5 * np.sqrt(d / 4.0)
+  syn = make_svgp(L, 40, d, seed=2100, ls_bounds=(lo, 3.0 * lo))
+  mu, Sigma = make_inputs(B, d, seed=2101, scale=0.1, lo=0.3, hi=0.7)
+  _, _, traj = mo.rollout_closed(mu, Sigma, oracle_params(syn), H, dt=1.0, keep=True)
+  assert min(np.linalg.eigvalsh(S).min() for _, S in traj) > 1e-4 and max(np.abs(m).max() for m, _ in traj) < 2.0
+  pm = syn.to_model(device).packed(dtype, True, device)
+  m1, S1, tmu, tS = ops.rollout_closed(pm, to_dev(mu, device, dtype), to_dev(Sigma, device, dtype), H, dt=1.0, keep_trajectory=True)
+  pm.check_status(B)
+  tol = 1e-6 if dtype == torch.float64 else 2e-5
+  errs = [max(scale_err(tmu[h], traj[h][0]), scale_err(tS[h], traj[h][1])) for h in range(H)]
+  print(f"closed rollout L = d = 12 {dtype}: worst error per step {errs}")
+  assert max(errs) < tol, errs
+  assert torch.equal(m1, tmu[-1]) and torch.equal(S1, tS[-1])
