@@ -204,6 +204,22 @@ def _composed_rollout_signatures():
 
 SIGNATURES.update(_composed_rollout_signatures())
 
+
+def _compose_wide_signatures():
+  """The reverse sweep for 8 < ne <= 16 (``mm_compose_wide_backward*``): the argument lists of the ``_nd`` sweeps of the same role,
+  the mixed ones with mix_W appended; their two size queries; and the switch between their dense paths."""
+  nd, seeded = (SIGNATURES[f"mm_rollout_composed_backward_nd{s}"][1] for s in ("", "_seeded"))
+  return {"mm_compose_wide_backward": (C.c_int, list(nd)),
+          "mm_compose_wide_backward_seeded": (C.c_int, list(seeded)),
+          "mm_compose_wide_backward_mixed": (C.c_int, list(nd) + [C.c_void_p]),
+          "mm_compose_wide_backward_mixed_seeded": (C.c_int, list(seeded) + [C.c_void_p]),
+          "mm_compose_backward_workspace_bytes_wide": (C.c_size_t, [C.c_int] * 6),
+          "mm_compose_backward_workspace_bytes_wide_mixed": (C.c_size_t, [C.c_int] * 7),
+          "mm_compose_wide_dense_path": (C.c_int, [C.c_int])}
+
+
+SIGNATURES.update(_compose_wide_signatures())
+
 _lib = None
 
 

@@ -419,12 +419,13 @@ def moment_match_torch(mu, Sigma, Z, ls, var, beta, C=None, mean_c=None, full_ou
 
 def _taped_composed_rollout(ctx, mx, Sxx, Z, ls, var, beta, mean_c, roll, num_steps, dt):
   """The forward of the two autograd functions below: pack the policy from its packed coordinates, run the taped rollout of
-  ``roll``'s family (``roll.uses_nd``: the ``_nd`` / ``_nd_mixed`` entries), keep what the backward needs on ``ctx``.
+  ``roll``'s family (``roll.uses_nd``: the ``_nd`` / ``_nd_mixed`` entries; ``roll.use_wide``: the same tapes for the wide reverse
+  sweep, 8 < ne <= 16), keep what the backward needs on ``ctx``.
   -> (cost [H, B], tape)."""
   f64 = torch.float64
   det = lambda t: t.detach().to(f64)
   pol = ops.pack_model(det(Z), det(ls), det(var), det(beta), None, det(mean_c), dtype=f64, sync=False)
-  taped = roll.taped_nd if roll.uses_nd else roll.taped
+  taped = roll.taped_wide if roll.use_wide else roll.taped_nd if roll.uses_nd else roll.taped
   m_H, S_H, cost, tape = taped(mx.detach(), Sxx.detach(), num_steps, dt=dt, policy=pol)
   ctx.roll, ctx.pol, ctx.tape, ctx.H, ctx.dt, ctx.B = roll, pol, tape, int(num_steps), float(dt), mx.shape[0]
   ctx.save_for_backward(ls)
@@ -437,7 +438,7 @@ def _composed_rollout_gradients(ctx, g_cost, seeds=None):
   """The backward of the two autograd functions below: one reverse sweep (``seeds = (g_xm [H,B,nx], g_xS [H,B,nx,nx])``: the seeded
   one), its packed gradient summed over the batch and split per input."""
   (ls,) = ctx.saved_tensors
-  sweep = ctx.roll.backward_nd if ctx.roll.uses_nd else ctx.roll.backward
+  sweep = ctx.roll.backward_wide if ctx.roll.use_wide else ctx.roll.backward_nd if ctx.roll.uses_nd else ctx.roll.backward
   g_pol, g_m, g_S = sweep(ctx.tape, g_cost.T.contiguous(), ctx.B, ctx.H, dt=ctx.dt, policy=ctx.pol,
                           want_state_grad=ctx.need_state, g_traj=seeds)
   nu, M, d = ctx.pol.L, ctx.pol.M, ctx.pol.d
@@ -456,7 +457,8 @@ class ComposedRolloutFunction(torch.autograd.Function):
   backward = ``mm_rollout_composed_backward`` (csrc/mm_compose_bwd.hip) -- the native counterpart of differentiating
   ``policy_loss_closure`` with a gradient tape (gpflow_pilco/utils/optimizers.py:51-56, loops/pilco.py:192-220).  A rollout of the
   ``_nd`` family (``roll.uses_nd``: 2 to 4 actions, or a coregionalised drift) takes ``mm_rollout_composed_taped_nd`` /
-  ``mm_rollout_composed_backward_nd`` (csrc/mm_compose_bwd_nd.hip) or their ``_nd_mixed`` forms.
+  ``mm_rollout_composed_backward_nd`` (csrc/mm_compose_bwd_nd.hip) or their ``_nd_mixed`` forms; one marked ``roll.use_wide``
+  (``loops.policy_loss_closure(native_wide=True)``, 8 < ne <= 16) the same tapes and ``mm_compose_wide_backward*``.
 
   Inputs: the initial state (mx [B,nx], Sxx [B,nx,nx]) and the policy in PACKED coordinates with a leading latent axis -- Z [nu,M,d],
   lengthscales [nu,d], variance [nu], beta = Kuu^-1 u [nu,M], mean_c [nu] -- which the caller computes from the trainable

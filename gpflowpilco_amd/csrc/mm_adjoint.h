@@ -279,6 +279,154 @@ __device__ inline double mma_solve_pivot(MMADevCtx c, double* Aug, int n, int nr
   c.sync();
   return det;
 }
+
+// ---- device fast paths for 8 < n <= 16: FOUR matrix entries per lane of ONE wave, broadcasts by wave shuffles ------------------
+// Entry (i, j) of a 16 x 16 matrix sits in register i >> 2 of lane 16 (i & 3) + j: a lane holds column j of the rows
+// q, q + 4, q + 8, q + 12 (q = lane >> 4).  With the step index k unrolled the register that holds row k is known at compile time.
+// Only the kernels of the wide reverse sweep (mm_compose_bwd_nd.hip, the _wide entries; k_gp_bwd_items as that sweep launches it)
+// instantiate MMAWideCtx<true>: the other device kernels reach n = 9..12 in the drift's chain rule and keep the generic code above, bit for bit.  MMAWideCtx<false> is the
+// same kernels on the generic code (mm_compose_wide_dense_path: the measurement in DESIGN.md section 8 f-2).
+template <bool Fast>
+struct MMAWideCtx : MMADevCtx {};
+
+// Gauss-Jordan inverse of an SPD matrix held in a[4] (identity outside d x d); the inverse in a[4], log det returned
+__device__ inline double mma_gj_spd16(double (&a)[4], int d, bool* ok) {
+  const int lane = (int)(threadIdx.x & 63u), q = lane >> 4, j = lane & 15;
+  double pk = 1.0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (k < d) {
+      const double rk = __shfl(a[k >> 2], 16 * (k & 3) + j, 64);      // row k, column j
+      const double p = __shfl(rk, k, 64);
+      if (!(p > 0.0)) *ok = false;
+      if (lane == k) pk = p;
+      const double ip = 1.0 / p;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = q + 4 * r;
+        const double ci = __shfl(a[r], 16 * q + k, 64);               // row i, column k
+        if (i == k) a[r] = (j == k) ? ip : rk * ip;
+        else a[r] = (j == k) ? -ci * ip : fma(-ci * ip, rk, a[r]);
+      }
+    }
+  }
+  double ld = lane < d ? log(pk) : 0.0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ld += __shfl_xor(ld, off, 64);
+  return ld;
+}
+
+// whole workgroup: wave 0 does the work, the log-determinant reaches every lane through Y[0].  The inverse is symmetrised through
+// A itself (one round trip of wave 0 through LDS: the transposed entry sits in another register of another lane).
+// d <= 8: the path of MMADevCtx; d > 16 (the drift's match at nd = 17..20), or Fast == false: the generic code.
+template <bool Fast>
+__device__ inline double mma_spd_inverse(MMAWideCtx<Fast> c, double* A, double* Y, int d, int dp, bool* ok) {
+  if (d <= 8) return mma_spd_inverse(static_cast<MMADevCtx>(c), A, Y, d, dp, ok);
+  if (!Fast || d > 16) return mma_spd_inverse<MMADevCtx>(c, A, Y, d, dp, ok);
+  c.sync();
+  if (c.group() == 0) {
+    const MMAWaveCtx w;
+    const int lane = c.lane(), q = lane >> 4, j = lane & 15;
+    double a[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = q + 4 * r;
+      a[r] = (i < d && j < d) ? A[i * dp + j] : (i == j ? 1.0 : 0.0);
+    }
+    bool okw = true;
+    const double ld = mma_gj_spd16(a, d, &okw);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const int i = q + 4 * r; if (i < d && j < d) A[i * dp + j] = a[r]; }
+    w.sync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const int i = q + 4 * r; if (i < d && j < d) a[r] = 0.5 * (a[r] + A[j * dp + i]); }
+    w.sync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const int i = q + 4 * r; if (i < d && j < d) A[i * dp + j] = a[r]; }
+    if (lane == 0) { Y[0] = ld; Y[1] = okw ? 1.0 : 0.0; }
+  }
+  c.sync();
+  const double ld = Y[0];
+  if (Y[1] == 0.0) *ok = false;
+  c.sync();
+  return ld;
+}
+
+// A X = R, 8 < max(n, nr) <= 16, partial pivoting: wave 0, four entries of A and four of R per lane.  The pivot of step k is the
+// FIRST largest |entry| of column k in rows k .. n - 1 (the generic code's strict >): each group of 16 lanes scans its own rows in
+// ascending order, the four groups are combined with ties going to the smaller row, and lane 0's choice is the wave's.
+template <bool Fast>
+__device__ inline double mma_solve_pivot(MMAWideCtx<Fast> c, double* Aug, int n, int nr, int ld) {
+  if (n <= 8 && nr <= 8) return mma_solve_pivot(static_cast<MMADevCtx>(c), Aug, n, nr, ld);
+  if (!Fast || n > 16 || nr > 16) return mma_solve_pivot<MMADevCtx>(c, Aug, n, nr, ld);
+  c.sync();
+  if (c.group() == 0) {
+    const int lane = c.lane(), q = lane >> 4, j = lane & 15;
+    double a[4], b[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = q + 4 * r;
+      a[r] = (i < n && j < n) ? Aug[i * ld + j] : (i == j ? 1.0 : 0.0);
+      b[r] = (i < n && j < nr) ? Aug[i * ld + n + j] : 0.0;
+    }
+    double det = 1.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      if (k < n) {
+        double cv[4];                                        // column k of this group's rows
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cv[r] = __shfl(a[r], 16 * q + k, 64);
+        double best = -1.0;
+        int p = 16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = q + 4 * r;
+          const double v = fabs(cv[r]);
+          if (i >= k && i < n && v > best) { best = v; p = i; }
+        }
+#pragma unroll
+        for (int off = 16; off <= 32; off <<= 1) {
+          const double ob = __shfl_xor(best, off, 64);
+          const int op = __shfl_xor(p, off, 64);
+          if (ob > best || (ob == best && op < p)) { best = ob; p = op; }
+        }
+        p = __shfl(p, 0, 64);
+        if (p > 15) p = k;                                   // (no comparable entry: a column of NaNs)
+        // row p, column j -- after the exchange row k
+        const int rp = p >> 2;
+        const double pa = rp == 0 ? a[0] : (rp == 1 ? a[1] : (rp == 2 ? a[2] : a[3]));
+        const double pb = rp == 0 ? b[0] : (rp == 1 ? b[1] : (rp == 2 ? b[2] : b[3]));
+        const double rk = __shfl(pa, 16 * (p & 3) + j, 64), bk = __shfl(pb, 16 * (p & 3) + j, 64);
+        const double akk = __shfl(cv[k >> 2], 16 * (k & 3), 64);   // the entry (k, k) before the exchange
+        if (p != k) {
+          const double ra = __shfl(a[k >> 2], 16 * (k & 3) + j, 64), rb = __shfl(b[k >> 2], 16 * (k & 3) + j, 64);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = q + 4 * r;
+            if (i == k) { a[r] = rk; b[r] = bk; }
+            else if (i == p) { a[r] = ra; b[r] = rb; cv[r] = akk; }
+          }
+          det = -det;
+        }
+        const double piv = __shfl(rk, k, 64), ip = 1.0 / piv;
+        det *= piv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = q + 4 * r;
+          if (i == k) { a[r] = rk * ip; b[r] = bk * ip; }
+          else { a[r] = fma(-cv[r] * ip, rk, a[r]); b[r] = fma(-cv[r] * ip, bk, b[r]); }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const int i = q + 4 * r; if (i < n && j < nr) Aug[i * ld + n + j] = b[r]; }
+    if (lane == 0) Aug[0] = det;                            // (the eliminated left block is not read again: carries det)
+  }
+  c.sync();
+  const double det = Aug[0];
+  c.sync();
+  return det;
+}
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------

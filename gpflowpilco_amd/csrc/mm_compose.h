@@ -205,7 +205,8 @@ int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L
                                   const void* g_f1, const void* g_Sff, const void* g_cross,
                                   void* g_mu, void* g_Sigma, int accumulate_Sigma,
                                   void* workspace, size_t workspace_bytes, void* bwd_ws, size_t bwd_ws_bytes,
-                                  int32_t* status, void* stream, bool workspace_is_current, bool skip_sum, int mode, bool verify_sums);
+                                  int32_t* status, void* stream, bool workspace_is_current, bool skip_sum, int mode, bool verify_sums,
+                                  bool wide_dense);
 // byte offset, inside the backward buffer of a match, of its (latent | pair) items [B][L + P][d^2 + d] (skip_sum: the consumer sums them)
 size_t mm_gp_bwd_items_offset(int B, int L, int M, int d, int dtype, int flags);
 

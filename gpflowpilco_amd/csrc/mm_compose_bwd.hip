@@ -51,6 +51,9 @@ extern "C" void mm_stage_profile_set_bwd(void* device_buffer) {
 // ---------------------------------------------------------------------------------------------------------------------
 // grid (L + P, B), 256 threads.  items [B][L + P][d^2 + d]; cbuf [B][L][Mp].
 // col [B][col_pairs][3 + d][Mp]: col_pairs = P, or L with pagg [B][Po][mma_pair_agg_len(d)] for the off-diagonal pairs.
+// Ctx: MMADevCtx, or -- the wide reverse sweep of mm_compose_bwd_nd.hip alone -- MMAWideCtx<true>: the pair items' inverse at
+// 8 < d <= 16 on the one-wave path of mm_adjoint.h
+template <class Ctx>
 __global__ __launch_bounds__(256) void k_gp_bwd_items(int L, int M, int Mp, int d, int P, int with_unc, int full_cov,
                                                       const double* __restrict__ Z, const double* __restrict__ ls2,
                                                       const double* __restrict__ mu, const double* __restrict__ Sigma,
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256) void k_gp_bwd_items(int L, int M, int Mp, int 
   const int item = blockIdx.x, b = blockIdx.y, Po = P - L, nsff = full_cov ? L * L : L;
   bool ok = true;
   double* out = items + ((size_t)b * (L + P) + item) * (d * d + d);
-  mma_gp_item_bwd(MMADevCtx(), item, L, M, Mp, d, P, with_unc != 0, Z, ls2, mu + (size_t)b * d, Sigma + (size_t)b * d * d,
+  mma_gp_item_bwd(Ctx(), item, L, M, Mp, d, P, with_unc != 0, Z, ls2, mu + (size_t)b * d, Sigma + (size_t)b * d * d,
                   latmat + (size_t)b * L * (2 * d * d + 2), w + (size_t)b * L * Mp, q + (size_t)b * L * Mp,
                   col + (size_t)b * col_pairs * (3 + d) * Mp, row + (size_t)b * Po * 2 * Mp, g_f1 + (size_t)b * L,
                   g_Sff + (size_t)b * nsff, full_cov, g_cross + (size_t)b * d * L, out, out + d * d,
@@ -205,7 +208,8 @@ int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L
                                   void* g_mu, void* g_Sigma, int accumulate_Sigma,
                                   void* workspace, size_t workspace_bytes, void* bwd_ws, size_t bwd_ws_bytes,
                                   int32_t* status, void* stream, bool workspace_is_current, bool skip_sum = false,
-                                  int mode = MMB_MODE_ALL, bool verify_sums = true /* check the caller's MM_*_CURRENT promises on the device */) {
+                                  int mode = MMB_MODE_ALL, bool verify_sums = true /* check the caller's MM_*_CURRENT promises on the device */,
+                                  bool wide_dense = false /* the items kernel with MMAWideCtx<true> (the wide reverse sweep) */) {
   // mode: MMB_MODE_ALL = sweeps + chain rule; MMB_MODE_SWEEPS = everything that does NOT depend on the incoming gradient (the two
   // M x M sweeps, the full moment GEMM, the pair aggregates: mm_moment_match_with_sums leaves them on bwd_ws);
   // MMB_MODE_CHAIN = the chain rule alone on sums a MMB_MODE_SWEEPS call left on bwd_ws (MM_SUMS_CURRENT)
@@ -317,8 +321,9 @@ int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L
   const double* row = col + (size_t)B * P * (3 + d) * Mp;       // (f64 packs; not read with aggregates)
   const size_t shm = (size_t)mma_gp_item_scratch(d, 256) * sizeof(double);
   if (shm > 160 * 1024) return MM_E_DIM;
+  auto k_items = wide_dense ? k_gp_bwd_items<MMAWideCtx<true>> : k_gp_bwd_items<MMADevCtx>;
   if (shm > 64 * 1024) {                                   // d >= 20: more than the default dynamic LDS limit
-    hipError_t ea = hipFuncSetAttribute((const void*)k_gp_bwd_items, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    hipError_t ea = hipFuncSetAttribute((const void*)k_items, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (ea != hipSuccess) return (int)ea;
   }
   const int chunk = mm_gp_moment_chunk(M, d), nchunk = chunk ? (M + chunk - 1) / chunk : 0;
@@ -334,7 +339,7 @@ int mm_moment_match_backward_impl(const void* packed, size_t packed_bytes, int L
     MMB_CHECK();
     pre = (const double*)(bw + bl.pre);
   }
-  hipLaunchKernelGGL(k_gp_bwd_items, dim3(L + P, B), dim3(256), shm, s, L, M, Mp, d, P, with_unc ? 1 : 0,
+  hipLaunchKernelGGL(k_items, dim3(L + P, B), dim3(256), shm, s, L, M, Mp, d, P, with_unc ? 1 : 0,
                      (flags & MM_FULL_OUTPUT_COV) ? 1 : 0, (const double*)(pk + ml.Z64), (const double*)(pk + ml.ls2),
                      mu64, S64, (const double*)(ws + wl.latmat), (const double*)(ws + wl.w64),
                      (const double*)(ws + wl.q64), col, row, col_pairs, pagg, (const double*)(ws + wl.f1raw),

@@ -62,6 +62,8 @@ static inline MMCarryLayoutND mm_carry_layout_nd(int B, int nx, int na, int nu) 
 }
 
 // k_compose_tail_bwd_nd: grid B, 64 threads; k_compose_tail_bwd with nu policy columns (cp, ccp [B][ne][nu]).
+// Ctx: MMADevCtx (the _nd entries) or MMAWideCtx (the _wide entries: the dense paths for 8 < n <= 16 of mm_adjoint.h).
+template <class Ctx>
 __global__ __launch_bounds__(64) void k_compose_tail_bwd_nd(MMComposeDims D, double dt, int first, const double* __restrict__ x1m,
                                                             const double* __restrict__ x1S, const double* __restrict__ me1,
                                                             const double* __restrict__ See1, const double* __restrict__ target,
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd_nd(MMComposeDims D, dou
   extern __shared__ double sm[];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nx = D.nx, ne = D.ne, nd = D.nd, nu = nd - ne;
-  MMADevCtx c;
+  Ctx c;
   double* gme = sm; double* gSee = gme + ne; double* gSxe = gSee + ne * ne; double* gm1 = gSxe + nx * ne; double* gS1 = gm1 + nx;
   double* wk = gS1 + nx * nx;
   cm += (size_t)b * nx; cS += (size_t)b * nx * nx; cme += (size_t)b * ne; cSee += (size_t)b * ne * ne; cSxe += (size_t)b * nx * ne;
@@ -108,6 +110,7 @@ static inline size_t mm_tail_bwd_nd_lds(int nx, int ne, int nd) {
 // k_policy_head_bwd_nd: grid B, 256 threads.  Sums the drift match's (latent | pair) items [B][nitems][nd^2 + nd] onto the
 // bookkeeping's part cSdd; writes cme, cSee (the adjoint of the encoding of x_h through the policy and the joint); accumulates the
 // packed policy's gradient into gpar [B][nu][mm_policy_grad_len(M, ne)], latent by latent.
+template <class Ctx>
 __global__ __launch_bounds__(256) void k_policy_head_bwd_nd(int M, int ne, int nu, MMHeadND hd, const double* __restrict__ Z,
                                                             const double* __restrict__ beta, const double* __restrict__ ls2,
                                                             const double* __restrict__ var, const double* __restrict__ me,
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(256) void k_policy_head_bwd_nd(int M, int ne, int n
                                                             const double* __restrict__ items, int nitems) {
   extern __shared__ double sm[];
   const int b = blockIdx.x, nd = ne + nu;
-  MMADevCtx c;
+  Ctx c;
   double* gme = sm; double* gSee = gme + ne; double* gpc = gSee + ne * ne; double* gmu = gpc + ne * nu; double* gSig = gmu + ne;
   double* gpf1 = gSig + ne * ne; double* gpS = gpf1 + nu; double* hsc = gpS + nu * nu;      // head constants: scale, shift [nu] each
   double* hw = hsc + 2 * nu;                                                               // head scratch
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(256) void k_policy_head_bwd_nd(int M, int ne, int n
   mma_head_bwd_nd(c, ne, nu, hsc, hsc + nu, pf1 + (size_t)b * nu, pSff + (size_t)b * nu * nu, pcross + (size_t)b * ne * nu, Seb, dmd,
                   dSd, ccp + (size_t)b * ne * nu, gme, gSee, gpc, gpf1, gpS, hw);
   bool ok = true;
-  mma_policy_nd_bwd<MMADevCtx, 8>(c, nu, M, ne, Z, beta, ls2, var, meb, Seb, gpf1, gpS, gpc, gmu, gSig,
+  mma_policy_nd_bwd<Ctx, 8>(c, nu, M, ne, Z, beta, ls2, var, meb, Seb, gpf1, gpS, gpc, gmu, gSig,
                                   gpar + (size_t)b * nu * ((size_t)M * ne + M + ne + 2), wk, &ok);
   __syncthreads();
   for (int k = threadIdx.x; k < ne; k += 256) cme[(size_t)b * ne + k] = gme[k] + gmu[k];
@@ -161,12 +164,27 @@ static inline size_t mm_policy_bwd_nd_lds(int M, int ne, int nu) {
                   + mma_policy_nd_bwd_scratch(M, ne, 256) + 8) * sizeof(double);
 }
 
-// shapes the sweep takes (see the header comment)
-static inline bool mm_compose_bwd_nd_takes(int nx, int na, int nu, int policy_M) {
+// the _wide entries' LDS: mm_policy_bwd_nd_lds, but with one action -- no pair item runs -- without the pair item's scratch
+static inline size_t mm_policy_bwd_wide_lds(int M, int ne, int nu) {
+  if (nu > 1) return mm_policy_bwd_nd_lds(M, ne, nu);
+  const int nd = ne + nu;
+  return (size_t)(2 * ne + 2 * ne * ne + ne * nu + 3 * nu + nu * nu + mma_head_bwd_nd_scratch(ne, nu) + nd + nd * nd
+                  + mma_policy_small_bwd_scratch(M, ne, 256) + ne * ne + 2 * ne + 8) * sizeof(double);
+}
+
+// shapes the sweep takes (see the header comment): ne <= ne_max = 8 (the _nd entries) or 16 (the _wide entries)
+#define MMB_ND_NE 8
+#define MMB_WIDE_NE 16
+static inline bool mm_compose_bwd_nd_takes(int nx, int na, int nu, int policy_M, int ne_max = MMB_ND_NE) {
   if (nx <= 0 || nx > MMC_NX || na < 0 || na > MMC_NA || na > nx || nu < 1 || nu > MMC_NU || policy_M <= 0) return false;
   const int ne = nx + na;
-  if (ne + nu > MMC_ND || ne > 8 || policy_M > MM_SORT_MIN_M) return false;
-  return mm_policy_bwd_nd_lds(policy_M, ne, nu) <= MMB_ND_LDS_MAX;
+  if (ne + nu > MMC_ND || ne > ne_max || policy_M > MM_SORT_MIN_M) return false;
+  if (ne_max <= MMB_ND_NE) return mm_policy_bwd_nd_lds(policy_M, ne, nu) <= MMB_ND_LDS_MAX;
+  // (the number of sub-sweeps max(1, 256 / M) drops as M grows, so the size is not monotone in M: a policy is taken when every
+  // smaller one fits too, which makes "M <= M*" the whole rule at given (ne, nu))
+  for (int m = 1; m <= policy_M; ++m)
+    if (mm_policy_bwd_wide_lds(m, ne, nu) > MMB_ND_LDS_MAX) return false;
+  return true;
 }
 
 // the carry, then the drift match's backward buffer (used where the tape did not keep the sums of the step)
@@ -204,6 +222,9 @@ __global__ __launch_bounds__(64) void k_compose_mix_bwd_nd(int nx, int Lg, int n
               cSgg + b * Lg * Lg, ccg + b * nd * Lg, sm);
 }
 
+// which dense code the _wide entries run (0: the fast paths of mm_adjoint.h for 8 < n <= 16; 1: the generic code)
+static int g_wide_generic = 0;
+
 extern "C" size_t mm_compose_backward_workspace_bytes_nd(int B, int nx, int na, int nu, int drift_M, int policy_M) {
   if (B <= 0 || drift_M <= 0 || !mm_compose_bwd_nd_takes(nx, na, nu, policy_M)) return 0;
   return mm_compose_bwd_layout_nd(B, nx, na, nu, drift_M).total;
@@ -230,7 +251,7 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
                                                 void* g_policy, void* g_mx0, void* g_Sxx0,
                                                 void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                                 int32_t* status, void* stream, bool mixed = false,
-                                                const double* mix_W = nullptr) {
+                                                const double* mix_W = nullptr, bool wide = false) {
   if ((g_xm == nullptr) != (g_xS == nullptr)) return MM_E_ARG;
   if (mixed && !mix_W) return MM_E_ARG;
   if (!drift_packed || !policy_packed || !tape || !g_cost || !g_policy || !ws_drift || !ws_bwd || !target || !precis) return MM_E_ARG;
@@ -244,7 +265,7 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
   const int ne = D.ne, nd = D.nd;
   if (mixed && (drift_L < 1 || drift_L > nx)) return MM_E_DIM;
   if ((!mixed && drift_L != nx) || drift_d != nd || policy_d != ne) return MM_E_STATE;
-  if (!mm_compose_bwd_nd_takes(nx, na, nu, policy_M)) return MM_E_DIM;
+  if (!mm_compose_bwd_nd_takes(nx, na, nu, policy_M, wide ? MMB_WIDE_NE : MMB_ND_NE)) return MM_E_DIM;
   const int Lg = drift_L;
   const MMMixStage ms = mm_mix_stage(B, Lg, nd, 8);
   const MMTapeLayout tl = mixed ? mm_tape_layout_nd_mixed(B, H, nx, na, nu, Lg, drift_M, dtype)
@@ -271,9 +292,15 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
   const char* tp = (const char*)tape; const char* pp = (const char*)policy_packed;
   auto cr = [&](size_t off) { return (double*)(cw + off); };
   const double* xm = (const double*)(tp + tl.xm); const double* xS = (const double*)(tp + tl.xS);
-  const size_t lds_tail = mm_tail_bwd_nd_lds(nx, ne, nd), lds_pol = mm_policy_bwd_nd_lds(policy_M, ne, nu);
+  const size_t lds_tail = mm_tail_bwd_nd_lds(nx, ne, nd);
+  const size_t lds_pol = wide ? mm_policy_bwd_wide_lds(policy_M, ne, nu) : mm_policy_bwd_nd_lds(policy_M, ne, nu);
+  // the kernels of this entry's family (the wide ones on the dense fast paths, or -- mm_compose_wide_dense_path -- the generic code)
+  auto k_tail = k_compose_tail_bwd_nd<MMADevCtx>;
+  auto k_policy = k_policy_head_bwd_nd<MMADevCtx>;
+  if (wide && g_wide_generic) { k_tail = k_compose_tail_bwd_nd<MMAWideCtx<false>>; k_policy = k_policy_head_bwd_nd<MMAWideCtx<false>>; }
+  else if (wide) { k_tail = k_compose_tail_bwd_nd<MMAWideCtx<true>>; k_policy = k_policy_head_bwd_nd<MMAWideCtx<true>>; }
   if (lds_pol > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_policy_head_bwd_nd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pol);
+    hipError_t e = hipFuncSetAttribute((const void*)k_policy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pol);
     if (e != hipSuccess) return (int)e;
   }
   const size_t npar = (size_t)B * nu * mm_policy_grad_len(policy_M, ne);
@@ -288,7 +315,7 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
   const double* gdcross = mixed ? (const double*)(sg + ms.cg) : cr(kl.cdcross);
   for (int h = H - 1; h >= 0; --h) {
     const char* sl = tp + (size_t)h * tl.slot_bytes; const char* sn = tp + (size_t)(h + 1) * tl.slot_bytes;
-    hipLaunchKernelGGL(k_compose_tail_bwd_nd, dim3(B), dim3(64), lds_tail, s, D, dt, h == H - 1 ? 1 : 0,
+    hipLaunchKernelGGL(k_tail, dim3(B), dim3(64), lds_tail, s, D, dt, h == H - 1 ? 1 : 0,
                        xm + (size_t)(h + 1) * B * nx, xS + (size_t)(h + 1) * B * nx * nx, (const double*)(sn + cl.me),
                        (const double*)(sn + cl.See), (const double*)target, (const double*)precis,
                        (const double*)g_cost + (size_t)h * B, (const double*)(sl + cl.Sxe), (const double*)(sl + cl.cpol),
@@ -311,9 +338,10 @@ static int mm_rollout_composed_backward_nd_impl(const void* drift_packed, size_t
     rc = mm_moment_match_backward_impl(drift_packed, drift_bytes, Lg, drift_M, nd, dtype, B, sl + cl.md, sl + cl.Sdd, dflags,
                                        gdf1, gdSff, gdcross, cr(kl.cmd), cr(kl.cSdd), 1, wsd,
                                        kept ? tl.ws_stride : ws_drift_bytes, gslot, sums ? tl.gp_stride : bl.gp_bytes, status, stream,
-                                       kept, true, sums ? MMB_MODE_CHAIN : MMB_MODE_ALL, false /* the tape is this rollout's own */);
+                                       kept, true, sums ? MMB_MODE_CHAIN : MMB_MODE_ALL, false /* the tape is this rollout's own */,
+                                       wide && !g_wide_generic);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_policy_head_bwd_nd, dim3(B), dim3(256), lds_pol, s, policy_M, ne, nu, hd, (const double*)(pp + pl.Z64),
+    hipLaunchKernelGGL(k_policy, dim3(B), dim3(256), lds_pol, s, policy_M, ne, nu, hd, (const double*)(pp + pl.Z64),
                        (const double*)(pp + pl.beta64), (const double*)(pp + pl.ls2), (const double*)(pp + pl.var),
                        (const double*)(sl + cl.me), (const double*)(sl + cl.See), (const double*)(sl + cl.pf1),
                        (const double*)(sl + cl.pSff), (const double*)(sl + cl.pcross), (const double*)cr(kl.cSdd),
@@ -385,4 +413,98 @@ extern "C" int mm_rollout_composed_backward_nd_mixed(const void* drift_packed, s
                                               policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
                                               target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
                                               ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, true, mix_W);
+}
+
+// ---- 8 < ne <= 16 encoded dims: the _wide entries ------------------------------------------------------------------------------
+// The same sweep over the same tapes (mm_rollout_composed_taped_nd / _nd_mixed take every ne the compose layer allows) with
+// MMAWideCtx kernels: ne <= 16 (ne <= 8 included, so that the two families can be compared), 1 <= nu <= 4, policy M <= 256 and
+// mm_policy_bwd_nd_lds(M, ne, nu) <= 160 KB -- the same LDS size function as the _nd entries, dominated by a pair item's
+// 11 [M][ne] + 14 [M] doubles plus the sub-sweeps' [ns][M][ne + 2] partial sums, ns = max(1, 256 / M); with one action no pair
+// item runs and its scratch is left out (mm_policy_bwd_wide_lds: the one-action item's 5 [M][ne] + 8 [M] doubles).  A policy is
+// taken when it and every smaller one fit: M <= 121 with one action and M <= 50 with 2 to 4 at ne = 16, M <= 229 and M <= 106 at
+// ne = 11, every M <= 256 with one action and M <= 146 with several at ne = 9.  The per-centre arrays
+// stay [M][d] (a lane-per-centre stride of 128 bytes at d = 16: a bank conflict a padded row would avoid): the bodies of
+// mm_adjoint.h / mm_adjoint_nd.h index them, are shared with the _nd kernels, whose code must not change, and a stride argument
+// would change it.  The drift's adjoint (mm_moment_match_backward_impl) launches its items kernel with the wide context too
+// (the pair items' inverse at d = nd <= 16).
+extern "C" size_t mm_compose_backward_workspace_bytes_wide(int B, int nx, int na, int nu, int drift_M, int policy_M) {
+  if (B <= 0 || drift_M <= 0 || !mm_compose_bwd_nd_takes(nx, na, nu, policy_M, MMB_WIDE_NE)) return 0;
+  return mm_compose_bwd_layout_nd(B, nx, na, nu, drift_M).total;
+}
+
+extern "C" size_t mm_compose_backward_workspace_bytes_wide_mixed(int B, int nx, int na, int nu, int drift_L, int drift_M,
+                                                                 int policy_M) {
+  if (B <= 0 || drift_M <= 0 || !mm_compose_bwd_nd_takes(nx, na, nu, policy_M, MMB_WIDE_NE) || drift_L < 1 || drift_L > nx) return 0;
+  return mm_compose_bwd_layout_nd_mixed(B, nx, na, nu, drift_L, drift_M).total;
+}
+
+// generic != 0: the _wide entries run the generic dense code from now on (0: the fast paths, the default).  Returns the previous
+// setting.  For measuring one against the other in one process (tools/bench_compose_wide.py); not thread-safe.
+extern "C" int mm_compose_wide_dense_path(int generic) {
+  const int was = g_wide_generic;
+  g_wide_generic = generic ? 1 : 0;
+  return was;
+}
+
+extern "C" int mm_compose_wide_backward(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                                 const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                                 int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                                 int nu, const double* head_scale, const double* head_shift,
+                                                 const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                                 const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                 void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                 int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, nullptr, nullptr, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, false, nullptr, true);
+}
+
+extern "C" int mm_compose_wide_backward_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                        int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                        int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                        const int32_t* active_dims, int nu, const double* head_scale,
+                                                        const double* head_shift, const void* target, const void* precis,
+                                                        const void* tape, size_t tape_bytes, const void* g_cost,
+                                                        const void* g_xm, const void* g_xS,
+                                                        void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                        void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                        int32_t* status, void* stream) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, false, nullptr, true);
+}
+
+// a coregionalised drift (the tape of mm_rollout_composed_taped_nd_mixed): mix_W as mm_rollout_composed_backward_nd_mixed
+extern "C" int mm_compose_wide_backward_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                       int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                       int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                       const int32_t* active_dims, int nu, const double* head_scale,
+                                                       const double* head_shift, const void* target, const void* precis,
+                                                       const void* tape, size_t tape_bytes, const void* g_cost,
+                                                       void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                       void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                       int32_t* status, void* stream, const double* mix_W) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, nullptr, nullptr, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, true, mix_W, true);
+}
+
+extern "C" int mm_compose_wide_backward_mixed_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                              int drift_d, const void* policy_packed, size_t policy_bytes,
+                                                              int policy_M, int policy_d, int dtype, int B, int H, double dt, int nx,
+                                                              int na, const int32_t* active_dims, int nu, const double* head_scale,
+                                                              const double* head_shift, const void* target, const void* precis,
+                                                              const void* tape, size_t tape_bytes, const void* g_cost,
+                                                              const void* g_xm, const void* g_xS,
+                                                              void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                              void* ws_drift, size_t ws_drift_bytes, void* ws_bwd,
+                                                              size_t ws_bwd_bytes, int32_t* status, void* stream,
+                                                              const double* mix_W) {
+  return mm_rollout_composed_backward_nd_impl(drift_packed, drift_bytes, drift_L, drift_M, drift_d, policy_packed, policy_bytes,
+                                              policy_M, policy_d, dtype, B, H, dt, nx, na, active_dims, nu, head_scale, head_shift,
+                                              target, precis, tape, tape_bytes, g_cost, g_xm, g_xS, g_policy, g_mx0, g_Sxx0,
+                                              ws_drift, ws_drift_bytes, ws_bwd, ws_bwd_bytes, status, stream, true, mix_W, true);
 }

@@ -215,7 +215,7 @@ def _warn_fallback(warned: list, native: Optional[bool], closure: str, reason: s
 
 def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: int, dt: float = 1.0,
                        why: Optional[list] = None, native_actions: int = 1, native_no_encoder: bool = False,
-                       native_objective: bool = False, native_coregionalized: bool = False):
+                       native_objective: bool = False, native_coregionalized: bool = False, native_wide: bool = False):
   """``f(mx, Sxx) -> loss [B]`` running the whole rollout in ``mm_rollout_composed`` (csrc/mm_compose.hip), or None
   when the system is not the shape that entry point implements: TrigonometricEncoder, policy =
   InverseLinkWrapper(KernelRegressor(SVGP with one latent per action), Chain[Scale, Shift, NormalCDF]), SVGP drift, no
@@ -242,8 +242,13 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
   ``native_coregionalized``: take a drift with a ``LinearCoregionalization`` kernel of Lg <= nx latents too: its mixing f = W g + c
   runs on the device after every drift match (csrc/mm_mix.h) and the rollout -- one action included -- goes through the
   ``_nd_mixed`` entries, forward and gradient (``ComposedRolloutFunction`` / ``ComposedTrajectoryFunction``).  W and the Constant
-  mean are constants of the frozen drift, re-read when they change in place."""
+  mean are constants of the frozen drift, re-read when they change in place.
+
+  ``native_wide``: let ``with_grad`` differentiate a rollout with 8 < ne <= 16 encoded dims natively too, through the tapes of the
+  ``_nd`` family and the wide reverse sweep (``mm_compose_wide_backward*``, ``ComposedRollout.backward_wide_refusal``); the other
+  options keep their meaning there (``native_actions`` still decides nu > 1).  ne <= 8 is routed as without it."""
   from . import ops
+  wide = bool(native_wide)
   parts = _native_parts(system, objective, why, moment_solver=True, no_encoder=bool(native_no_encoder),
                         any_objective=bool(native_objective), coregionalized=bool(native_coregionalized))
   if parts is None:
@@ -322,6 +327,7 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       mx, Sxx = mx.double(), Sxx.double()
     traj = uses_trajectory(mx)
     roll = current_roll(mx, fresh_policy=False, zero=traj)
+    roll.use_wide = wide and roll.ne > 8                   # (8 < ne <= 16: the tape of the _nd family and the wide reverse sweep)
     Zp, lsp, varp, betap, _, mcp = pm_.precompute(mx.device)
     if mcp is None:
       mcp = torch.zeros(roll.nu, dtype=Zp.dtype, device=mx.device)
@@ -359,6 +365,8 @@ def native_policy_loss(system: DynamicalSystem, objective: Callable, num_steps: 
       return "the drift is being trained (the native reverse sweep takes a frozen drift)"
     mx64 = mx if mx.dtype == torch.float64 else torch.empty(mx.shape, dtype=torch.float64, device=mx.device)
     roll = current_roll(mx64, fresh_policy=False, zero=uses_trajectory(mx))
+    if wide and roll.ne > 8:
+      return roll.backward_wide_refusal()
     if roll.uses_nd:
       return roll.backward_nd_refusal()
     if not roll.supports_backward():
@@ -379,7 +387,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
                         num_steps: int, initial_time: float = 0.0,
                         solution_times: Optional[Sequence[float]] = None, native: Optional[bool] = None,
                         native_actions: int = 1, native_no_encoder: bool = False, native_objective: bool = False,
-                        native_coregionalized: bool = False, **kwargs) -> Callable:
+                        native_coregionalized: bool = False, native_wide: bool = False, **kwargs) -> Callable:
   """pilco.py:176-220.  Returns ``closure() -> loss [B]``; ``system.solver`` should be a
   ``MomentMatchingEuler`` (pilco.py:141-144).
 
@@ -414,7 +422,15 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
   (``mm_rollout_composed_nd_mixed`` and its tape / reverse sweep).  A coregionalised policy, Lg > nx, a trainable drift (W and the
   mean included) and head / objective constants that require a gradient each fall back once, with a named reason.  So does a
   drift or a policy with Matern latents: moment matching has closed forms for SquaredExponential only (``native=True`` raises with
-  that reason, and the torch composition meets ``moment_matching``'s own ``NotImplementedError``)."""
+  that reason, and the torch composition meets ``moment_matching``'s own ``NotImplementedError``).
+
+  ``native_wide``: with the default False a gradient at more than 8 encoded dims (ne = nx + na > 8) takes the torch composition, as
+  before and with the same text.  True runs it as one differentiable op for 8 < ne <= 16 (``mm_compose_wide_backward*``: the wide
+  reverse sweep over the ``_nd`` family's tape) -- 1 to 4 actions under ``native_actions``, with or without an encoder
+  (``native_no_encoder``), any objective (``native_objective``: the seeded sweep), a coregionalised drift
+  (``native_coregionalized``), and under ``GraphedPolicyLoss``.  ne = 17..24, a policy past the sweep's LDS bound, a trainable
+  drift, and head / objective constants that require a gradient (without ``native_objective``) each fall back once with a named
+  reason.  ne <= 8 is routed as without the option."""
   uniform = solution_times is None
   if solution_times is None:
     solution_times = np.arange(1, 1 + num_steps, dtype=np.float64)     # pilco.py:186
@@ -430,7 +446,7 @@ def policy_loss_closure(system: DynamicalSystem, objective: Callable, state_init
       why_not = []
       fast = native_policy_loss(system, objective, num_steps, dt=1.0, why=why_not, native_actions=native_actions,
                                 native_no_encoder=native_no_encoder, native_objective=native_objective,
-                                native_coregionalized=native_coregionalized)
+                                native_coregionalized=native_coregionalized, native_wide=native_wide)
       if fast is None:
         shape_reason = why_not[0] if why_not else "the system is not the shape mm_rollout_composed implements"
   if native is True and fast is None:

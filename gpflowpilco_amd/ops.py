@@ -428,6 +428,16 @@ _COMPOSED = {
                                 "mm_compose_nd_mixed_workspace_bytes", "mm_compose_tape_bytes_nd_mixed",
                                 "mm_compose_backward_workspace_bytes_nd_mixed", head_arrays=True, mix=True, latent_axis=True,
                                 plain="nd"),
+    # 8 < ne <= 16 in the gradient: the forward, the tape and their size queries are the _nd family's (general in ne), the reverse
+    # sweep and its size query are the wide entries (csrc/mm_compose_bwd_nd.hip)
+    "wide": _ComposedFamily("wide", "mm_rollout_composed_nd", "mm_rollout_composed_taped_nd", "mm_compose_wide_backward",
+                            "mm_compose_wide_backward_seeded", "mm_compose_nd_workspace_bytes", "mm_compose_tape_bytes_nd",
+                            "mm_compose_backward_workspace_bytes_wide", head_arrays=True, mix=False, latent_axis=True, plain="wide"),
+    "wide_mixed": _ComposedFamily("wide_mixed", "mm_rollout_composed_nd_mixed", "mm_rollout_composed_taped_nd_mixed",
+                                  "mm_compose_wide_backward_mixed", "mm_compose_wide_backward_mixed_seeded",
+                                  "mm_compose_nd_mixed_workspace_bytes", "mm_compose_tape_bytes_nd_mixed",
+                                  "mm_compose_backward_workspace_bytes_wide_mixed", head_arrays=True, mix=True, latent_axis=True,
+                                  plain="wide"),
 }
 
 
@@ -441,6 +451,8 @@ class ComposedRollout:
   moments are bivariate normal CDFs); ``taped`` / ``backward`` are one-action, ``taped_nd`` / ``backward_nd`` the tape and reverse
   sweep for 1 to 4 actions (csrc/mm_compose_bwd_nd.hip).  ``head_scale`` / ``head_shift``: a float or one value per action.
   ``__call__(mx, Sxx, H)`` returns ``(mx_H, Sxx_H, cost [B, H])`` (and the trajectory if asked); the inputs are not modified.
+  ``taped_wide`` / ``backward_wide``: the same tape and the wide reverse sweep (``mm_compose_wide_backward*``) for up to 16
+  encoded dims, where ``taped_nd`` / ``backward_nd`` stop at 8 (``supports_backward_wide``).
 
   ``mix_W`` [nx, Lg] (and optionally ``mix_c`` [nx]): the drift is coregionalised -- ``drift`` packs its Lg <= nx latents (with C, no
   mean) and its outputs are f = W g + c, mixed on the device after every drift match (csrc/mm_mix.h).  Such a rollout (``mixed``)
@@ -501,8 +513,12 @@ class ComposedRollout:
     self._consts = {arrays: (self.nx, self.na, self._act, *head, *cost_args) for arrays, head in heads.items()}
     # the dims a family's size queries take after (nx, na), by family name; the family this rollout runs in, and the one its
     # _nd methods take
-    self._dims = {"one": (), "nd": (self.nu,), "nd_mixed": (self.nu, int(drift.L))}
+    self._dims = {"one": (), "nd": (self.nu,), "nd_mixed": (self.nu, int(drift.L)), "wide": (self.nu,),
+                  "wide_mixed": (self.nu, int(drift.L))}
     self._nd_family = _COMPOSED["nd_mixed" if self.mixed else "nd"]
+    self._wide_family = _COMPOSED["wide_mixed" if self.mixed else "wide"]
+    # the differentiable ops (autodiff.ComposedRolloutFunction / ComposedTrajectoryFunction) tape and sweep through the wide family
+    self.use_wide = False
     self._family = self._nd_family if self.uses_nd else _COMPOSED["one"]
     self._wsc = {}
 
@@ -549,8 +565,9 @@ class ComposedRollout:
                        status.data_ptr(), stream, *(self._mixing if fam.mix else ()))
 
   def _sweep_call(self, fam, pol, B, H, dt, tape, g_cost, seeds, g_pol, g_m, g_S, wd, wb, status, stream):
-    """``seeds``: None (the unseeded entry) or (g_xm | None, g_xS | None).  The mixed sweep always takes the seeded signature."""
-    if fam.mix and seeds is None:
+    """``seeds``: None (the unseeded entry) or (g_xm | None, g_xS | None).  The ``_nd_mixed`` sweep always takes the seeded
+    signature (it has no unseeded entry)."""
+    if fam.mix and seeds is None and fam.backward == fam.seeded:
       seeds = (None, None)
     return (fam.backward if seeds is None else fam.seeded,
             (*self._prefix(fam, pol, B, H, dt), tape.data_ptr(), tape.numel(), g_cost.data_ptr(),
@@ -613,7 +630,7 @@ class ComposedRollout:
     dt_ = self.drift.dtype
     B, H = self._check_state(mx, Sxx), int(num_steps)
     if fam.latent_axis:
-      why = self.backward_nd_refusal()
+      why = self.backward_wide_refusal() if fam is self._wide_family else self.backward_nd_refusal()
       if why is not None:
         raise ValueError(why)
     mx, Sxx = mx.contiguous().clone(), Sxx.contiguous().clone()
@@ -641,7 +658,7 @@ class ComposedRollout:
     g_S = torch.empty(B, self.nx, self.nx, dtype=f64, device=dev) if want_state_grad else None
     wd = self.drift.workspace(B, MM_FULL_OUTPUT_COV | MM_MODEL_UNCERTAINTY)
     plain = _COMPOSED[fam.plain]
-    key = ("bwd_nd" if fam.latent_axis else "bwd", B)
+    key = ("bwd_wide" if fam is self._wide_family else "bwd_nd" if fam.latent_axis else "bwd", B)
     wb = self._wsc.get(key)
     if wb is None:
       n = self._backward_ws_bytes(fam, B, pol.M)
@@ -712,8 +729,9 @@ class ComposedRollout:
   def tape_states(self, tape: torch.Tensor, B: int, num_steps: int):
     """The states x_1 .. x_H a taped rollout left on its tape: -> (xm [H, B, nx], xS [H, B, nx, nx]), float64 copies."""
     H = int(num_steps)
-    n = self._tape_bytes(self._family, B, H, MM_F64)
-    slot = self._bytes(_COMPOSED[self._family.plain], "compose_ws", (B,), (MM_F64,))
+    fam = self._wide_family if self.use_wide else self._family
+    n = self._tape_bytes(fam, B, H, MM_F64)
+    slot = self._bytes(_COMPOSED[fam.plain], "compose_ws", (B,), (MM_F64,))
     if n == 0 or tape.numel() < n or tape.dtype != torch.uint8:
       raise ValueError("not a tape of this rollout")
     # MMTapeLayout (csrc/mm_compose.h): H + 1 slots, then x_0 .. x_H means and covariances, each block aligned to 256 bytes
@@ -754,6 +772,42 @@ class ComposedRollout:
     variance, mean), and the gradient w.r.t. the initial state.  ``policy`` must be the pack the tape was recorded with.
     ``g_traj``: seeds on the taped states as in ``backward`` (``mm_rollout_composed_backward_nd_seeded``)."""
     return self._sweep(self._nd_family, tape, g_cost, B, num_steps, dt, policy, want_state_grad, g_traj)
+
+  # ---- the same for 8 < ne <= 16 encoded dims: the tape of the _nd family, the wide reverse sweep --------------------------------
+  WIDE_MAX_NE = 16
+
+  def max_policy_M_wide(self) -> int:
+    """The largest number of policy centres the wide reverse sweep takes at this rollout's (ne, nu): its LDS bound (0: none)."""
+    for M in range(self.BACKWARD_MAX_POLICY_M, 0, -1):
+      if self._backward_ws_bytes(self._wide_family, 1, M):
+        return M
+    return 0
+
+  def backward_wide_refusal(self) -> Optional[str]:
+    """Why ``taped_wide`` / ``backward_wide`` do not take this rollout (None: they do)."""
+    if self.drift.dtype != torch.float64:
+      return "the wide tape and reverse sweep are float64 only"
+    if self.ne > self.WIDE_MAX_NE:
+      return f"encoded dim ne = {self.ne} > {self.WIDE_MAX_NE} (the wide reverse sweep takes ne <= {self.WIDE_MAX_NE})"
+    if self._backward_ws_bytes(self._wide_family, 1, self.policy.M) == 0:
+      return (f"the policy (M = {self.policy.M} centres on ne = {self.ne} dims, {self.nu} actions) is past the LDS bound of the "
+              f"wide reverse sweep (M <= 256 and 160 KB of LDS per workgroup: M <= {self.max_policy_M_wide()} at these dims)")
+    return None
+
+  def supports_backward_wide(self) -> bool:
+    """The wide reverse sweep (``taped_wide`` / ``backward_wide``) takes this rollout: f64, ne <= 16 (ne <= 8 included), up to 4
+    actions, policy M <= 256 inside the sweep's LDS bound (``backward_wide_refusal`` names the reason if not)."""
+    return self.backward_wide_refusal() is None
+
+  def taped_wide(self, mx: torch.Tensor, Sxx: torch.Tensor, num_steps: int, dt: float = 1.0, policy: Optional[PackedModel] = None):
+    """``taped_nd`` for the shapes ``backward_wide`` takes (the tape is the ``_nd`` family's): -> (mx_H, Sxx_H, cost [H, B], tape)."""
+    return self._taped(self._wide_family, mx, Sxx, num_steps, dt, policy)
+
+  def backward_wide(self, tape: torch.Tensor, g_cost: torch.Tensor, B: int, num_steps: int, dt: float = 1.0,
+                    policy: Optional[PackedModel] = None, want_state_grad: bool = True, g_traj=None):
+    """``mm_compose_wide_backward`` (``_seeded`` with ``g_traj``; ``_mixed`` for a coregionalised drift): ``backward_nd`` for
+    ne <= 16 encoded dims, with the same results' shapes."""
+    return self._sweep(self._wide_family, tape, g_cost, B, num_steps, dt, policy, want_state_grad, g_traj)
 
 
 class GraphedComposedRollout:

@@ -392,6 +392,57 @@ int mm_rollout_composed_backward_nd_mixed(const void* drift_packed, size_t drift
                                           void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
                                           int32_t* status, void* stream, const double* mix_W);
 
+/* ---- the reverse sweep for 8 < ne <= 16 encoded dims: the _wide entries (csrc/mm_compose_bwd_nd.hip) -----------------------------
+ * The sweeps of mm_rollout_composed_backward_nd[_seeded] / _nd_mixed over the same tapes (mm_rollout_composed_taped_nd and
+ * _taped_nd_mixed take every ne the compose layer allows), argument for argument, for ne = nx + na <= 16 (ne <= 8 included), 1 to 4
+ * actions, policy M <= 256 and the policy kernel's LDS -- the _nd entries' size function at the wider ne, without the pair item's
+ * scratch when there is one action -- within 160 KB for this M and every smaller one: at ne = 16, M <= 121 with one action and
+ * M <= 50 with 2 to 4; at ne = 9, 256 and 146.  Beyond, the size queries return 0 and the entries MM_E_DIM; the
+ * other codes are those of the _nd entries.  The small dense algebra at 8 < n <= 16 (the SPD inverses of the policy adjoint and
+ * of the drift's pair items, the pivoted solve of the cost adjoint) runs on one wave with four entries per lane; pivot choice, row exchanges and the sign of
+ * the determinant are those of the generic code.  f64 only; no floating-point atomics (two sweeps over one tape are bit-equal).
+ * The _wide_mixed entries take mix_W last; _wide_mixed_seeded has the argument list of mm_rollout_composed_backward_nd_mixed.
+ * mm_compose_wide_dense_path(generic): which dense code the _wide entries run from now on in this process -- 0 (default) the
+ * one-wave paths, non-zero the generic code of the _nd entries; returns the previous setting.  A measuring aid, not thread-safe. */
+size_t mm_compose_backward_workspace_bytes_wide(int B, int nx, int na, int nu, int drift_M, int policy_M);
+size_t mm_compose_backward_workspace_bytes_wide_mixed(int B, int nx, int na, int nu, int drift_L, int drift_M, int policy_M);
+int mm_compose_wide_dense_path(int generic);
+int mm_compose_wide_backward(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                      const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                      int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                      int nu, const double* head_scale, const double* head_shift,
+                                      const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                      const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
+                                      void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                      int32_t* status, void* stream);
+int mm_compose_wide_backward_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                             const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                             int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                             int nu, const double* head_scale, const double* head_shift,
+                                             const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                             const void* g_cost, const void* g_xm, const void* g_xS,
+                                             void* g_policy, void* g_mx0, void* g_Sxx0,
+                                             void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                             int32_t* status, void* stream);
+int mm_compose_wide_backward_mixed(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M, int drift_d,
+                                            const void* policy_packed, size_t policy_bytes, int policy_M, int policy_d,
+                                            int dtype, int B, int H, double dt, int nx, int na, const int32_t* active_dims,
+                                            int nu, const double* head_scale, const double* head_shift,
+                                            const void* target, const void* precis, const void* tape, size_t tape_bytes,
+                                            const void* g_cost, void* g_policy, void* g_mx0, void* g_Sxx0,
+                                            void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                            int32_t* status, void* stream, const double* mix_W);
+int mm_compose_wide_backward_mixed_seeded(const void* drift_packed, size_t drift_bytes, int drift_L, int drift_M,
+                                                   int drift_d, const void* policy_packed, size_t policy_bytes, int policy_M,
+                                                   int policy_d, int dtype, int B, int H, double dt, int nx, int na,
+                                                   const int32_t* active_dims, int nu, const double* head_scale,
+                                                   const double* head_shift, const void* target, const void* precis,
+                                                   const void* tape, size_t tape_bytes, const void* g_cost,
+                                                   const void* g_xm, const void* g_xS,
+                                                   void* g_policy, void* g_mx0, void* g_Sxx0,
+                                                   void* ws_drift, size_t ws_drift_bytes, void* ws_bwd, size_t ws_bwd_bytes,
+                                                   int32_t* status, void* stream, const double* mix_W);
+
 /* ---- backward w.r.t. the input moments, stage A (f64 mode) ---------------------
  * The M x M part of d(f1, Sff, cross)/d(mu, Sigma) reduced to M-sized sums (see csrc/mm_backward.hip);
  * gpflowpilco_amd/autodiff.py finishes the chain rule.  Must follow mm_moment_match / mm_q_forward +
