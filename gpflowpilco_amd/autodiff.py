@@ -496,3 +496,35 @@ class ComposedTrajectoryFunction(torch.autograd.Function):
   def backward(ctx, g_cost, g_xm, g_xS):
     g_xS = 0.5 * (g_xS + g_xS.transpose(-1, -2))
     return _composed_rollout_gradients(ctx, g_cost, (g_xm.transpose(0, 1).contiguous(), g_xS.transpose(0, 1).contiguous()))
+
+
+class GramSEFunction(torch.autograd.Function):
+  """The SE-ARD Gram matrix K [L,M,N] between the data X [N,d] and the inducing points Z [L,M,d] as a differentiable op
+  (``mm_gram_se`` / ``mm_gram_se_backward``, csrc/mm_gram.hip): gradients with respect to Z, the lengthscales [L,d] and the variances
+  [L]; X is a constant.  Only the operands are saved -- the adjoint recomputes K -- so autograd holds no [L,M,N] tensor for it."""
+
+  @staticmethod
+  def forward(ctx, X, Z, ls, var):
+    ctx.save_for_backward(X, Z, ls, var)
+    return ops.gram_se(X, Z, ls, var)
+
+  @staticmethod
+  def backward(ctx, G):
+    X, Z, ls, var = ctx.saved_tensors
+    gZ, gls, gvar = ops.gram_se_backward(G, X, Z, ls, var)
+    return None, gZ, gls, gvar
+
+
+class GramSESelfFunction(torch.autograd.Function):
+  """K [L,M,M] = k_l(Z_l, Z_l) (no jitter) as a differentiable op: the self mode of ``GramSEFunction``.  The incoming gradient
+  may be any matrix (the blocked Cholesky's is not symmetric): the adjoint is the full derivative through both slots."""
+
+  @staticmethod
+  def forward(ctx, Z, ls, var):
+    ctx.save_for_backward(Z, ls, var)
+    return ops.gram_se_self(Z, ls, var)
+
+  @staticmethod
+  def backward(ctx, G):
+    Z, ls, var = ctx.saved_tensors
+    return ops.gram_se_backward(G, None, Z, ls, var)

@@ -142,7 +142,7 @@ def cholesky(A: torch.Tensor) -> torch.Tensor:
   if failed:
     msg = _describe(A, info)
   elif A.is_cuda and A.shape[-1] > 64:
-    res = _residual(A, L)
+    res = _residual(A.detach(), L.detach())                  # (the ELBO factorises under autograd: the check itself is a constant)
     if not res < 1e-9:                                       # also catches NaN
       failed = True
       msg = f"info = 0 but the factor does not reproduce the matrix: probe residual {res:.3e} (n={A.shape[-1]}, device={A.device})"

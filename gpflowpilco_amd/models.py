@@ -1,7 +1,8 @@
 """Parameter containers for the moment-matching handlers.
 
 Minimal torch equivalents of the gpflow / gpflow_pilco objects the hot path
-reads (fields only; hyper-parameter fitting is out of scope):
+reads (fields, plus what trains an ``SVGP`` from data: ``SVGP.elbo``, ``SVGP.initialize``, ``PilcoPenaltySNR``; the
+optimiser is ``training.fit_svgp``):
 
 * kernels: ``SquaredExponential``, ``Matern32`` / ``Matern52`` (pathwise sampling only) and the multi-output ``SeparateIndependent`` /
   ``SharedIndependent`` / ``LinearCoregionalization`` (gpflow.kernels), read at
@@ -442,6 +443,265 @@ class SVGP:
   def packed(self, dtype, with_C: bool, device):
     """(A Matern model is refused by ``precompute``, which every cache miss runs: nothing is checked per call.)"""
     return self._cache.get(self, dtype, with_C, device)
+
+  # -- training: the ELBO, its objective and the initialiser (gpflow's SVGP.elbo; models/svgp.py:41-121) --------------------------
+  def _native_gram_refusal(self, X, kernels, family: int, d: int, differ: bool) -> Optional[str]:
+    """Why the ELBO of this model on these data does not take the HIP Gram (None: it does)."""
+    if not X.is_cuda:
+      return f"the data are on {X.device} (the HIP Gram kernel runs on the GPU)"
+    if family != KERNEL_SE:
+      return f"the native Gram is SquaredExponential only, the latents are {type(kernels[0]).__name__} (torch Gram)"
+    if differ:
+      return "the latent kernels act on differing active_dims (torch Gram)"
+    if d > 32:
+      return f"input dimension {d} exceeds MM_DMAX = 32"
+    return None
+
+  def elbo(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """gpflow's ``SVGP.elbo`` on the full batch ``data = (X [N,d], Y [N,P])``, Gaussian likelihood: expected log-likelihood under
+    the marginals of q(f) minus KL(q(u) || p(u)), differentiable in every parameter (kernel variances and lengthscales, Z, q_mu,
+    q_sqrt, the Constant mean, ``kernel.W``, ``likelihood.variance``).
+
+    Per latent: Kuu = k(Z, Z) + jitter I = Lu Lu^T, A = Lu^-1 Kuf; whitened, mean_g = A^T q_mu and
+    var_g = var - colsum(A^2) + colsum((tril(q_sqrt)^T A)^2); not whitened, the two q terms with Lu^-T A.  The two Gram matrices
+    are the only [L,M,N]-sized elementwise work: ``native=None`` takes them from the HIP kernel (``autodiff.GramSEFunction`` /
+    ``GramSESelfFunction``) on a GPU for SquaredExponential latents with d <= 32 and from torch otherwise (CPU data, a Matern
+    family, latents on differing ``active_dims``); ``native=False`` always from torch; ``native=True`` raises with the reason where
+    the native route does not apply.  The factorisation, the solves and the products are torch's on both routes."""
+    import math
+    X, Y = data
+    if not isinstance(self.likelihood, GaussianLikelihood):
+      raise NotImplementedError(f"SVGP.elbo: Gaussian likelihood only, got {type(self.likelihood).__name__}")
+    kernels, Zs = unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)
+    family = kernel_family(kernels)
+    device = X.device
+    Z, ls, var = _stack_kernel_params(kernels, Zs, device)
+    L, M, d = Z.shape
+    union, differ = kernel_input_dims(kernels, X.shape[-1])
+    Xs = (X[..., list(union)] if differ else kernels[0].slice(X)).to(DEFAULT_FLOAT)
+    Y = Y.to(device=device, dtype=DEFAULT_FLOAT)
+    N = Xs.shape[0]
+    refusal = self._native_gram_refusal(Xs, kernels, family, d, differ)
+    if native and refusal is not None:
+      raise ValueError(f"SVGP.elbo(native=True): {refusal}")
+    if native is not False and refusal is None:
+      from .autodiff import GramSEFunction, GramSESelfFunction
+      Kuf = GramSEFunction.apply(Xs.detach(), Z, ls, var)
+      Kuu = GramSESelfFunction.apply(Z, ls, var)
+    else:
+      Az, Ax = Z / ls[:, None, :], Xs[None] / ls[:, None, :]
+      Kuf = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Ax), family)
+      Kuu = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Az), family)
+    eye = torch.eye(M, dtype=DEFAULT_FLOAT, device=device)
+    Lu = cholesky(Kuu + DEFAULT_JITTER * eye)
+    A = torch.linalg.solve_triangular(Lu, Kuf, upper=False)                       # [L,M,N]
+    qm = self.q_mu.to(device=device, dtype=DEFAULT_FLOAT).T                       # [L,M]
+    S = torch.tril(self.q_sqrt.to(device=device, dtype=DEFAULT_FLOAT))            # [L,M,M]
+    log_qdiag = torch.log(torch.diagonal(S, dim1=-2, dim2=-1).abs()).sum()
+    if self.whiten:
+      Aq = A
+      kl = 0.5 * ((qm * qm).sum() + (S * S).sum() - L * M) - log_qdiag
+    else:
+      Aq = torch.linalg.solve_triangular(Lu.transpose(1, 2), A, upper=True)       # Lu^-T A = Kuu^-1 Kuf
+      Lm = torch.linalg.solve_triangular(Lu, qm.unsqueeze(-1), upper=False)
+      LS = torch.linalg.solve_triangular(Lu, S, upper=False)
+      log_udiag = torch.log(torch.diagonal(Lu, dim1=-2, dim2=-1)).sum()
+      kl = 0.5 * ((Lm * Lm).sum() + (LS * LS).sum() - L * M) + log_udiag - log_qdiag
+    mean_g = (Aq * qm[:, :, None]).sum(1)                                         # [L,N]
+    SA = S.transpose(1, 2) @ Aq
+    var_g = var[:, None] - (A * A).sum(1) + (SA * SA).sum(1)                      # [L,N]
+    if isinstance(self.kernel, LinearCoregionalization):
+      W = self.kernel.W.to(device=device, dtype=DEFAULT_FLOAT)                    # [P,L]
+      f_mean, f_var = mean_g.T @ W.T, var_g.T @ (W * W).T
+    else:
+      f_mean, f_var = mean_g.T, var_g.T
+    if isinstance(self.mean_function, Constant):
+      f_mean = f_mean + self.mean_function.c.to(device=device, dtype=DEFAULT_FLOAT)
+    elif not isinstance(self.mean_function, Zero):
+      raise NotImplementedError(f"SVGP.elbo: mean function {type(self.mean_function).__name__}")
+    if Y.shape != f_mean.shape:
+      raise ValueError(f"SVGP.elbo: Y {tuple(Y.shape)} against {tuple(f_mean.shape)} model outputs")
+    s2 = self.likelihood.variance.to(device=device, dtype=DEFAULT_FLOAT)
+    fit = (-0.5 * torch.log(2.0 * math.pi * s2) - ((Y - f_mean) ** 2 + f_var) / (2.0 * s2)).sum()
+    return fit - kl
+
+  def maximum_log_likelihood_objective(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """``elbo + prior(self)`` (models/svgp.py:41-45)."""
+    objective = self.elbo(data, native=native)
+    if self.prior is not None:
+      objective = objective + self.prior(self)
+    return objective
+
+  def training_loss(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    return -self.maximum_log_likelihood_objective(data, native=native)
+
+  def training_loss_closure(self, data, native: Optional[bool] = None) -> Callable[[], torch.Tensor]:
+    """Zero-argument callable of the training loss: the reference's ``dynamics_loss_closure`` (loops/pilco.py:173-174)."""
+    return lambda: self.training_loss(data, native=native)
+
+  @classmethod
+  def initialize(cls, data, num_inducing: int, likelihood=None, mean_function="default", kernels=None,
+                 coregionalize: Optional[bool] = None, num_latent_gps: Optional[int] = None, max_corr: float = 1.0,
+                 seed: Optional[int] = None, **kwargs):
+    """A model to start ``training.fit_svgp`` from (models/svgp.py:47-121, models/initializers.py): SquaredExponential latents
+    with median-heuristic lengthscales, inducing points by k-means (the data themselves when N <= num_inducing; one draw shared
+    by every latent when ``max_corr == 1``, else per distinct kernel with overly correlated points replaced), a ``Constant`` zero
+    mean, q_mu = 0 and q_sqrt = I, and -- when the latent count differs from the output count, or on request -- a
+    ``LinearCoregionalization`` with row-normalised random ``W``.  ``likelihood=None`` is ``GaussianLikelihood()``; ``seed`` seeds
+    the k-means, the replacements and ``W``."""
+    X, Y = (_as_param(t) for t in data)
+    P = Y.shape[-1]
+    L = P if num_latent_gps is None else int(num_latent_gps)
+    if coregionalize is None:
+      coregionalize = P != L
+    if isinstance(mean_function, str) and mean_function == "default":
+      mean_function = Constant(torch.zeros(P, dtype=DEFAULT_FLOAT))
+    if kernels is None:
+      kernels = [SquaredExponential(lengthscales=lengthscales_median(X)) for _ in range(L)]
+    gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+    cache, points = {}, []
+    for kern in kernels:
+      key = None if max_corr == 1 else (type(kern), tuple(kern.variance.reshape(-1).tolist()),
+                                        tuple(kern.lengthscales.reshape(-1).tolist()))
+      if key not in cache:
+        cache[key] = inducing_points_kmeans(X, num_inducing, kernel_and_tol=(kern, max_corr), generator=gen)
+      points.append(InducingPoints(cache[key].clone()))
+    if coregionalize:
+      if P == L:
+        W = torch.eye(P, dtype=DEFAULT_FLOAT)
+      else:
+        W = torch.randn(P, L, dtype=DEFAULT_FLOAT, generator=gen)
+        W = W / W.norm(dim=-1, keepdim=True)
+      kernel = LinearCoregionalization(kernels, W)
+    else:
+      if P != L:
+        raise ValueError(f"{L} independent latents for {P} outputs: coregionalize")
+      kernel = SeparateIndependent(kernels)
+    M = points[0].Z.shape[0]
+    kwargs.setdefault("q_mu", torch.zeros(M, L, dtype=DEFAULT_FLOAT))
+    kwargs.setdefault("q_sqrt", torch.eye(M, dtype=DEFAULT_FLOAT).repeat(L, 1, 1))
+    return cls(kernel=kernel, inducing_variable=SeparateIndependentInducingVariables(points),
+               likelihood=GaussianLikelihood() if likelihood is None else likelihood, mean_function=mean_function,
+               num_latent_gps=L, **kwargs)
+
+
+# ---------------------------------------------------------------------------
+# initialisers (models/initializers.py) and the signal-to-noise prior (models/priors.py)
+# ---------------------------------------------------------------------------
+def lengthscales_median(X: torch.Tensor, lower: float = 0.01, upper: float = 100.0) -> torch.Tensor:
+  """Median heuristic: sqrt(1/2) x the median pairwise distance on every dimension, clipped to [1.1 lower, 0.9 upper]."""
+  dist = torch.pdist(_as_param(X))
+  if dist.numel() == 0:
+    med = torch.ones((), dtype=DEFAULT_FLOAT)
+  else:
+    n = dist.numel()
+    med = 0.5 * (dist.kthvalue((n - 1) // 2 + 1).values + dist.kthvalue(n // 2 + 1).values)
+  return torch.full((X.shape[-1],), float((0.5 ** 0.5 * med).clamp(1.1 * lower, 0.9 * upper)), dtype=DEFAULT_FLOAT)
+
+
+def _kmeans(X: torch.Tensor, k: int, generator=None, iterations: int = 50) -> torch.Tensor:
+  """k-means++ seeding and Lloyd iterations.  Every centre is a data point or the mean of data points, so it lies inside the
+  data's bounding box; a cluster that empties keeps its centre."""
+  N = X.shape[0]
+  centres = X[torch.randint(N, (1,), generator=generator)]
+  d2 = ((X - centres[0]) ** 2).sum(-1)
+  for _ in range(1, k):
+    if float(d2.sum()) > 0.0:
+      i = torch.multinomial(d2 / d2.sum(), 1, generator=generator)
+    else:                                                       # fewer distinct points than centres
+      i = torch.randint(N, (1,), generator=generator)
+    centres = torch.cat([centres, X[i]])
+    d2 = torch.minimum(d2, ((X - X[i]) ** 2).sum(-1))
+  assign = None
+  for _ in range(iterations):
+    new = torch.cdist(X, centres).argmin(-1)
+    if assign is not None and torch.equal(new, assign):
+      break
+    assign = new
+    sums = torch.zeros_like(centres).index_add_(0, assign, X)
+    counts = torch.zeros(k, dtype=X.dtype).index_add_(0, assign, torch.ones(N, dtype=X.dtype))
+    centres = torch.where(counts[:, None] > 0, sums / counts.clamp_min(1.0)[:, None], centres)
+  return centres
+
+
+def inducing_points_kmeans(X: torch.Tensor, num_inducing: int, kernel_and_tol=None, generator=None) -> torch.Tensor:
+  """Z [min(N, num_inducing), d]: the data when N <= num_inducing, else k-means centres; with ``kernel_and_tol = (kernel, tol)``
+  and tol < 1, points correlated above tol are replaced (``replace_duplicates``)."""
+  X = _as_param(X).detach().cpu()
+  if X.ndim != 2:
+    raise ValueError(f"X [N,d] expected, got {tuple(X.shape)}")
+  points = X.clone() if X.shape[0] <= num_inducing else _kmeans(X, int(num_inducing), generator)
+  if kernel_and_tol is not None and kernel_and_tol[1] < 1:
+    points = replace_duplicates(points, *kernel_and_tol, generator=generator)
+  return points
+
+
+def replace_duplicates(points: torch.Tensor, kernel, tol: float, num_attempts: int = 32, generator=None) -> torch.Tensor:
+  """Perturb the points whose correlation k(z, z') / variance with another point exceeds ``tol``: the most entangled first, by
+  growing Gaussian steps (1e-3 x 1.1^attempt), until no correlation reaches ``tol``; a point that cannot be moved is left."""
+  if tol == 1:
+    return points
+  if not 0 < tol < 1:
+    raise ValueError(f"max_corr {tol}: expected a value in (0, 1]")
+  import warnings
+  points = points.clone()
+  with torch.no_grad():
+    corr = kernel.K(points) / kernel.variance
+    corr.fill_diagonal_(-float("inf"))
+    while True:
+      hits = (corr > tol).sum(-1)
+      if not bool((hits > 0).any()):
+        return points
+      i = int(hits.argmax())
+      for attempt in range(num_attempts):
+        alt = points[i] + 1e-3 * 1.1 ** attempt * torch.randn(points.shape[-1], dtype=points.dtype, generator=generator)
+        xorr = (kernel.K(points, alt[None]) / kernel.variance).squeeze(-1)
+        xorr[i] = -float("inf")
+        if not bool((xorr >= tol).any()):
+          points[i] = alt
+          corr[i, :] = xorr
+          corr[:, i] = xorr
+          break
+      else:
+        warnings.warn("failed to replace an overly correlated inducing point; continuing")
+        corr[i, :] = -float("inf")
+        corr[:, i] = -float("inf")
+
+
+class AbstractSNR:
+  """log signal-to-noise ratio per output of a model with a Gaussian likelihood (models/priors.py:22-44)."""
+
+  def get_log_snr(self, model) -> torch.Tensor:
+    if not isinstance(model.likelihood, GaussianLikelihood):
+      raise NotImplementedError("the signal-to-noise prior needs a Gaussian likelihood")
+    kernel = model.kernel
+    log_noise = torch.log(model.likelihood.variance)
+    if isinstance(kernel, SharedIndependent):
+      log_signals = torch.log(kernel.kernel.variance).expand(model.num_latent_gps)
+    elif isinstance(kernel, SeparateIndependent):
+      log_signals = torch.log(torch.stack([k.variance for k in kernel.kernels]))
+    elif isinstance(kernel, LinearCoregionalization):
+      variances = torch.stack([k.variance for k in kernel.kernels])
+      log_signals = torch.log((kernel.W ** 2) @ variances.to(kernel.W))
+    else:
+      log_signals = torch.log(kernel.variance)
+    return log_signals - log_noise.to(log_signals)
+
+  def __call__(self, model) -> torch.Tensor:
+    raise NotImplementedError
+
+
+class PilcoPenaltySNR(AbstractSNR):
+  """PILCO's penalty on large signal-to-noise ratios: -sum (log snr / log threshold)^power (models/priors.py:47-55)."""
+
+  def __init__(self, threshold: float, power: float):
+    self.threshold = threshold
+    self.power = power
+
+  def __call__(self, model) -> torch.Tensor:
+    import math
+    log_snr = self.get_log_snr(model)
+    return -((log_snr / math.log(self.threshold)) ** self.power).sum()
 
 
 class GPR:

@@ -931,3 +931,52 @@ def moment_match_backward(pm: PackedModel, mu: torch.Tensor, Sigma: torch.Tensor
                                       pm.status().data_ptr(), _stream(pm.device))
   check(rc, "mm_moment_match_backward")
   return g_mu, g_S
+
+
+def _gram_operands(X: Optional[torch.Tensor], Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor):
+  """Checked, contiguous float64 operands of the Gram entries and (L, M, N, d); ``X`` None is the self mode (N = M)."""
+  _require_device(X, Z, ls, var)
+  if Z.ndim != 3 or ls.shape != (Z.shape[0], Z.shape[2]) or var.shape != (Z.shape[0],):
+    raise ValueError(f"gram_se: Z [L,M,d], ls [L,d], var [L] expected, got {tuple(Z.shape)}, {tuple(ls.shape)}, {tuple(var.shape)}")
+  L, M, d = Z.shape
+  if X is not None:
+    if X.requires_grad:
+      raise ValueError("gram_se: the data X are constants (the adjoint has no gradient with respect to X)")
+    if X.ndim != 2 or X.shape[1] != d:
+      raise ValueError(f"gram_se: X [N,{d}] expected, got {tuple(X.shape)}")
+  f64 = torch.float64
+  ops_ = [None if t is None else t.detach().to(f64).contiguous() for t in (X, Z, ls, var)]
+  return ops_, (L, M, M if X is None else X.shape[0], d)
+
+
+def gram_se(X: Optional[torch.Tensor], Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor) -> torch.Tensor:
+  """``mm_gram_se``: K [L,M,N] = var_l exp(-1/2 |(x_n - z_lm) / ls_l|^2) in float64, the squared distance from differences
+  (csrc/mm_gram.hip).  X [N,d] (None: ``gram_se_self``), Z [L,M,d], ls [L,d], var [L].  Not differentiable by itself:
+  ``autodiff.GramSEFunction``."""
+  (X, Z, ls, var), (L, M, N, d) = _gram_operands(X, Z, ls, var)
+  K = torch.empty(L, M, N, dtype=torch.float64, device=Z.device)
+  check(lib().mm_gram_se(L, M, N, d, _ptr(X), Z.data_ptr(), ls.data_ptr(), var.data_ptr(), K.data_ptr(), _stream(Z.device)),
+        "mm_gram_se")
+  return K
+
+
+def gram_se_self(Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor) -> torch.Tensor:
+  """K [L,M,M] = k_l(Z_l, Z_l): symmetric to the bit, diagonal exactly var_l (no jitter)."""
+  return gram_se(None, Z, ls, var)
+
+
+def gram_se_backward(G: torch.Tensor, X: Optional[torch.Tensor], Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor):
+  """``mm_gram_se_backward``: G [L,M,N] -> (gZ [L,M,d], gls [L,d], gvar [L]); K is recomputed from the operands.  X None: the self
+  mode, G a general [L,M,M] matrix, the derivative through both argument slots.  Deterministic: two calls are bit-equal."""
+  (X, Z, ls, var), (L, M, N, d) = _gram_operands(X, Z, ls, var)
+  _require_device(G)
+  if G.shape != (L, M, N):
+    raise ValueError(f"gram_se_backward: G [{L},{M},{N}] expected, got {tuple(G.shape)}")
+  G = G.detach().to(torch.float64).contiguous()
+  nbytes = lib().mm_gram_workspace_bytes(L, M, N, d)
+  ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=Z.device)
+  gZ, gls, gvar = torch.empty_like(Z), torch.empty_like(ls), torch.empty_like(var)
+  check(lib().mm_gram_se_backward(L, M, N, d, G.data_ptr(), _ptr(X), Z.data_ptr(), ls.data_ptr(), var.data_ptr(), gZ.data_ptr(),
+                                  gls.data_ptr(), gvar.data_ptr(), ws.data_ptr(), ws.numel(), _stream(Z.device)),
+        "mm_gram_se_backward")
+  return gZ, gls, gvar

@@ -779,6 +779,25 @@ int mm_pathwise_basis(int L, int K, int M, int d, int dtype, const double* n, co
 int mm_pathwise_pack_stream(int S, int L, int K, int M, int dtype, const double* w, const double* v, void* wb_out,
                             void* stream);
 
+/* ---- SE-ARD Gram matrix of the SVGP ELBO and its adjoint (csrc/mm_gram.hip; everything f64, row-major) ----------------------
+ * mm_gram_se: X [N,d], Z [L,M,d], ls [L,d], var [L] -> K [L,M,N],
+ *   K[l][m][n] = var_l exp(-1/2 sum_k ((x_nk - z_lmk) / ls_lk)^2), the squared distance formed from differences.
+ *   X == NULL is the SELF mode: K[l] = k_l(Z_l, Z_l) as [L,M,M] (N must equal M), symmetric to the bit with a diagonal of
+ *   exactly var_l; the caller adds its jitter.
+ * mm_gram_se_backward: G [L,M,N] and the same operands -> gZ [L,M,d], gls [L,d], gvar [L]; with t = G K (K recomputed, not read)
+ *   gZ[l][m][k] = sum_n t (x_nk - z_lmk) / ls_lk^2,  gls[l][k] = sum_mn t (x_nk - z_lmk)^2 / ls_lk^3,  gvar[l] = sum_mn t / var_l.
+ *   There is no gradient with respect to X.  In the self mode G is a GENERAL [L,M,M] matrix (it need not be symmetric) and the
+ *   result is the full derivative through both argument slots: gZ_i = sum_j (G_ij + G_ji) K_ij (z_j - z_i) / ls^2.
+ *   Per-chunk partial sums go to the workspace (mm_gram_workspace_bytes(L, M, N, d), N = M in the self mode) and a second launch
+ *   adds them in a fixed order: no atomics, two calls on the same inputs are bit-equal.
+ * Any L, M, N >= 1 (no padding asked of the caller), 1 <= d <= MM_DMAX; MM_E_DIM otherwise (the size query returns 0). */
+size_t mm_gram_workspace_bytes(int L, int M, int N, int d);
+int mm_gram_se(int L, int M, int N, int d, const double* X, const double* Z, const double* ls, const double* var, double* K,
+               void* stream);
+int mm_gram_se_backward(int L, int M, int N, int d, const double* G, const double* X, const double* Z, const double* ls,
+                        const double* var, double* gZ, double* gls, double* gvar, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
