@@ -67,10 +67,14 @@ def main():
   drift = gp.SVGP.initialize((torch.tensor(X), torch.tensor(Y)), args.inducing, seed=0, prior=gp.PilcoPenaltySNR(1000.0, 30.0),
                              likelihood=gp.GaussianLikelihood(1e-2))
   rmse = lambda: float(((drift.predict_mean(t(held_X)) - t(held_Y)) ** 2).mean().sqrt())
-  before = rmse()
+
+  def log_density():                                      # held-out mean log density of the transitions under predict_y
+    with torch.no_grad():
+      return float(drift.predict_log_density((t(held_X), t(held_Y))).mean())
+  before, before_ld = rmse(), log_density()
   history = fit_svgp(drift, (t(X), t(Y)), max_iter=args.fit_iters)
   print(f"drift fit: {len(X)} transitions, {len(history) - 1} L-BFGS iterations, loss {history[0]:+.2f} -> {history[-1]:+.2f}, "
-        f"held-out RMSE {before:.2e} -> {rmse():.2e}")
+        f"held-out RMSE {before:.2e} -> {rmse():.2e}, held-out mean log density {before_ld:+.3f} -> {log_density():+.3f}")
   # 3. the policy, on the fitted drift
   pol = make_policy(12, 2, 8).to_model(dev)
   kern = pol.latent_kernels[0]

@@ -247,12 +247,18 @@ class _PackCache:
     self._pre = None
     self._packed = {}
 
-  def get(self, model, dtype, with_C, device):
+  def pre(self, model, device):
+    """The cached ``model.precompute(device)`` tuple (Z, ls, var, beta, C, mean_c), nothing packed: a second call on an unchanged
+    model factors nothing."""
     key = tuple((id(t), t._version, t.device) for t in model._parameters()) + (str(device),)
     if key != self._key:
       self._key, self._pre, self._packed = key, None, {}
     if self._pre is None:
       self._pre = model.precompute(device)
+    return self._pre
+
+  def get(self, model, dtype, with_C, device):
+    self.pre(model, device)
     slot = (dtype, bool(with_C))
     if slot not in self._packed:
       from . import ops
@@ -316,6 +322,39 @@ def _stack_kernel_params(kernels, Zs, device):
     Z, ls = torch.stack(Zl), torch.stack(lsl)
   var = torch.stack([k.variance.to(device=device, dtype=DEFAULT_FLOAT).reshape(()) for k in kernels])
   return Z, ls, var
+
+
+PREDICT_CHUNK_BYTES = 256 * 2 ** 20  # the torch route of predict_f keeps every intermediate below about this size
+
+
+def _native_predict_refusal(model, X, kernels, family: int, d: int, differ: bool) -> Optional[str]:
+  """Why ``predict_f`` of this model at these points does not take the HIP kernel (None: it does)."""
+  if not X.is_cuda:
+    return f"the points are on {X.device} (the HIP predictive kernel runs on the GPU)"
+  if family != KERNEL_SE:
+    return f"the native predict_f is SquaredExponential only, the latents are {type(kernels[0]).__name__} (torch route)"
+  if differ:
+    return "the latent kernels act on differing active_dims (torch route)"
+  if d > 32:
+    return f"input dimension {d} exceeds MM_DMAX = 32"
+  if torch.is_grad_enabled() and (X.requires_grad or any(t.requires_grad for t in model._parameters())):
+    return "a gradient is being recorded (the native predict_f is not differentiable: torch route, or torch.no_grad())"
+  return None
+
+
+def _predict_y_from_f(model, who: str, mean, var, full_output_cov: bool):
+  """Adds the Gaussian likelihood's variance to the latent marginals (on the diagonal under ``full_output_cov``)."""
+  if not isinstance(model.likelihood, GaussianLikelihood):
+    raise NotImplementedError(f"{who}: Gaussian likelihood only, got {type(model.likelihood).__name__}")
+  s2 = model.likelihood.variance.to(var)
+  if full_output_cov:
+    return mean, var + torch.diag_embed(s2.expand(var.shape[-1]))
+  return mean, var + s2
+
+
+def _gaussian_log_density(Y, mean, var):
+  import math
+  return -0.5 * (torch.log(2.0 * math.pi * var) + (Y - mean) ** 2 / var)
 
 
 class SVGP:
@@ -443,6 +482,87 @@ class SVGP:
   def packed(self, dtype, with_C: bool, device):
     """(A Matern model is refused by ``precompute``, which every cache miss runs: nothing is checked per call.)"""
     return self._cache.get(self, dtype, with_C, device)
+
+  # -- prediction at deterministic points (gpflow's predict_f / predict_y / predict_log_density) ---------------------------------
+  def _latent_marginals_torch(self, X2, kernels, Zs, family: int):
+    """mean_g, var_g [n, L] of the latents at X2 [n, d]: gpflow's conditional (Lu^-1 Kuf, whitened or not -- the algebra of
+    ``elbo``), differentiable, any kernel family, any device; n in chunks that keep [L, M, chunk] below PREDICT_CHUNK_BYTES."""
+    device = X2.device
+    Z, ls, var = _stack_kernel_params(kernels, Zs, device)
+    L, M, d = Z.shape
+    Az = Z / ls[:, None, :]
+    Kuu = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Az), family)
+    Lu = cholesky(Kuu + DEFAULT_JITTER * torch.eye(M, dtype=DEFAULT_FLOAT, device=device))
+    qm = self.q_mu.to(device=device, dtype=DEFAULT_FLOAT).T                       # [L,M]
+    S = torch.tril(self.q_sqrt.to(device=device, dtype=DEFAULT_FLOAT))            # [L,M,M]
+    chunk = max(1, PREDICT_CHUNK_BYTES // (8 * L * M))
+    means, variances = [], []
+    for start in range(0, X2.shape[0], chunk):
+      Ax = X2[None, start:start + chunk] / ls[:, None, :]
+      Kuf = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Ax), family)
+      A = torch.linalg.solve_triangular(Lu, Kuf, upper=False)                     # [L,M,n]
+      Aq = A if self.whiten else torch.linalg.solve_triangular(Lu.transpose(1, 2), A, upper=True)
+      SA = S.transpose(1, 2) @ Aq
+      means.append((Aq * qm[:, :, None]).sum(1).T)
+      variances.append((var[:, None] - (A * A).sum(1) + (SA * SA).sum(1)).T)
+    if not means:
+      empty = X2.new_zeros(0, L)
+      return empty, empty
+    return torch.cat(means), torch.cat(variances)
+
+  def predict_f(self, Xnew: torch.Tensor, full_cov: bool = False, full_output_cov: bool = False, native: Optional[bool] = None):
+    """gpflow's ``predict_f`` at deterministic points Xnew [..., D]: (mean [..., P], var [..., P]), or the output covariance
+    [..., P, P] with ``full_output_cov``.  Independent latents: mean_g + c and var_g (``diag_embed`` of it); a
+    ``LinearCoregionalization``: W mean_g + c and var_g (W o W)^T (W diag(var_g) W^T), mixed in torch on the [n, L] marginals.
+    ``full_cov=True`` (covariances between points) is not implemented.
+
+    ``native=None`` takes the HIP kernel (``ops.predict_se``: mean_g = k^T beta, var_g = var + k^T C k from the cached
+    ``precompute``, K never materialised) for SquaredExponential latents with equal ``active_dims`` and d <= 32 at points on a GPU
+    when no gradient is being recorded (grad mode off, or neither a parameter nor Xnew requires one), and torch otherwise;
+    ``native=False`` always torch (the conditional of ``elbo``; differentiable, CPU and Matern families too, chunked over the
+    points); ``native=True`` raises ``ValueError`` with the reason where the native route does not apply."""
+    if full_cov:
+      raise NotImplementedError("SVGP.predict_f: full_cov=True is not implemented (marginals per point only)")
+    kernels, Zs = unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)
+    family = kernel_family(kernels)
+    union, differ = kernel_input_dims(kernels, Xnew.shape[-1])
+    Xs = (Xnew[..., list(union)] if differ else kernels[0].slice(Xnew)).to(DEFAULT_FLOAT)
+    lead, d = Xs.shape[:-1], Xs.shape[-1]
+    X2 = Xs.reshape(-1, d)
+    coreg = isinstance(self.kernel, LinearCoregionalization)
+    if not isinstance(self.mean_function, (Zero, Constant)):
+      raise NotImplementedError(f"SVGP.predict_f: mean function {type(self.mean_function).__name__}")
+    refusal = _native_predict_refusal(self, X2, kernels, family, d, differ)
+    if native and refusal is not None:
+      raise ValueError(f"SVGP.predict_f(native=True): {refusal}")
+    if native is not False and refusal is None:
+      from . import ops
+      Z, ls, var, beta, C, mean_c = (None if t is None else t.detach() for t in self._cache.pre(self, X2.device))
+      mean_g, var_g = ops.predict_se(X2.detach(), Z, ls, var, beta, C, None)
+    else:
+      mean_g, var_g = self._latent_marginals_torch(X2, kernels, Zs, family)
+    if coreg:
+      W = self.kernel.W.to(mean_g)                                                # [P,L]
+      mean = mean_g @ W.T
+      var = torch.einsum("pl,nl,ql->npq", W, var_g, W) if full_output_cov else var_g @ (W * W).T
+    else:
+      mean, var = mean_g, (torch.diag_embed(var_g) if full_output_cov else var_g)
+    if isinstance(self.mean_function, Constant):
+      mean = mean + self.mean_function.c.to(mean)
+    return mean.reshape(lead + mean.shape[1:]).to(Xnew.dtype), var.reshape(lead + var.shape[1:]).to(Xnew.dtype)
+
+  def predict_y(self, Xnew: torch.Tensor, full_cov: bool = False, full_output_cov: bool = False, native: Optional[bool] = None):
+    """``predict_f`` plus ``likelihood.variance`` (on the diagonal under ``full_output_cov``); Gaussian likelihood only."""
+    mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov, native=native)
+    return _predict_y_from_f(self, "SVGP.predict_y", mean, var, full_output_cov)
+
+  def predict_log_density(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """log N(Y | predict_y(X)) per point and output, [N, P], for ``data = (X, Y)``; Gaussian likelihood only."""
+    X, Y = data
+    if not isinstance(self.likelihood, GaussianLikelihood):
+      raise NotImplementedError(f"SVGP.predict_log_density: Gaussian likelihood only, got {type(self.likelihood).__name__}")
+    mean, var = self.predict_y(X, native=native)
+    return _gaussian_log_density(Y.to(mean), mean, var)
 
   # -- training: the ELBO, its objective and the initialiser (gpflow's SVGP.elbo; models/svgp.py:41-121) --------------------------
   def _native_gram_refusal(self, X, kernels, family: int, d: int, differ: bool) -> Optional[str]:
@@ -752,6 +872,64 @@ class GPR:
 
   def packed(self, dtype, with_C: bool, device):
     return self._cache.get(self, dtype, with_C, device)
+
+  # -- prediction at deterministic points ------------------------------------------------------------------------------------
+  def predict_f(self, Xnew: torch.Tensor, full_cov: bool = False, full_output_cov: bool = False, native: Optional[bool] = None):
+    """gpflow's ``GPR.predict_f`` at Xnew [..., D], single-output as ``precompute``: (mean [..., 1], var [..., 1]), or the
+    [..., 1, 1] covariance with ``full_output_cov``.  ``native`` as ``SVGP.predict_f``: the HIP kernel on ``precompute``'s tuple
+    (Z = X, beta = (K + s2 I)^-1 (Y - c), C = -(K + s2 I)^-1), or torch (Ly^-1 Kxf; differentiable, any device and family)."""
+    if full_cov:
+      raise NotImplementedError("GPR.predict_f: full_cov=True is not implemented (marginals per point only)")
+    family = kernel_family([self.kernel])
+    Xs = self.kernel.slice(Xnew).to(DEFAULT_FLOAT)
+    lead, d = Xs.shape[:-1], Xs.shape[-1]
+    X2 = Xs.reshape(-1, d)
+    refusal = _native_predict_refusal(self, X2, [self.kernel], family, d, False)
+    if native and refusal is not None:
+      raise ValueError(f"GPR.predict_f(native=True): {refusal}")
+    if native is not False and refusal is None:
+      from . import ops
+      Z, ls, var, beta, C, c = (None if t is None else t.detach() for t in self._cache.pre(self, X2.device))
+      mean, var = ops.predict_se(X2.detach(), Z, ls, var, beta, C, c)
+    else:
+      device = X2.device
+      X, Y = (t.to(device=device, dtype=DEFAULT_FLOAT) for t in self.data)
+      if Y.shape[-1] != 1:
+        raise NotImplementedError("GPR.predict_f is single-output")
+      c = None
+      if isinstance(self.mean_function, Constant):
+        c = self.mean_function.c.to(device=device, dtype=DEFAULT_FLOAT).reshape(1)
+        Y = Y - c
+      elif not isinstance(self.mean_function, Zero):
+        raise NotImplementedError(f"GPR.predict_f: mean function {type(self.mean_function).__name__}")
+      n = X.shape[0]
+      Ly = cholesky(self.kernel.K(X) + self.likelihood.variance.to(X) * torch.eye(n, dtype=DEFAULT_FLOAT, device=device))
+      alpha = torch.linalg.solve_triangular(Ly, Y, upper=False)                   # [n,1]
+      chunk = max(1, PREDICT_CHUNK_BYTES // (8 * n))
+      means, variances = [], []
+      for start in range(0, X2.shape[0], chunk):
+        A = torch.linalg.solve_triangular(Ly, self.kernel.K(X, Xnew.reshape(-1, Xnew.shape[-1])[start:start + chunk].to(DEFAULT_FLOAT)),
+                                          upper=False)
+        means.append(A.T @ alpha)
+        variances.append((self.kernel.variance.to(A) - (A * A).sum(0))[:, None])
+      mean = torch.cat(means) if means else X2.new_zeros(0, 1)
+      var = torch.cat(variances) if variances else X2.new_zeros(0, 1)
+      if c is not None:
+        mean = mean + c
+    if full_output_cov:
+      var = var[..., None]
+    return mean.reshape(lead + mean.shape[1:]).to(Xnew.dtype), var.reshape(lead + var.shape[1:]).to(Xnew.dtype)
+
+  def predict_y(self, Xnew: torch.Tensor, full_cov: bool = False, full_output_cov: bool = False, native: Optional[bool] = None):
+    """``predict_f`` plus the noise variance."""
+    mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov, native=native)
+    return _predict_y_from_f(self, "GPR.predict_y", mean, var, full_output_cov)
+
+  def predict_log_density(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """log N(Y | predict_y(X)) per point, [N, 1], for ``data = (X, Y)``."""
+    X, Y = data
+    mean, var = self.predict_y(X, native=native)
+    return _gaussian_log_density(Y.to(mean), mean, var)
 
 
 class GPModelWrapper:

@@ -10,9 +10,11 @@ __all__ = (
     "MomentMatch",
     "dispatcher",
     "register_type",
+    "sampled_moments",
 )
 
 from .core import (Chain, LinearOperatorDiag, MomentMatch, Moments, dispatcher,
                    moment_matching, register_type)
 from .gaussian import GaussianMatch, GaussianMoments
 from . import maths, bijectors, components, models  # registers the handlers
+from .sampled import sampled_moments

@@ -980,3 +980,46 @@ def gram_se_backward(G: torch.Tensor, X: Optional[torch.Tensor], Z: torch.Tensor
                                   gls.data_ptr(), gvar.data_ptr(), ws.data_ptr(), ws.numel(), _stream(Z.device)),
         "mm_gram_se_backward")
   return gZ, gls, gvar
+
+
+_PREDICT_WS: Dict[Tuple[int, int, int, str], torch.Tensor] = {}      # (L, M, d, device) -> the K strips of mm_predict_se
+
+
+def predict_se(X: torch.Tensor, Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor, beta: torch.Tensor,
+               C: Optional[torch.Tensor] = None, mean_c: Optional[torch.Tensor] = None):
+  """``mm_predict_se`` (csrc/mm_predict.hip): mean [N,L] = K^T beta (+ mean_c) and var [N,L] = var_l + k^T C k of SE-ARD latents at the
+  points X [N,d], in float64, K formed tile by tile (no [M,N] buffer) and the symmetric C [L,M,M] read on and below its block
+  diagonal only.  Z [L,M,d], ls [L,d], var [L], beta [L,M]; ``C`` None: the mean alone, the second result is None.  Runs on the
+  current stream and can be captured once the workspace of this (L, M, d) exists (it is cached: call once before capturing).
+  Deterministic: two calls are bit-equal.  Not differentiable."""
+  _require_device(X, Z, ls, var, beta, C, mean_c)
+  if Z.ndim != 3 or ls.shape != (Z.shape[0], Z.shape[2]) or var.shape != (Z.shape[0],) or beta.shape != Z.shape[:2]:
+    raise ValueError(f"predict_se: Z [L,M,d], ls [L,d], var [L], beta [L,M] expected, got {tuple(Z.shape)}, {tuple(ls.shape)}, "
+                     f"{tuple(var.shape)}, {tuple(beta.shape)}")
+  L, M, d = Z.shape
+  if X.ndim != 2 or X.shape[1] != d:
+    raise ValueError(f"predict_se: X [N,{d}] expected, got {tuple(X.shape)}")
+  if C is not None and C.shape != (L, M, M):
+    raise ValueError(f"predict_se: C [{L},{M},{M}] expected, got {tuple(C.shape)}")
+  if mean_c is not None and mean_c.shape != (L,):
+    raise ValueError(f"predict_se: mean_c [{L}] expected, got {tuple(mean_c.shape)}")
+  for name, t in (("X", X), ("Z", Z), ("ls", ls), ("var", var), ("beta", beta), ("C", C), ("mean_c", mean_c)):
+    if t is not None and t.dtype != torch.float64:
+      raise ValueError(f"predict_se: {name} is {t.dtype}; MM_E_DTYPE: the predictive kernel is float64 only")
+  N = X.shape[0]
+  X, Z, ls, var, beta, C, mean_c = (None if t is None else t.detach().contiguous() for t in (X, Z, ls, var, beta, C, mean_c))
+  nbytes = lib().mm_predict_workspace_bytes(L, M, max(N, 1), d)
+  if nbytes == 0:
+    check(-2, "mm_predict_workspace_bytes")      # the size query's 0 is MM_E_DIM
+  key = (L, M, d, str(Z.device))
+  ws = _PREDICT_WS.get(key)
+  if ws is None or ws.numel() < nbytes:
+    ws = _PREDICT_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=Z.device)
+  mean = torch.empty(N, L, dtype=torch.float64, device=Z.device)
+  fvar = None if C is None else torch.empty(N, L, dtype=torch.float64, device=Z.device)
+  if N == 0:
+    return mean, fvar
+  check(lib().mm_predict_se(L, M, N, d, X.data_ptr(), Z.data_ptr(), ls.data_ptr(), var.data_ptr(), beta.data_ptr(), _ptr(C),
+                            _ptr(mean_c), mean.data_ptr(), _ptr(fvar), ws.data_ptr(), ws.numel(), _stream(Z.device)),
+        "mm_predict_se")
+  return mean, fvar

@@ -798,6 +798,20 @@ int mm_gram_se_backward(int L, int M, int N, int d, const double* G, const doubl
                         const double* var, double* gZ, double* gls, double* gvar, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ---- predictive mean and variance at deterministic points (csrc/mm_predict.hip, schedule in csrc/mm_predict.h; f64, row-major) ----
+ * mm_predict_se: X [N,d], Z [L,M,d], ls [L,d], var [L], beta [L,M], C [L,M,M] SYMMETRIC (only the blocks on and below the diagonal
+ *   are read), mean_c [L] or NULL ->
+ *     mean[n][l] = sum_m K_l[m][n] beta_l[m] (+ mean_c[l]),   fvar[n][l] = var_l + sum_ij K_l[i][n] C_l[i][j] K_l[j][n],
+ *   K_l[m][n] as mm_gram_se's.  With beta = Kuu^-1 u and C = Kuu^-1 (S - Kuu) Kuu^-1 (what a packed model is built from) these are the
+ *   marginals of gpflow's predict_f per latent.  C == NULL and fvar == NULL together: the mean alone (MM_E_ARG when only one is NULL).
+ *   K is formed tile by tile and never stored beyond one strip per workgroup of a capped grid: mm_predict_workspace_bytes depends
+ *   on M alone (it ignores N; > 0 for every accepted shape, 0 for a rejected one).  No atomics: two calls are bit-equal.
+ * Any L, M, N >= 1, 1 <= d <= MM_DMAX, M <= 2^20; MM_E_DIM otherwise; MM_E_WORKSPACE for a workspace below the query's size. */
+size_t mm_predict_workspace_bytes(int L, int M, int N, int d);
+int mm_predict_se(int L, int M, int N, int d, const double* X, const double* Z, const double* ls, const double* var,
+                  const double* beta, const double* C, const double* mean_c, double* mean, double* fvar, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
