@@ -15,6 +15,7 @@
 #include "mm_common.h"
 #include "mm_compose.h"
 #include "mm_adjoint.h"
+#include "mm_adjoint_lds.h"
 
 // mm_backward.hip / mm_bwd_f32.hip
 int mm_backward_sums_impl(const char* pk, const MMModelLayout& ml, const char* ws, const MMWorkspaceLayout& wl, int L, int M, int d,
@@ -525,13 +526,7 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd(MMComposeDims D, double
   for (int i = lane; i < nx; i += 64) cm[i] = gm1[i];
   for (int i = lane; i < nx * nx; i += 64) cS[i] = gS1[i];
 }
-static inline size_t mm_tail_bwd_lds(int nx, int ne, int nd) {
-  int wk = mma_cost_bwd_scratch(ne);
-  const int e = mma_encode_bwd_scratch(nx, ne - nx), st = mma_step_bwd_scratch(nx, nd);
-  if (e > wk) wk = e;
-  if (st > wk) wk = st;
-  return (size_t)(ne + ne * ne + nx * ne + nx + nx * nx + wk + 8) * sizeof(double);
-}
+// (its LDS: mm_tail_bwd_lds, mm_adjoint_lds.h)
 
 // k_policy_head_bwd_small: grid B, 256 threads.  Reads cmd, cSdd, ccp; writes cme, cSee (the adjoint of the encoding of x_h
 // through the policy and the joint); accumulates the packed policy's gradient into gpar [B][mm_policy_grad_len].
@@ -587,10 +582,7 @@ __global__ __launch_bounds__(256) void k_policy_head_bwd_small(int M, int ne, do
   for (int idx = threadIdx.x; idx < ne * ne; idx += 256) cSee[(size_t)b * ne * ne + idx] = gSee[idx] + gSig[idx];
   if (!ok && threadIdx.x == 0 && status) { atomicMax(status, (int)gridDim.x - b); status[1] = 0; }
 }
-static inline size_t mm_policy_bwd_lds(int M, int ne) {
-  const int nd = ne + 1;
-  return (size_t)(4 * ne + 2 * ne * ne + 4 + nd + nd * nd + mma_policy_small_bwd_scratch(M, ne, 256) + 8) * sizeof(double);
-}
+// (its LDS: mm_policy_bwd_lds, mm_adjoint_lds.h)
 
 // k_compose_encode_bwd0: grid B, 64 threads: the adjoint of the initial state.
 __global__ __launch_bounds__(64) void k_compose_encode_bwd0(MMComposeDims D, const double* __restrict__ x0m, const double* __restrict__ x0S,

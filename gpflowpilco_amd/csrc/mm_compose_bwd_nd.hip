@@ -25,6 +25,7 @@
 #include "mm_common.h"
 #include "mm_compose.h"
 #include "mm_adjoint_nd.h"
+#include "mm_adjoint_lds.h"
 #include "mm_mix.h"
 
 #define MMB_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -99,13 +100,7 @@ __global__ __launch_bounds__(64) void k_compose_tail_bwd_nd(MMComposeDims D, dou
   for (int i = lane; i < nx; i += 64) cm[i] = gm1[i];
   for (int i = lane; i < nx * nx; i += 64) cS[i] = gS1[i];
 }
-static inline size_t mm_tail_bwd_nd_lds(int nx, int ne, int nd) {
-  int wk = mma_cost_bwd_scratch(ne);
-  const int e = mma_encode_bwd_scratch(nx, ne - nx), st = mma_step_bwd_scratch(nx, nd);
-  if (e > wk) wk = e;
-  if (st > wk) wk = st;
-  return (size_t)(ne + ne * ne + nx * ne + nx + nx * nx + wk + 8) * sizeof(double);
-}
+// (its LDS: mm_tail_bwd_nd_lds, mm_adjoint_lds.h)
 
 // k_policy_head_bwd_nd: grid B, 256 threads.  Sums the drift match's (latent | pair) items [B][nitems][nd^2 + nd] onto the
 // bookkeeping's part cSdd; writes cme, cSee (the adjoint of the encoding of x_h through the policy and the joint); accumulates the
@@ -158,19 +153,7 @@ __global__ __launch_bounds__(256) void k_policy_head_bwd_nd(int M, int ne, int n
   for (int idx = threadIdx.x; idx < ne * ne; idx += 256) cSee[(size_t)b * ne * ne + idx] = gSee[idx] + gSig[idx];
   if (!ok && threadIdx.x == 0 && status) { atomicMax(status, (int)gridDim.x - b); status[1] = 0; }
 }
-static inline size_t mm_policy_bwd_nd_lds(int M, int ne, int nu) {
-  const int nd = ne + nu;
-  return (size_t)(2 * ne + 2 * ne * ne + ne * nu + 3 * nu + nu * nu + mma_head_bwd_nd_scratch(ne, nu) + nd + nd * nd
-                  + mma_policy_nd_bwd_scratch(M, ne, 256) + 8) * sizeof(double);
-}
-
-// the _wide entries' LDS: mm_policy_bwd_nd_lds, but with one action -- no pair item runs -- without the pair item's scratch
-static inline size_t mm_policy_bwd_wide_lds(int M, int ne, int nu) {
-  if (nu > 1) return mm_policy_bwd_nd_lds(M, ne, nu);
-  const int nd = ne + nu;
-  return (size_t)(2 * ne + 2 * ne * ne + ne * nu + 3 * nu + nu * nu + mma_head_bwd_nd_scratch(ne, nu) + nd + nd * nd
-                  + mma_policy_small_bwd_scratch(M, ne, 256) + ne * ne + 2 * ne + 8) * sizeof(double);
-}
+// (its LDS: mm_policy_bwd_nd_lds, and mm_policy_bwd_wide_lds for the _wide entries: mm_adjoint_lds.h)
 
 // shapes the sweep takes (see the header comment): ne <= ne_max = 8 (the _nd entries) or 16 (the _wide entries)
 #define MMB_ND_NE 8
