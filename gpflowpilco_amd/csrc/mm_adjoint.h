@@ -22,8 +22,8 @@
 
 #define MMA_FN template <class Ctx> __host__ __device__ inline
 
-// one wave of a workgroup working on its own data (d x d items handled by several waves at once): LDS traffic of a
-// single wave is processed in order, so a wave-scope fence (no reordering by the compiler) is all a phase boundary needs
+// one wave of a workgroup working on its own data (wave 0 in the wide inverse below): LDS traffic of a single wave is
+// processed in order, so a wave-scope fence (no reordering by the compiler) is all a phase boundary needs
 struct MMAWaveCtx {
   __device__ void stamp(int) const {}
   __device__ int lane() const { return (int)(threadIdx.x & 63u); }
@@ -44,32 +44,9 @@ struct MMADevCtx {
   __device__ int lane() const { return (int)threadIdx.x; }
   __device__ int nl() const { return (int)blockDim.x; }
   __device__ void sync() const { __syncthreads(); }
-  // groups = waves: independent small items are dealt to them and run concurrently in sub()
+  // groups = waves: the one-wave dense fast paths below run in group 0 and the other waves wait at the barrier
   __device__ int group() const { return (int)(threadIdx.x >> 6); }
   __device__ int ngroups() const { return (int)(blockDim.x >> 6); }
-  __device__ MMAWaveCtx sub() const { return MMAWaveCtx(); }
-  // sum of v[k] over all lanes of the workgroup, result in every lane; scratch: ngroups() * N doubles
-  template <int N>
-  __device__ void reduce(double (&v)[N], double* scratch) const {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    const int g = group(), ng = ngroups();
-    if ((threadIdx.x & 63u) == 0) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) scratch[g * N + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      double s = 0.0;
-      for (int t = 0; t < ng; ++t) s += scratch[t * N + k];
-      v[k] = s;
-    }
-    __syncthreads();
-  }
 };
 struct MMAHostCtx {
   __host__ __device__ void stamp(int) const {}
@@ -78,9 +55,6 @@ struct MMAHostCtx {
   __host__ __device__ void sync() const {}
   __host__ __device__ int group() const { return 0; }
   __host__ __device__ int ngroups() const { return 1; }
-  __host__ __device__ MMAHostCtx sub() const { return MMAHostCtx(); }
-  template <int N>
-  __host__ __device__ void reduce(double (&)[N], double*) const {}
 };
 
 #define MMA_INV_SQRT_2PI 0.39894228040143267794
@@ -204,18 +178,6 @@ __device__ inline double mma_gj_spd8(double a, int d, bool* ok, double* logdet) 
   for (int off = 32; off > 0; off >>= 1) ld += __shfl_xor(ld, off, 64);
   *logdet = ld;
   return a;
-}
-
-__device__ inline double mma_spd_inverse(MMAWaveCtx c, double* A, double* Y, int d, int dp, bool* ok) {
-  if (d > 8) return mma_spd_inverse<MMAWaveCtx>(c, A, Y, d, dp, ok);
-  const int lane = c.lane(), i = lane >> 3, j = lane & 7;
-  const bool in = i < d && j < d;
-  c.sync();
-  double ld;
-  const double a = mma_gj_spd8(in ? A[i * dp + j] : (i == j ? 1.0 : 0.0), d, ok, &ld);
-  if (in) A[i * dp + j] = a;
-  c.sync();
-  return ld;
 }
 
 // whole workgroup: wave 0 does the work, the log-determinant reaches every lane through Y[0]

@@ -42,8 +42,8 @@ static const double kNaN = std::numeric_limits<double>::quiet_NaN();
 
 // ---- the threaded execution context ------------------------------------------------------------------------------------------------
 struct Team {
-  int nl; bool nosync; pthread_barrier_t bar; V red;
-  Team(int n, bool ns) : nl(n), nosync(ns), red((size_t)n * 16, 0.0) { pthread_barrier_init(&bar, nullptr, (unsigned)n); }
+  int nl; bool nosync; pthread_barrier_t bar;
+  Team(int n, bool ns) : nl(n), nosync(ns) { pthread_barrier_init(&bar, nullptr, (unsigned)n); }
   ~Team() { pthread_barrier_destroy(&bar); }
 };
 struct MMATeamCtx {
@@ -58,16 +58,6 @@ struct MMATeamCtx {
   }
   __host__ __device__ int group() const { return 0; }
   __host__ __device__ int ngroups() const { return 1; }
-  __host__ __device__ MMATeamCtx sub() const { return *this; }
-  // sum over the lanes, result in every lane: through the team's own scratch (nl * N doubles), two barriers
-  template <int N>
-  __host__ __device__ void reduce(double (&v)[N], double*) const {
-    static_assert(N <= 16, "Team::red holds 16 doubles per lane");
-    for (int k = 0; k < N; ++k) t->red[(size_t)ln * N + k] = v[k];
-    sync();
-    for (int k = 0; k < N; ++k) { double s = 0.0; for (int l = 0; l < t->nl; ++l) s += t->red[(size_t)l * N + k]; v[k] = s; }
-    sync();
-  }
 };
 
 // nl threads that live for the whole program (starting 256 threads per case costs more than the cases): a job starts and ends at

@@ -43,35 +43,50 @@ def gen(d, N=N, seed=None):
   return mean, cov, target, W
 
 
-def eliminate(mean, cov, target, W, ft=np.longdouble, mutation=None):
-  """-det(I + S W)^-1/2 exp(-1/2 err^T W y), (I + S W) y = err, by Gaussian elimination with partial pivoting on [I + S W | err]
-  in ``ft``, one element at a time.  -> (cost [N] in ``ft``, swapped [N, d - 1] bool: column k exchanged rows in element n).
-  ``mutation``: a wrong swap branch, for test_a_wrong_row_exchange_misses_the_bar -- "no_exchange" (the branch never taken),
+def eliminate_system(A, R, ft=np.longdouble, mutation=None):
+  """A X = R (A [n, n], R [n, nr]) by Gaussian elimination with partial pivoting on [A | R] in ``ft``: the pivot of step k is the
+  first largest |entry| of column k in rows k .. n-1.  -> (X [n, nr], det(A) with its sign, rows [n] int: the row exchanged with
+  row k at step k, k itself where none was).  ``mutation``: a wrong swap branch -- "no_exchange" (the branch never taken),
   "rhs_stays" (the matrix rows move, the right-hand side does not), "no_sign" (the determinant's sign is not flipped)."""
+  d = A.shape[0]
+  A = np.concatenate([np.asarray(A, dtype=ft), np.asarray(R, dtype=ft)], axis=1)
+  nr = A.shape[1] - d
+  det = ft(1.0)
+  rows = np.arange(d)
+  for k in range(d):
+    p = k + int(np.argmax(np.abs(A[k:, k])))                          # (argmax: the first largest, as the kernel's strict >)
+    if p != k and mutation != "no_exchange":
+      cols = d if mutation == "rhs_stays" else d + nr
+      A[[k, p], :cols] = A[[p, k], :cols]
+      if mutation != "no_sign":
+        det = -det
+      rows[k] = p
+    det = det * A[k, k]
+    for i in range(k + 1, d):
+      A[i, k:] = A[i, k:] - (A[i, k] / A[k, k]) * A[k, k:]
+  X = np.zeros((d, nr), dtype=ft)
+  for r in range(nr):
+    y = np.zeros(d, dtype=ft)
+    for i in range(d - 1, -1, -1):
+      y[i] = (A[i, d + r] - A[i, i + 1:d] @ y[i + 1:]) / A[i, i]
+    X[:, r] = y
+  return X, det, rows
+
+
+def eliminate(mean, cov, target, W, ft=np.longdouble, mutation=None):
+  """-det(I + S W)^-1/2 exp(-1/2 err^T W y), (I + S W) y = err, by ``eliminate_system`` on [I + S W | err] in ``ft``, one element
+  at a time.  -> (cost [N] in ``ft``, swapped [N, d - 1] bool: column k exchanged rows in element n).
+  ``mutation``: a wrong swap branch of ``eliminate_system``, for test_a_wrong_row_exchange_misses_the_bar."""
   n_el, d = mean.shape
   Wf = np.asarray(W, dtype=ft)
   cost = np.zeros(n_el, dtype=ft)
   swapped = np.zeros((n_el, max(d - 1, 0)), dtype=bool)
   for n in range(n_el):
     err = np.asarray(mean[n], dtype=ft) - np.asarray(target, dtype=ft)
-    A = np.concatenate([np.eye(d, dtype=ft) + np.asarray(cov[n], dtype=ft) @ Wf, err[:, None]], axis=1)
-    det = ft(1.0)
-    for k in range(d):
-      p = k + int(np.argmax(np.abs(A[k:, k])))                        # (argmax: the first largest, as the kernel's strict >)
-      if p != k and mutation != "no_exchange":
-        cols = d if mutation == "rhs_stays" else d + 1
-        A[[k, p], :cols] = A[[p, k], :cols]
-        if mutation != "no_sign":
-          det = -det
-        swapped[n, k] = True
-      det = det * A[k, k]
-      for i in range(k + 1, d):
-        A[i, k:] = A[i, k:] - (A[i, k] / A[k, k]) * A[k, k:]
-    y = np.zeros(d, dtype=ft)
-    for i in range(d - 1, -1, -1):
-      y[i] = (A[i, d] - A[i, i + 1:d] @ y[i + 1:]) / A[i, i]
+    y, det, rows = eliminate_system(np.eye(d, dtype=ft) + np.asarray(cov[n], dtype=ft) @ Wf, err[:, None], ft=ft, mutation=mutation)
+    swapped[n] = (rows != np.arange(d))[:d - 1]
     with np.errstate(invalid="ignore"):
-      cost[n] = -np.exp(ft(-0.5) * (err @ (Wf @ y))) / np.sqrt(det)
+      cost[n] = -np.exp(ft(-0.5) * (err @ (Wf @ y[:, 0]))) / np.sqrt(det)
   return cost, swapped
 
 
