@@ -32,6 +32,9 @@ MM_SUMS_CURRENT = 1024
 # the Euclidean bound at every site / no bound-based skipping at all
 MM_ISTAGE_OLD_SKIP_BOUND = 1 << 26
 MM_ISTAGE_NO_BOUND_SKIP = 1 << 27
+# internal A/B bit of the forward's f64 weight moments (csrc/mm_common.h; results are bit-identical): the 64 x 128 GEMM tiling and
+# the one-workgroup-per-item contraction
+MM_ISTAGE_OLD_WMOM = 1 << 28
 
 ERRORS = {
     -1: "MM_E_ARG: NULL pointer or non-positive size",

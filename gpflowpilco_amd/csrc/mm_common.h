@@ -38,6 +38,10 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 //                     screening product, and every item with a collapsed or dense group is listed
 #define MM_ISTAGE_OLD_SKIP_BOUND (1 << 26)
 #define MM_ISTAGE_NO_BOUND_SKIP (1 << 27)
+// f64 weight moments of the forward (mm_moments.hip): take k_wmom_gemm's 64 x 128 column blocks and the one-workgroup-per-item
+// k_spoly even where the one-pass tiling k_wmom_gemm1 and the one-wave-per-item contraction apply -- A/B tests and measurements on
+// one build; every moment the forward reads, and s12, are bit-identical
+#define MM_ISTAGE_OLD_WMOM (1 << 28)
 
 // kernel families of the pathwise entries' `kernel` argument (mm_pathwise_*_kern): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
 #define MM_PW_KERNELS 3

@@ -24,12 +24,16 @@
 //                 (bank-conflict-free strides), next block's global loads in flight during the MFMAs,
 //                 split-K over MM_MOM_SPLIT slices, XCD-aware 1-D grid (tiles sharing a table slice share an L2);
 //   k_spoly     : per (b, pair) the d^n contractions above for n = 0..2 (or 0..4), one workgroup each (n = 5, 6: k_spoly56).
+//   k_wmom_gemm1 / k_spoly_wave8 : what the forward runs (mm_launch_moments): the GEMM with every column tile a row block needs formed
+//                 in one pass, and the contraction at d <= 8 with one wave per item; bit-equal to the two above, which stay for
+//                 the backward's full table (mm_launch_wmom_full), for d > 8 (k_spoly<32, 5>) and behind MM_ISTAGE_OLD_WMOM.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "mm_common.h"
 #include "mm_mono.h"
 
 typedef double f64x4m __attribute__((ext_vector_type(4)));
+typedef double f64x2m __attribute__((ext_vector_type(2)));
 
 #define MM_GEMM_RB 64        // batch rows per workgroup
 #define MM_GEMM_NB 128       // table columns per workgroup (4 waves x 32)
@@ -177,7 +181,129 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_wmom_perm: grid L, 1024 threads.  gperm[a][0 .. R) = the rows r of latent a's GEMM (R = (L - 1) B; row -> (partner, b) as in
+// k_wmom_gemm1: the same GEMM with the column width chosen per launch.  One workgroup forms ALL the column tiles (16 columns each,
+// at most MM_GEMM1_MAXT) its 64 rows need, in one pass over the weight rows: wave w owns the 16-row tile w x NT column tiles
+// (NT f64x4 accumulators), and reads one A and NT B operands per K step of 4.  The rows are taken in k_wmom_perm's order
+// throughout, so a row block behind the collapsed rows forms the NT_LO tiles below (and around) col_deg3 only, the others all
+// NT_HI.  MM_MOM_SPLIT, the K-block order and the K order inside a block are k_wmom_gemm's: every output element sees the same
+// sequence of MFMA accumulations and is bit-equal to that kernel's.
+// LDS: A as in k_wmom_gemm; B rows of NT * 16 doubles, one 16-double pad where NT is even (rows k and k + 1 then 16 eight-byte
+// banks apart for the operand read: lanes (l15, kq) and (l15, kq + 1) never meet); staged with 16-byte stores at consecutive
+// addresses from consecutive lanes.  NT = 11: 61 KB, two workgroups per CU as before; 88 accumulator registers of the 256 that
+// two waves per SIMD leave each wave.
+// Work items: (latent, row block, k slice), the k slice innermost: every XCD's range starts with its collapsed (heavy) row blocks.
+// ---------------------------------------------------------------------------------------------
+#define MM_GEMM1_MAXT 11       // (11 tiles: 61 KB of LDS; 12 would pass the 64 KB a launch gets without asking for more)
+#define MM_GEMM1_BS(NT_) ((NT_) * 16 + (((NT_) & 1) ? 0 : 16))
+#define MM_GEMM1_LDS(NT_) ((size_t)(MM_GEMM_RB * MM_GEMM_AS + MM_GEMM_KB * MM_GEMM1_BS(NT_)) * sizeof(double))
+
+template <int NT, class OutRow>
+__device__ __forceinline__ void mm_wmom_rows(const double* __restrict__ aptr, const double* __restrict__ bptr, int KMp, int nkb,
+                                             double* __restrict__ As, double* __restrict__ Bs, int tid, OutRow&& out_row) {
+  constexpr int BS = MM_GEMM1_BS(NT), W2 = NT * 8;          // W2: double2 chunks per table row
+  const int wv = tid >> 6, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
+  const int ar = tid >> 2, ak = (tid & 3) * 8;
+  // B: chunk tid + 256 i of the [32][W2] block, i < NT (32 W2 = 256 NT chunks)
+  int bsrc[NT], bdst[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int c = tid + 256 * i, row = c / W2, cp = c - row * W2;
+    bsrc[i] = row * KMp + 2 * cp;
+    bdst[i] = row * BS + 2 * cp;
+  }
+  f64x2m ra[4], rbv[NT];
+  f64x4m acc[NT];
+#define MM_G1_LOAD(kb_)                                                                                             \
+  do {                                                                                                              \
+    const double* ap_ = aptr + (kb_) * MM_GEMM_KB;                                                                  \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const f64x2m*>(ap_ + 2 * i);           \
+    const double* bp_ = bptr + (size_t)(kb_) * MM_GEMM_KB * KMp;                                                    \
+    _Pragma("unroll") for (int i = 0; i < NT; ++i) rbv[i] = *reinterpret_cast<const f64x2m*>(bp_ + bsrc[i]);       \
+  } while (0)
+#pragma unroll
+  for (int ct = 0; ct < NT; ++ct) acc[ct] = (f64x4m){0.0, 0.0, 0.0, 0.0};
+  MM_G1_LOAD(0);
+  for (int kb = 0; kb < nkb; ++kb) {
+    __syncthreads();                                        // the previous block's MFMA operands have been read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<f64x2m*>(&As[ar * MM_GEMM_AS + ak + 2 * i]) = ra[i];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) *reinterpret_cast<f64x2m*>(&Bs[bdst[i]]) = rbv[i];
+    __syncthreads();
+    MM_G1_LOAD(kb + 1 < nkb ? kb + 1 : kb);                 // unconditional (clamped): in flight during the MFMAs
+#pragma unroll
+    for (int s = 0; s < MM_GEMM_KB / 4; ++s) {
+      const double av = As[(wv * 16 + l15) * MM_GEMM_AS + 4 * s + kq];
+      double bv[NT];
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) bv[ct] = Bs[(4 * s + kq) * BS + ct * 16 + l15];
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[ct], acc[ct], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double* o = out_row(r);
+    if (o == nullptr) continue;
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct) o[ct * 16] = acc[ct][r];
+  }
+#undef MM_G1_LOAD
+}
+
+template <int NT_HI, int NT_LO>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_wmom_gemm1(
+    const double* __restrict__ whR, const double* __restrict__ whC, const double* __restrict__ Zm, int KMp, int L, int Mp, int B,
+    int Po, int nrb, int nwork, int col0, const int* __restrict__ gperm, double* __restrict__ mom) {
+  static_assert(NT_LO <= NT_HI && NT_HI <= MM_GEMM1_MAXT, "column tiles per workgroup");
+  const int orig = blockIdx.x;
+  const int xcd = orig & 7, slot = orig >> 3;
+  const int qn = nwork >> 3, rn = nwork & 7;
+  int wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
+  const int ks = wi % MM_MOM_SPLIT; wi /= MM_MOM_SPLIT;
+  const int rb = wi % nrb; wi /= nrb;
+  const int a = wi;
+  const int R = (L - 1) * B;
+  auto row_item = [&](int r, int& b, int& po, int& side) {   // as in k_wmom_gemm
+    const int which = r / B;
+    b = r - which * B;
+    const int ap = which < a ? which : which + 1;
+    const int lo = ap < a ? ap : a, hi = ap < a ? a : ap;
+    po = lo * (L - 1) - lo * (lo - 1) / 2 + (hi - lo - 1);
+    side = ap < a ? 1 : 0;
+  };
+  const int* perm = gperm != nullptr ? gperm + (size_t)a * R : nullptr;
+  // (NT_LO < NT_HI is launched with gperm alone: the tiles from NT_LO on hold cubic monomials only, read by collapsed items)
+  const bool all_tiles = NT_LO == NT_HI || rb * MM_GEMM_RB < gperm[(size_t)L * R + a];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
+  const int kslice = Mp / MM_MOM_SPLIT;
+  const int k_begin = ks * kslice, nkb = kslice / MM_GEMM_KB;
+
+  extern __shared__ double sm_g1[];                         // MM_GEMM1_LDS(NT_HI) bytes
+  double* As = sm_g1;
+  double* Bs = sm_g1 + MM_GEMM_RB * MM_GEMM_AS;
+
+  int arow = rb * MM_GEMM_RB + (tid >> 2);
+  arow = arow < R ? arow : R - 1;                           // rows past the end recompute the last one (not stored)
+  int ab, apo, aside;
+  row_item(perm ? perm[arow] : arow, ab, apo, aside);
+  const double* aptr = (aside ? whC : whR) + ((size_t)ab * Po + apo) * Mp + k_begin + (tid & 3) * 8;
+  const double* bptr = Zm + ((size_t)a * Mp + k_begin) * KMp + col0;
+
+  // output row of accumulator register r (lane (l15 = column, kq) <-> row kq + 4 r of the wave's 16 x 16 tiles); nullptr past R
+  auto out_row = [&](int r) -> double* {
+    const int row = rb * MM_GEMM_RB + wv * 16 + kq + 4 * r;
+    if (row >= R) return nullptr;
+    int b, po, side;
+    row_item(perm ? perm[row] : row, b, po, side);
+    return mom + ((((size_t)b * Po + po) * 2 + side) * MM_MOM_SPLIT + ks) * KMp + col0 + l15;
+  };
+  if (all_tiles) mm_wmom_rows<NT_HI>(aptr, bptr, KMp, nkb, As, Bs, tid, out_row);
+  else mm_wmom_rows<NT_LO>(aptr, bptr, KMp, nkb, As, Bs, tid, out_row);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_wmom_perm: grid L, 1024 threads. gperm[a][0 .. R) = the rows r of latent a's GEMM (R = (L - 1) B; row -> (partner, b) as in
 // k_wmom_gemm) ordered by collapse class (mm_common.h: MM_C6_X5_2), the collapsed classes first in their natural order, the others
 // behind them from the back; three counts behind the permutations.  Two passes (class totals, placement), 1024 rows at a time.
 // ---------------------------------------------------------------------------------------------
@@ -404,6 +530,147 @@ __global__ __launch_bounds__(256) void k_spoly(const double* __restrict__ mom, i
 #undef MM_PADI
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_spoly_wave8: k_spoly<8, 3> with ONE WAVE per (b, pair) and no workgroup barrier: MM_SPW_WAVES items per workgroup, each wave on
+// its own LDS slice; the phases of an item are ordered by the wave's own LDS queue (mm_wave_sync_m: a compiler fence, no
+// s_barrier).  The n = 3 pass has 64 fibres, one per lane.  Only the columns the item uses are summed over the k slices: below
+// off3, or below off4 for a collapsed item -- the GEMM forms no others for it.  The degree is fixed at 3: what the forward takes from
+// the f64 moments at d <= 8 (mm_launch_moments); the quartic arms of k_spoly have no counterpart here.
+// s12 is bit-equal to k_spoly's: lane l plays that kernel's threads l, l + 64, l + 128, l + 192 (virtual thread v = 0..3) with one
+// `total` / `part` accumulator each and the stride of 256 in every dot; the final sum is mm_block_sum256m's -- the shuffle tree
+// per virtual wave, then red[0] + red[1] + red[2] + red[3].  Filling T, the fibre transforms and the dmu contractions are
+// per-element and do not depend on who runs them.
+// ---------------------------------------------------------------------------------------------
+#define MM_SPW_WAVES 4
+__device__ __forceinline__ void mm_wave_sync_m() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// doubles of one wave's slice: T [8^3], U [8^2] (both padded), ncs row-side and ncs column-side moments, G, dmu
+static inline int mm_spw_slice(int ncs) { return 512 + 16 + 64 + 2 + 2 * ncs + 64 + 8; }
+
+__global__ __launch_bounds__(64 * MM_SPW_WAVES) void k_spoly_wave8(const double* __restrict__ mom, int KMp, const double* __restrict__ pairmat,
+                                                                   const double* __restrict__ zbar, const unsigned int* __restrict__ amax,
+                                                                   const unsigned int* __restrict__ amaxc, const float* __restrict__ mu,
+                                                                   int L, int d, int P, int B, int allow_collapse,
+                                                                   int off1, int off2, int off3, int off4, int ncs, int slice,
+                                                                   const short* __restrict__ rtab, double c0,
+                                                                   double* __restrict__ s12) {
+  constexpr int DK = 8, LB = 3, DEG = 3;
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int Po = P - L;
+  const int item = blockIdx.x * MM_SPW_WAVES + wv;
+  if (item >= B * Po) return;                              // (whole waves; no workgroup barrier follows)
+  const int b = item / Po, po = item - b * Po, p = L + po;
+  int a, a2;
+  mm_decode_pair_m(p, L, a, a2);
+  constexpr int dn = 1 << (LB * DEG);
+#define MM_PADI(i_) ((i_) + ((i_) >> 5))
+  double* T = sm + (size_t)wv * slice;
+  double* U = T + MM_PADI(dn);
+  double* nh = U + MM_PADI(dn >> LB);
+  double* qh = nh + ncs;
+  double* Gs = qh + ncs;
+  double* dmu = Gs + DK * DK;
+  const bool coll = allow_collapse && mm_item_collapsed(amaxc[(size_t)b * Po + po]);
+  const int nmax = coll ? DEG : 2;
+  {
+    const int ncol = coll ? off4 : off3;                   // columns of degree <= nmax
+    const double* nm = mom + (((size_t)b * Po + po) * 2 + 0) * MM_MOM_SPLIT * KMp;
+    const double* qm = mom + (((size_t)b * Po + po) * 2 + 1) * MM_MOM_SPLIT * KMp;
+    for (int k = lane; k < ncol; k += 64) {                // fixed summation order of the split-K partials
+      double sn = 0.0, sq = 0.0;
+#pragma unroll
+      for (int t = 0; t < MM_MOM_SPLIT; ++t) { sn += nm[t * KMp + k]; sq += qm[t * KMp + k]; }
+      nh[k] = sn; qh[k] = sq;
+    }
+    const double* pm = pairmat + ((size_t)b * P + p) * (d * d + 1);
+    {
+      const int i = lane >> LB, j = lane & (DK - 1);
+      Gs[lane] = (i < d && j < d) ? pm[i * d + j] : 0.0;
+    }
+    const bool rcen = mm_rows_recentred(amax[(size_t)b * Po + po]);
+    if (lane < DK) dmu[lane] = (lane < d && !rcen) ? (double)mu[(size_t)b * d + lane] - zbar[a * d + lane] : 0.0;
+  }
+  mm_wave_sync_m();
+  double Gr[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) Gr[i] = Gs[i];
+  double total[4] = {0.0, 0.0, 0.0, 0.0};                  // k_spoly's per-thread partials of threads lane + 64 v
+  for (int n = nmax; n >= 1; --n) {
+    const double an = n == 1 ? 1.0 : n == 2 ? 0.5 : c0;
+    const int dsz = 1 << (LB * n);
+    const int offn = n == 1 ? off1 : n == 2 ? off2 : off3;
+    const short* rtn = rtab + (((1 << (LB * n)) - DK) / (DK - 1));
+    for (int idx = lane; idx < dsz; idx += 64) {
+      const int r = rtn[idx];
+      T[MM_PADI(idx)] = r >= 0 ? qh[offn + r] : 0.0;
+    }
+    mm_wave_sync_m();
+    for (int t = 0; t < n; ++t) {
+      const int sh = LB * t, nfib = dsz >> LB;
+      for (int f = lane; f < nfib; f += 64) {
+        const int lo = f & ((1 << sh) - 1), hi = f >> sh;
+        const int base = (hi << (sh + LB)) + lo;
+        double v[DK];
+#pragma unroll
+        for (int l = 0; l < DK; ++l) v[l] = T[MM_PADI(base + (l << sh))];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          double s = 0.0;
+#pragma unroll
+          for (int l = 0; l < 8; ++l) s = fma(Gr[k * 8 + l], v[l], s);
+          T[MM_PADI(base + (k << sh))] = s;
+        }
+      }
+      mm_wave_sync_m();
+    }
+    double* cur = T;
+    double* oth = U;
+    int ksz = dsz;
+    double sign_binom = 1.0;
+    for (int k = n; k >= 0; --k) {
+      const int offk = k == 0 ? 0 : k == 1 ? off1 : k == 2 ? off2 : off3;
+      const short* rtk = rtab + (k ? (((1 << (LB * k)) - DK) / (DK - 1)) : 0);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        double part = 0.0;
+        for (int idx = lane + 64 * v; idx < ksz; idx += 256) {
+          const int r = k ? rtk[idx] : 0;
+          if (r >= 0) part = fma(cur[MM_PADI(idx)], nh[offk + r], part);
+        }
+        total[v] = fma(an * sign_binom, part, total[v]);
+      }
+      if (k == 0) break;
+      const int nsz = ksz >> LB;
+      for (int idx = lane; idx < nsz; idx += 64) {
+        double s = 0.0;
+#pragma unroll
+        for (int l = 0; l < DK; ++l) s = fma(cur[MM_PADI(l * nsz + idx)], dmu[l], s);
+        oth[MM_PADI(idx)] = s;
+      }
+      mm_wave_sync_m();
+      double* tsw = cur; cur = oth; oth = tsw;
+      ksz = nsz;
+      sign_binom = -sign_binom * (double)k / (double)(n - k + 1);
+    }
+    mm_wave_sync_m();
+  }
+  // mm_block_sum256m: the tree of each virtual wave (lane 0 holds its sum), then the four in order
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) total[v] += __shfl_down(total[v], off, 64);
+  }
+  if (lane == 0) {
+    const double tot = total[0] + total[1] + total[2] + total[3];
+    s12[(size_t)b * Po + po] = tot + nh[0] * qh[0];
+  }
+#undef MM_PADI
+}
+
 // the moment GEMM alone with EVERY column block for every (b, pair) (no early exit for the cubic / quartic blocks): the
 // backward's aggregates need the moments to degree 4 whether or not the forward collapsed the item (mm_bwd_f32.hip)
 int mm_launch_wmom_full(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
@@ -417,6 +684,41 @@ int mm_launch_wmom_full(const char* packed, const MMModelLayout& ml, char* ws, c
                      (const int*)nullptr, (double*)(ws + wl.mom));
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// k_wmom_gemm1 over the columns [0, ncol) for every row of every latent.  gperm != nullptr (d <= 8, some item may collapse): rows
+// in k_wmom_perm's order, the tiles from column col_deg3 on for the row blocks that hold a collapsed row only; nullptr: natural
+// row order, every tile for every row, in passes of at most MM_GEMM1_MAXT tiles.
+typedef void (*mm_gemm1_fn)(const double*, const double*, const double*, int, int, int, int, int, int, int, int, const int*, double*);
+static mm_gemm1_fn mm_gemm1_kernel(int hi, int lo) {
+#define MM_G1(HI_, LO_) if (hi == HI_ && lo == LO_) return k_wmom_gemm1<HI_, LO_>
+  MM_G1(1, 1); MM_G1(2, 2); MM_G1(3, 3); MM_G1(4, 4); MM_G1(5, 5); MM_G1(6, 6); MM_G1(7, 7); MM_G1(8, 8); MM_G1(9, 9);
+  MM_G1(10, 10); MM_G1(11, 11);
+  MM_G1(2, 1); MM_G1(3, 1); MM_G1(4, 2); MM_G1(6, 2); MM_G1(8, 3); MM_G1(11, 3);      // d = 3 .. 8: (all tiles, tiles below degree 3)
+#undef MM_G1
+  return nullptr;
+}
+
+static int mm_launch_wmom_onepass(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl, int B, int L,
+                                  int ncol, int col_deg3, const int* gperm, hipStream_t stream) {
+  const int nrb = ((L - 1) * B + MM_GEMM_RB - 1) / MM_GEMM_RB;
+  const long long nwork_ll = (long long)L * MM_MOM_SPLIT * nrb;
+  if (nwork_ll <= 0 || nwork_ll > 0x7fffffffLL) return MM_E_DIM;
+  const int nt = (ncol + 15) / 16;                          // (16 nt <= KMp: the table's columns are padded to a multiple of 16)
+  const int npass = gperm != nullptr ? 1 : (nt + MM_GEMM1_MAXT - 1) / MM_GEMM1_MAXT;
+  const int per = (nt + npass - 1) / npass;
+  for (int p = 0; p < npass; ++p) {
+    const int hi = nt - p * per < per ? nt - p * per : per;
+    const int lo = gperm != nullptr ? (col_deg3 + 15) / 16 : hi;
+    const mm_gemm1_fn fn = mm_gemm1_kernel(hi, lo < hi ? lo : hi);
+    if (fn == nullptr || 16 * (p * per + hi) > ml.KMp) return MM_E_DIM;
+    hipLaunchKernelGGL(fn, dim3((int)nwork_ll), dim3(256), MM_GEMM1_LDS(hi), stream, (const double*)(ws + wl.whR), (const double*)(ws + wl.whC),
+                       (const double*)(packed + ml.Zm), ml.KMp, L, wl.Mp, B, wl.Po, nrb, (int)nwork_ll, 16 * p * per, gperm,
+                       (double*)(ws + wl.mom));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
 }
 
 int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
@@ -449,12 +751,23 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
     hipError_t ep = hipGetLastError();
     if (ep != hipSuccess) return (int)ep;
   }
-  hipLaunchKernelGGL(k_wmom_gemm, dim3(nwork), dim3(256), 0, stream, (const double*)(ws + wl.whR),
-                     (const double*)(ws + wl.whC), Zm, ml.KMp, L, wl.Mp, B, wl.Po, nrb, ncb, nwork, col_deg3,
-                     some ? (const unsigned int*)(ws + wl.amaxc) : (const unsigned int*)nullptr,
-                     (const double*)(packed + ml.zmax2), some ? (const int*)(ws + wl.gperm) : (const int*)nullptr, mom);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  // MM_ISTAGE_OLD_WMOM (mm_common.h): the 64 x 128 tiling and the one-workgroup-per-item contraction
+  const bool old_wmom = (flags & MM_ISTAGE_OLD_WMOM) != 0;
+  hipError_t e = hipSuccess;
+  if (old_wmom) {
+    hipLaunchKernelGGL(k_wmom_gemm, dim3(nwork), dim3(256), 0, stream, (const double*)(ws + wl.whR),
+                       (const double*)(ws + wl.whC), Zm, ml.KMp, L, wl.Mp, B, wl.Po, nrb, ncb, nwork, col_deg3,
+                       some ? (const unsigned int*)(ws + wl.amaxc) : (const unsigned int*)nullptr,
+                       (const double*)(packed + ml.zmax2), some ? (const int*)(ws + wl.gperm) : (const int*)nullptr, mom);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  } else {
+    // (no item collapses at d <= 8: the columns below degree 3 are all k_spoly reads)
+    const int ncol = (mm_moment_deg(d) >= 4 && !some) ? col_deg3 : ncol_fwd;
+    const int rc = mm_launch_wmom_onepass(packed, ml, ws, wl, B, L, ncol, col_deg3, some ? (const int*)(ws + wl.gperm) : (const int*)nullptr,
+                                          stream);
+    if (rc != 0) return rc;
+  }
   const int off1 = mm_mono_offset(1, d), off2 = mm_mono_offset(2, d), off3 = mm_mono_offset(3, d), off4 = mm_mono_offset(4, d);
 #define MM_SPOLY(DK_, LB_)                                                                                                       \
   do {                                                                                                                          \
@@ -467,7 +780,16 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
                        (const short*)(packed + ml.rtab),                                                                        \
                        (double)MM_C6_C0, (double)MM_C6_C1, (double*)(ws + wl.s12));                                             \
   } while (0)
-  if (d <= 8) MM_SPOLY(8, 3); else MM_SPOLY(32, 5);
+  if (d <= 8 && !old_wmom) {
+    const int ncs = (off4 + 7) & ~7;                        // (deg = 3 here: the columns below off4 are all an item reads)
+    const int slice = mm_spw_slice(ncs);
+    const int nitem = B * wl.Po;
+    hipLaunchKernelGGL(k_spoly_wave8, dim3((nitem + MM_SPW_WAVES - 1) / MM_SPW_WAVES), dim3(64 * MM_SPW_WAVES),
+                       (size_t)MM_SPW_WAVES * slice * sizeof(double), stream, (const double*)mom, ml.KMp,
+                       (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zbar), (const unsigned int*)(ws + wl.amax),
+                       (const unsigned int*)(ws + wl.amaxc), (const float*)mu_f32, L, d, wl.P, B, allow, off1, off2, off3, off4,
+                       ncs, slice, (const short*)(packed + ml.rtab), (double)MM_C6_C0, (double*)(ws + wl.s12));
+  } else if (d <= 8) MM_SPOLY(8, 3); else MM_SPOLY(32, 5);
 #undef MM_SPOLY
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;

@@ -5,7 +5,7 @@
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 tmp="$(mktemp -d)"
-for f in mm_kernels mm_mfma mm_f64 mm_moments6 mm_backward mm_pathwise mm_pathwise_mean mm_compose_nd mm_pathwise_policy mm_compose_bwd_nd mm_pathwise_sample; do
+for f in mm_kernels mm_mfma mm_f64 mm_moments mm_moments6 mm_backward mm_pathwise mm_pathwise_mean mm_compose_nd mm_pathwise_policy mm_compose_bwd_nd mm_pathwise_sample; do
   extra=()
   [[ $f == mm_mfma ]] && extra=(-fno-honor-nans)
   [[ $f == mm_pathwise ]] && extra=(-fno-slp-vectorize)
