@@ -21,6 +21,7 @@
 #include <math.h>
 #include <atomic>
 #include "mm_common.h"
+#include "mm_pathwise_drift.h"
 
 #define MM_PW_NS 4      // samples per workgroup (and per block of the weight stream)
 #ifndef PW_RING
@@ -984,10 +985,12 @@ __global__ __launch_bounds__(64 * PW_LDS_WAVES) void k_pathwise_lds(int S, int L
 }
 
 template <typename T>
-static int pw_launch(int S, int L, int M, int K, int d, const T* x, const T* omega, const T* phase, const T* zs,
-                     const T* hz, const double* xscale, const double* pscale, const double* var,
-                     const double* meanc, const T* wb, T* out, T* traj, int euler, double dt, hipStream_t s,
-                     T* jac = nullptr, T* cnd = nullptr, int kern = 0) {
+static int pw_launch(const MMPwDrift& D, const T* x, const MMPwOut& o, hipStream_t s) {
+  const int S = D.S, L = D.L, M = D.M, K = D.K, d = D.d, kern = D.kernel, euler = o.euler;
+  const T *omega = (const T*)D.omega_t, *phase = (const T*)D.phase, *zs = (const T*)D.zs_t, *hz = (const T*)D.hz;
+  const T* wb = (const T*)D.wb;
+  const double *xscale = D.x_scale, *pscale = D.prior_scale, *var = D.variance, *meanc = D.mean_c, dt = o.dt;
+  T *out = (T*)o.f, *traj = (T*)o.traj, *jac = (T*)o.jac, *cnd = (T*)o.abs_out;
   if (kern < 0 || kern >= MM_PW_KERNELS) return MM_E_ARG;
   if (jac && cnd) return MM_E_ARG;                  // (one extra output per pass)
   if (jac && d > 16) return MM_E_DIM;              // the Jacobian pass: d <= 8 whole groups, 8 < d <= 16 half-groups
@@ -1056,6 +1059,25 @@ static int pw_check(int S, int L, int M, int K, int d, int dtype, int kern = 0) 
   return 0;
 }
 
+// one evaluation of a drift for every caller: the entries below and the policy rollout (mm_pathwise_policy.hip)
+template <typename T>
+static int pw_eval(const MMPwDrift& D, const void* x, const MMPwOut& o, hipStream_t s) {
+  return D.beta ? pwm_launch<T>(D, (const T*)x, (T*)o.f, (T*)o.jac, s) : pw_launch<T>(D, (const T*)x, o, s);
+}
+int mm_pw_drift_eval(const MMPwDrift& D, const void* x, const MMPwOut& o, hipStream_t s) {
+  if (D.beta && (o.abs_out || o.traj || o.euler)) return MM_E_ARG;       // the mean pass writes f and its Jacobian
+  const int rc = D.beta ? pwm_check(D.S, D.L, D.M, D.d, D.dtype, D.kernel) : pw_check(D.S, D.L, D.M, D.K, D.d, D.dtype, D.kernel);
+  if (rc) return rc;
+  return D.dtype == MM_F64 ? pw_eval<double>(D, x, o, s) : pw_eval<float>(D, x, o, s);
+}
+
+// the operand list the eight sample entries share, by name
+#define PW_DRIFT(D_)                                                                                                   \
+  MMPwDrift D_;                                                                                                        \
+  D_.S = S; D_.L = L; D_.M = M; D_.K = K; D_.d = d; D_.dtype = dtype; D_.kernel = kernel;                                \
+  D_.omega_t = omega_t; D_.phase = phase; D_.zs_t = zs_t; D_.hz = hz; D_.wb = wb;                                        \
+  D_.x_scale = x_scale; D_.prior_scale = prior_scale; D_.variance = variance; D_.mean_c = mean_c
+
 // the entries without a kernel argument are their _kern siblings with kernel = 0 (SquaredExponential)
 extern "C" int mm_pathwise_eval_kern(int S, int L, int M, int K, int d, int dtype,
                                      const void* x, const void* omega_t, const void* phase, const void* zs_t,
@@ -1066,14 +1088,9 @@ extern "C" int mm_pathwise_eval_kern(int S, int L, int M, int K, int d, int dtyp
   if (rc) return rc;
   if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out)
     return MM_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MM_F64)
-    return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
-                             (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, nullptr, nullptr, kernel);
-  return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
-                          (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, nullptr, nullptr, kernel);
+  PW_DRIFT(D);
+  MMPwOut o; o.f = f_out;
+  return mm_pw_drift_eval(D, x, o, (hipStream_t)stream);
 }
 extern "C" int mm_pathwise_eval(int S, int L, int M, int K, int d, int dtype,
                                 const void* x, const void* omega_t, const void* phase, const void* zs_t,
@@ -1093,14 +1110,9 @@ extern "C" int mm_pathwise_eval_bound_kern(int S, int L, int M, int K, int d, in
   if (rc) return rc;
   if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out || !abs_out)
     return MM_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MM_F64)
-    return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
-                             (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, nullptr, (double*)abs_out, kernel);
-  return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
-                          (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, nullptr, (float*)abs_out, kernel);
+  PW_DRIFT(D);
+  MMPwOut o; o.f = f_out; o.abs_out = abs_out;
+  return mm_pw_drift_eval(D, x, o, (hipStream_t)stream);
 }
 extern "C" int mm_pathwise_eval_bound(int S, int L, int M, int K, int d, int dtype,
                                       const void* x, const void* omega_t, const void* phase, const void* zs_t,
@@ -1111,21 +1123,6 @@ extern "C" int mm_pathwise_eval_bound(int S, int L, int M, int K, int d, int dty
                                      wb, f_out, abs_out, stream, 0);
 }
 
-// one evaluation f [S,L] (and, jac != NULL, d f / d x [S,L,d]) for the other translation units (mm_pathwise_policy.hip)
-int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
-                       const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
-                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel) {
-  int rc = pw_check(S, L, M, K, d, dtype, kernel);
-  if (rc) return rc;
-  if (dtype == MM_F64)
-    return pw_launch<double>(S, L, M, K, d, (const double*)x, (const double*)omega_t, (const double*)phase,
-                             (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)f_out, nullptr, 0, 0.0, s, (double*)jac, nullptr, kernel);
-  return pw_launch<float>(S, L, M, K, d, (const float*)x, (const float*)omega_t, (const float*)phase,
-                          (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                          (const float*)wb, (float*)f_out, nullptr, 0, 0.0, s, (float*)jac, nullptr, kernel);
-}
-
 extern "C" int mm_pathwise_eval_jac_kern(int S, int L, int M, int K, int d, int dtype,
                                          const void* x, const void* omega_t, const void* phase, const void* zs_t,
                                          const void* hz, const double* x_scale, const double* prior_scale,
@@ -1134,8 +1131,9 @@ extern "C" int mm_pathwise_eval_jac_kern(int S, int L, int M, int K, int d, int 
   if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;
   if (!x || !omega_t || !phase || !zs_t || !hz || !x_scale || !prior_scale || !variance || !wb || !f_out || !jac_out)
     return MM_E_ARG;
-  return mm_pathwise_launch(S, L, M, K, d, dtype, x, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
-                            f_out, jac_out, (hipStream_t)stream, kernel);
+  PW_DRIFT(D);
+  MMPwOut o; o.f = f_out; o.jac = jac_out;
+  return mm_pw_drift_eval(D, x, o, (hipStream_t)stream);
 }
 extern "C" int mm_pathwise_eval_jac(int S, int L, int M, int K, int d, int dtype,
                                     const void* x, const void* omega_t, const void* phase, const void* zs_t,
@@ -1158,17 +1156,13 @@ extern "C" int mm_pathwise_rollout_kern(int S, int L, int M, int K, int d, int d
   if (d != L) return MM_E_STATE;
   hipStream_t s = (hipStream_t)stream;
   const size_t es = mm_elem_size(dtype), stride = (size_t)S * d * es;
+  PW_DRIFT(D);
+  MMPwOut o; o.euler = 1; o.dt = dt;
   char* cur = (char*)x; char* nxt = (char*)x_tmp;
   for (int h = 0; h < H; ++h) {
-    char* tr = traj ? (char*)traj + (size_t)h * stride : nullptr;
-    if (dtype == MM_F64)
-      rc = pw_launch<double>(S, L, M, K, d, (const double*)cur, (const double*)omega_t, (const double*)phase,
-                             (const double*)zs_t, (const double*)hz, x_scale, prior_scale, variance, mean_c,
-                             (const double*)wb, (double*)nxt, (double*)tr, 1, dt, s, nullptr, nullptr, kernel);
-    else
-      rc = pw_launch<float>(S, L, M, K, d, (const float*)cur, (const float*)omega_t, (const float*)phase,
-                            (const float*)zs_t, (const float*)hz, x_scale, prior_scale, variance, mean_c,
-                            (const float*)wb, (float*)nxt, (float*)tr, 1, dt, s, nullptr, nullptr, kernel);
+    o.f = nxt;
+    o.traj = traj ? (char*)traj + (size_t)h * stride : nullptr;
+    rc = mm_pw_drift_eval(D, cur, o, s);
     if (rc) return rc;
     char* t = cur; cur = nxt; nxt = t;
   }

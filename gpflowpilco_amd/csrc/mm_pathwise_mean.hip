@@ -19,7 +19,7 @@
 // reproducible.  Values accumulate in f64 whatever T (the stream pass: T per lane, f64 across lanes), the Jacobian sums in T
 // as the stream pass keeps them; beta is f64 in both modes.  Centres with beta = 0 (padding) add exactly 0: their basis value
 // is finite (zs = hz = 0: e = 2^-hx <= 1).
-#include "mm_pathwise_policy_dev.h"
+#include "mm_pathwise_drift.h"
 #include "mm_pathwise_kern.h"
 
 #define PWM_MC 256      // centres per LDS chunk (f64, DK = 16: 38 KB)
@@ -130,7 +130,7 @@ __global__ __launch_bounds__((PwMean<T, DK>::NT)) void k_pw_mean(int S, int L, i
   }
 }
 
-static int pwm_check(int S, int L, int M, int d, int dtype, int kern) {
+int pwm_check(int S, int L, int M, int d, int dtype, int kern) {
   if (kern < 0 || kern >= MM_PW_KERNELS) return MM_E_ARG;     // 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
   if (S <= 0 || L <= 0 || M <= 0 || d <= 0) return MM_E_ARG;
   if (d > 16) return MM_E_DIM;                                // DK = 8 | 16: what the policy rollouts take
@@ -138,9 +138,12 @@ static int pwm_check(int S, int L, int M, int d, int dtype, int kern) {
   return 0;
 }
 
+// one evaluation f [S,L] (and, jac != NULL, d f / d x [S,L,d]); reached through mm_pw_drift_eval (mm_pathwise.hip)
 template <typename T>
-static int pwm_launch(int S, int L, int M, int d, const T* x, const T* zs, const T* hz, const double* xscale, const double* var,
-                      const double* meanc, const double* beta, T* out, T* jac, hipStream_t s, int kern) {
+int pwm_launch(const MMPwDrift& D, const T* x, T* out, T* jac, hipStream_t s) {
+  const int S = D.S, L = D.L, M = D.M, d = D.d, kern = D.kernel;
+  const T *zs = (const T*)D.zs_t, *hz = (const T*)D.hz;
+  const double *xscale = D.x_scale, *var = D.variance, *meanc = D.mean_c, *beta = D.beta;
   // samples per workgroup: the largest of 64 .. 8 that still gives the chip a workgroup per CU
   int SB = 64;
   while (SB > 8 && (size_t)((S + SB - 1) / SB) * L < 256) SB >>= 1;
@@ -160,19 +163,8 @@ static int pwm_launch(int S, int L, int M, int d, const T* x, const T* zs, const
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
-
-// one evaluation f [S,L] (and, jac != NULL, d f / d x [S,L,d]) for the policy rollout (mm_pathwise_policy.hip)
-int mm_pathwise_mean_launch(int S, int L, int M, int d, int dtype, const void* x, const void* zs_t, const void* hz,
-                            const double* x_scale, const double* variance, const double* mean_c, const double* beta, void* f_out,
-                            void* jac, hipStream_t s, int kernel) {
-  const int rc = pwm_check(S, L, M, d, dtype, kernel);
-  if (rc) return rc;
-  if (dtype == MM_F64)
-    return pwm_launch<double>(S, L, M, d, (const double*)x, (const double*)zs_t, (const double*)hz, x_scale, variance, mean_c,
-                              beta, (double*)f_out, (double*)jac, s, kernel);
-  return pwm_launch<float>(S, L, M, d, (const float*)x, (const float*)zs_t, (const float*)hz, x_scale, variance, mean_c, beta,
-                           (float*)f_out, (float*)jac, s, kernel);
-}
+template int pwm_launch<double>(const MMPwDrift&, const double*, double*, double*, hipStream_t);
+template int pwm_launch<float>(const MMPwDrift&, const float*, float*, float*, hipStream_t);
 
 extern "C" int mm_pathwise_mean_eval(int S, int L, int M, int d, int dtype, const void* x, const void* zs_t, const void* hz,
                                      const double* x_scale, const double* variance, const double* mean_c, const double* beta,
@@ -180,6 +172,9 @@ extern "C" int mm_pathwise_mean_eval(int S, int L, int M, int d, int dtype, cons
   const int rc = pwm_check(S, L, M, d, dtype, kernel);
   if (rc) return rc;
   if (!x || !zs_t || !hz || !x_scale || !variance || !beta || !f_out) return MM_E_ARG;
-  return mm_pathwise_mean_launch(S, L, M, d, dtype, x, zs_t, hz, x_scale, variance, mean_c, beta, f_out, jac_out,
-                                 (hipStream_t)stream, kernel);
+  MMPwDrift D;
+  D.S = S; D.L = L; D.M = M; D.d = d; D.dtype = dtype; D.kernel = kernel;
+  D.zs_t = zs_t; D.hz = hz; D.x_scale = x_scale; D.variance = variance; D.mean_c = mean_c; D.beta = beta;
+  MMPwOut o; o.f = f_out; o.jac = jac_out;
+  return mm_pw_drift_eval(D, x, o, (hipStream_t)stream);
 }

@@ -12,7 +12,7 @@
 //                                          nd = ne + nu drift inputs, actions in latent order (as forward_sde appends them)
 //     cost[h][s] = -exp(-(enc(x_{h+1}) - t)^T W (enc(x_{h+1}) - t) / 2)                                  (components.py:39-41)
 // Forward: per step one small kernel (k_pw_head_nd: Euler update of the previous step, cost, encoder, policy -> the drift's
-// input) and one stream pass (mm_pathwise_launch, d <= 16, as it is); the taped forward makes the stream pass also emit
+// input) and one stream pass (mm_pw_drift_eval, d <= 16, as it is); the taped forward makes the stream pass also emit
 // d f_s / d d_s [S][nx][nd] (its JAC variant).
 // Backward: samples are independent, so the WHOLE reverse sweep is one kernel (k_pw_policy_bwd_nd: thread = sample, loop over
 // the steps backwards, the state's adjoint in registers) that reads the tape -- states, drift inputs, Jacobians: no second
@@ -252,17 +252,18 @@ static inline size_t mmp_nd_bwd_lds(int pM, int ne, int nu) {
   return mmp_nd_head_lds(pM, ne, nu) + (size_t)4 * nu * (pM * ne + pM + ne + 2) * sizeof(double);
 }
 
-// everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions.  one_action: the one-action
-// entries, whose contract differs in one answer -- na > 0 without active_dims is MM_E_DIM from mm_compose_dims (after sizes and
-// dtype), where every other entry says MM_E_ARG first
-static int mmp_nd_check(int S, int M, int K, int dtype, int H, int nx, int na, int nu, const int32_t* active_dims, int policy_M,
-                        int nd_max, bool one_action, MMComposeDims& D) {
-  if (S <= 0 || M <= 0 || K <= 0 || H <= 0 || policy_M <= 0 || (!one_action && na > 0 && !active_dims)) return MM_E_ARG;
-  if (dtype != MM_F32 && dtype != MM_F64) return MM_E_DTYPE;
-  const int rc = mm_compose_dims_nd(nx, na, nu, active_dims, D);
+// everything that can be refused without a HIP call, in the order sizes -> dtype -> dimensions (forward: the drift's M and K
+// are sizes too).  one_action: the one-action entries, whose contract differs in one answer -- na > 0 without active_dims is
+// MM_E_DIM from mm_compose_dims (after sizes and dtype), where every other entry says MM_E_ARG first
+static int mmp_nd_check(const MMPwRollout& P, bool forward, MMComposeDims& D) {
+  const MMPwDrift& F = P.drift;
+  if (F.S <= 0 || (forward && (F.M <= 0 || (!F.beta && F.K <= 0))) || P.H <= 0 || P.policy_M <= 0 ||
+      (!P.one_action && P.na > 0 && !P.active_dims)) return MM_E_ARG;
+  if (F.dtype != MM_F32 && F.dtype != MM_F64) return MM_E_DTYPE;
+  const int rc = mm_compose_dims_nd(P.nx, P.na, P.nu, P.active_dims, D);
   if (rc) return rc;
   // nd_max: 8 for the _nd entries (the Jacobian pass over whole sample groups), 16 for the _wide ones (+ its half-group form)
-  if (D.nd > nd_max || policy_M > MMP_POLICY_MMAX) return MM_E_DIM;
+  if (D.nd > P.nd_max || P.policy_M > MMP_POLICY_MMAX) return MM_E_DIM;
   return 0;
 }
 
@@ -291,18 +292,30 @@ extern "C" size_t mm_pathwise_tape_bytes_mixed(int S, int H, int nx, int na, int
     default: M_(4); break;                                                             \
   }
 
+// the head's per-action constants as the kernels take them (by value; zero beyond nu)
+static MMHeadND mmp_head_constants(int nu, const double* head_scale, const double* head_shift) {
+  MMHeadND hd;
+  for (int a = 0; a < MMC_NU; ++a) { hd.scale[a] = a < nu ? head_scale[a] : 0.0; hd.shift[a] = a < nu ? head_shift[a] : 0.0; }
+  return hd;
+}
+
 template <typename T>
-static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K, int dtype, int H, double dt, const void* omega_t,
-                            const void* phase, const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
-                            const double* variance, const double* mean_c, const void* wb, const char* pp, const MMModelLayout& pl,
-                            int policy_M, const MMHeadND& hd, const T* target, const T* precis, const T* x0, T* cost,
-                            char* tape, const MMPwTapeLayout& tl, int Lg, const double* mix_W, const double* mix_c,
-                            hipStream_t s, int kernel, const double* beta) {
-  // beta != NULL: the _mean entry -- the drift is its posterior MEAN, one shared weight vector per latent in place of the stream
-  // (mm_pathwise_mean.hip: same f and Jacobian slots); omega_t, phase, prior_scale, wb and K are then not read
+static int mmp_nd_rollout_t(const MMPwRollout& P, const MMComposeDims& D, const MMModelLayout& pl, const MMPwTapeLayout& tl,
+                            const T* x0, T* cost, char* tape) {
+  // drift.beta != NULL: the _mean entry -- the drift is its posterior MEAN, one shared weight vector per latent in place of the
+  // stream (mm_pathwise_mean.hip: same f and Jacobian slots)
   // Lg > 0: the _mixed entries -- the stream pass runs with Lg latents and no latent mean straight into the tape's (latent-sized)
   // f and Jacobian slots, the head kernel mixes
-  const int nx = D.nx, ne = D.ne, nd = D.nd, Lf = Lg > 0 ? Lg : nx;
+  const int nx = D.nx, ne = D.ne, nd = D.nd, nu = P.nu, S = P.drift.S, H = P.H, policy_M = P.policy_M;
+  const int Lg = P.mixed ? P.Lg : 0, Lf = Lg > 0 ? Lg : nx;           // (Lg = 0: what the launches take for "no mixing")
+  const double dt = P.dt, *mix_W = P.mix_W, *mix_c = P.mix_c;
+  const T *target = (const T*)P.target, *precis = (const T*)P.precis;
+  const char* pp = (const char*)P.policy_packed;
+  const MMHeadND hd = mmp_head_constants(nu, P.head_scale, P.head_shift);
+  hipStream_t s = (hipStream_t)P.stream;
+  MMPwDrift drift = P.drift;                                            // one step's pass: Lf latents on the nd drift inputs
+  drift.L = Lf; drift.d = nd;
+  if (Lg > 0) drift.mean_c = nullptr;
   T* xs = (T*)(tape + tl.x); T* dins = (T*)(tape + tl.din); T* f = (T*)(tape + tl.f);
   T* jac = tl.jac != tl.total ? (T*)(tape + tl.jac) : nullptr;
   hipError_t e = hipMemcpyAsync(xs, x0, (size_t)S * nx * sizeof(T), hipMemcpyDeviceToDevice, s);
@@ -328,58 +341,45 @@ static int mmp_nd_rollout_t(const MMComposeDims& D, int nu, int S, int M, int K,
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (h == H) break;
-    T* jh = jac ? jac + (size_t)h * S * Lf * nd : nullptr;
-    const int rc = beta ? mm_pathwise_mean_launch(S, Lf, M, nd, dtype, dins + (size_t)h * S * nd, zs_t, hz, x_scale, variance,
-                                                  Lg > 0 ? nullptr : mean_c, beta, f, jh, s, kernel)
-                        : mm_pathwise_launch(S, Lf, M, K, nd, dtype, dins + (size_t)h * S * nd, omega_t, phase, zs_t, hz, x_scale,
-                                             prior_scale, variance, Lg > 0 ? nullptr : mean_c, wb, f, jh, s, kernel);
+    MMPwOut o; o.f = f; o.jac = jac ? jac + (size_t)h * S * Lf * nd : nullptr;
+    const int rc = mm_pw_drift_eval(drift, dins + (size_t)h * S * nd, o, s);
     if (rc) return rc;
   }
   return 0;
 }
 
-// the head's per-action constants as the kernels take them (by value; zero beyond nu)
-static MMHeadND mmp_head_constants(int nu, const double* head_scale, const double* head_shift) {
-  MMHeadND hd;
-  for (int a = 0; a < MMC_NU; ++a) { hd.scale[a] = a < nu ? head_scale[a] : 0.0; hd.shift[a] = a < nu ? head_shift[a] : 0.0; }
-  return hd;
+// the forward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8), _wide (nd_max = 16), _mixed (nd_max = 16,
+// mixed: Lg, mix_W, mix_c), _kern (drift.kernel: the drift's family) and _mean (drift.beta) are this function
+static int mmp_nd_rollout(const MMPwRollout& P, const void* x0, void* cost, void* tape, size_t tape_bytes, int with_jacobians) {
+  const MMPwDrift& F = P.drift;
+  if (F.kernel < 0 || F.kernel >= MM_PW_KERNELS) return MM_E_ARG;         // the drift's kernel family (mm_pathwise_eval_kern)
+  MMComposeDims D;
+  int rc = mmp_nd_check(P, true, D);
+  if (rc) return rc;
+  if (P.mixed && (P.Lg < 1 || P.Lg > P.nx)) return MM_E_DIM;
+  if ((!F.beta && (!F.omega_t || !F.phase || !F.prior_scale || !F.wb)) || !F.zs_t || !F.hz || !F.x_scale || !F.variance ||
+      !P.policy_packed || !P.head_scale || !P.head_shift || !P.target || !P.precis || !x0 || !cost || !tape ||
+      (P.mixed && !P.mix_W)) return MM_E_ARG;
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(F.S, P.H, P.nx, P.na, P.nu, P.mixed ? P.Lg : P.nx, F.dtype, with_jacobians);
+  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
+  const MMModelLayout pl = mm_model_layout(P.nu, P.policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
+  if (P.policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  if (F.dtype == MM_F64) return mmp_nd_rollout_t<double>(P, D, pl, tl, (const double*)x0, (double*)cost, (char*)tape);
+  return mmp_nd_rollout_t<float>(P, D, pl, tl, (const float*)x0, (float*)cost, (char*)tape);
 }
 
-// the forward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8), _wide (nd_max = 16), _mixed (nd_max = 16,
-// mixed: Lg, mix_W, mix_c) and _kern (kernel: the drift's family) are this function
-static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, const double* mix_c, int S, int M, int K,
-                          int dtype, int H, double dt, int nx, int na,
-                          const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
-                          const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
-                          const double* variance, const double* mean_c, const void* wb,
-                          const void* policy_packed, size_t policy_bytes, int policy_M,
-                          const double* head_scale, const double* head_shift, const void* target,
-                          const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
-                          int with_jacobians, void* stream, int kernel = 0, bool one_action = false,
-                          const double* beta = nullptr) {
-  if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;             // the drift's kernel family (mm_pathwise_eval_kern)
-  MMComposeDims D;
-  int rc = mmp_nd_check(S, M, K, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, one_action, D);
-  if (rc) return rc;
-  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
-  if (!mixed) Lg = 0;                                        // (what the launches below take for "no mixing")
-  if ((!beta && (!omega_t || !phase || !prior_scale || !wb)) || !zs_t || !hz || !x_scale || !variance || !policy_packed ||
-      !head_scale || !head_shift || !target || !precis || !x0 || !cost || !tape || (mixed && !mix_W)) return MM_E_ARG;
-  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, with_jacobians);
-  if (tape_bytes < tl.total) return MM_E_WORKSPACE;
-  const MMModelLayout pl = mm_model_layout(nu, policy_M, D.ne, MM_F64, 1);   // the f64 blocks precede the T blocks in every pack
-  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
-  const MMHeadND hd = mmp_head_constants(nu, head_scale, head_shift);
-  const char* pp = (const char*)policy_packed;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MM_F64)
-    return mmp_nd_rollout_t<double>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c,
-                                    wb, pp, pl, policy_M, hd, (const double*)target, (const double*)precis, (const double*)x0,
-                                    (double*)cost, (char*)tape, tl, Lg, mix_W, mix_c, s, kernel, beta);
-  return mmp_nd_rollout_t<float>(D, nu, S, M, K, dtype, H, dt, omega_t, phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb,
-                                 pp, pl, policy_M, hd, (const float*)target, (const float*)precis, (const float*)x0, (float*)cost,
-                                 (char*)tape, tl, Lg, mix_W, mix_c, s, kernel, beta);
-}
+// What the entries' argument lists name alike, into the fields of the same names (nothing here goes by position).
+// MMP_ROLLOUT_FIELDS: every entry; MMP_STREAM_FIELDS: the forward entries of a sampled drift.
+#define MMP_ROLLOUT_FIELDS(P_)                                                                                                   \
+  MMPwRollout P_;                                                                                                                \
+  P_.drift.S = S; P_.drift.dtype = dtype; P_.H = H; P_.dt = dt; P_.nx = nx; P_.na = na; P_.active_dims = active_dims;            \
+  P_.policy_packed = policy_packed; P_.policy_bytes = policy_bytes; P_.policy_M = policy_M; P_.target = target;                  \
+  P_.precis = precis; P_.stream = stream
+#define MMP_STREAM_FIELDS(P_)                                                                                                    \
+  P_.drift.M = M; P_.drift.K = K; P_.drift.omega_t = omega_t; P_.drift.phase = phase; P_.drift.zs_t = zs_t; P_.drift.hz = hz;    \
+  P_.drift.x_scale = x_scale; P_.drift.prior_scale = prior_scale; P_.drift.variance = variance; P_.drift.mean_c = mean_c;        \
+  P_.drift.wb = wb
+#define MMP_HEAD_FIELDS(P_) P_.nu = nu; P_.head_scale = head_scale; P_.head_shift = head_shift
 
 #define MMP_ROLLOUT_ENTRY(name_, nd_max_)                                                                                          \
   extern "C" int name_(int S, int M, int K, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,      \
@@ -388,9 +388,9 @@ static int mmp_nd_rollout(int nd_max, bool mixed, int Lg, const double* mix_W, c
                        const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
                        const double* head_shift, const void* target, const void* precis, const void* x0, void* cost, void* tape, \
                        size_t tape_bytes, int with_jacobians, void* stream) {                                                    \
-    return mmp_nd_rollout(nd_max_, false, 0, nullptr, nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase,   \
-                          zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,           \
-                          head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);           \
+    MMP_ROLLOUT_FIELDS(P); MMP_STREAM_FIELDS(P); MMP_HEAD_FIELDS(P);                                                             \
+    P.nd_max = nd_max_;                                                                                                          \
+    return mmp_nd_rollout(P, x0, cost, tape, tape_bytes, with_jacobians);                                                        \
   }
 MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_nd, 8)
 MMP_ROLLOUT_ENTRY(mm_pathwise_policy_rollout_wide, 16)
@@ -404,9 +404,9 @@ extern "C" int mm_pathwise_policy_rollout(int S, int M, int K, int dtype, int H,
                                           const void* policy_packed, size_t policy_bytes, int policy_M, double head_scale,
                                           double head_shift, const void* target, const void* precis, const void* x0, void* cost,
                                           void* tape, size_t tape_bytes, int with_jacobians, void* stream) {
-  return mmp_nd_rollout(8, false, 0, nullptr, nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, 1, omega_t, phase, zs_t, hz,
-                        x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, &head_scale, &head_shift,
-                        target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, 0, true);
+  MMP_ROLLOUT_FIELDS(P); MMP_STREAM_FIELDS(P);
+  P.nu = 1; P.head_scale = &head_scale; P.head_shift = &head_shift; P.one_action = true;       // (nd_max: 8)
+  return mmp_nd_rollout(P, x0, cost, tape, tape_bytes, with_jacobians);
 }
 
 // a coregionalised drift: the paths' operands are those of Lg latents, mean_c is not read (the constant is mix_c)
@@ -419,14 +419,14 @@ extern "C" int mm_pathwise_policy_rollout_mixed(int S, int M, int K, int dtype, 
                                                 const void* precis, const void* x0, void* cost, void* tape, size_t tape_bytes,
                                                 int with_jacobians, void* stream, int Lg, const double* mix_W,
                                                 const double* mix_c) {
-  return mmp_nd_rollout(16, true, Lg, mix_W, mix_c, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t, phase, zs_t, hz,
-                        x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M, head_scale, head_shift,
-                        target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream);
+  MMP_ROLLOUT_FIELDS(P); MMP_STREAM_FIELDS(P); MMP_HEAD_FIELDS(P);
+  P.nd_max = 16; P.mixed = true; P.Lg = Lg; P.mix_W = mix_W; P.mix_c = mix_c;
+  return mmp_nd_rollout(P, x0, cost, tape, tape_bytes, with_jacobians);
 }
 
 // the one forward entry for a drift of any kernel family (kernel: 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2): the argument
 // list of the _mixed entry plus kernel; Lg = 0 / mix_W = NULL: no mixing (then the _wide entry: nd <= 16, 1 .. 4 actions).  The
-// tape layout does not depend on the family, so the reverse sweeps above are used as they are.
+// tape layout does not depend on the family, so the reverse sweeps below are used as they are.
 extern "C" int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, int H, double dt, int nx, int na,
                                                const int32_t* active_dims, int nu, const void* omega_t, const void* phase,
                                                const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale,
@@ -437,10 +437,10 @@ extern "C" int mm_pathwise_policy_rollout_kern(int S, int M, int K, int dtype, i
                                                int with_jacobians, void* stream, int Lg, const double* mix_W,
                                                const double* mix_c, int kernel) {
   if (kernel < 0 || kernel >= MM_PW_KERNELS) return MM_E_ARG;
-  const bool mixed = Lg != 0 || mix_W != nullptr;
-  return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, K, dtype, H, dt, nx, na, active_dims, nu, omega_t,
-                        phase, zs_t, hz, x_scale, prior_scale, variance, mean_c, wb, policy_packed, policy_bytes, policy_M,
-                        head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel);
+  MMP_ROLLOUT_FIELDS(P); MMP_STREAM_FIELDS(P); MMP_HEAD_FIELDS(P);
+  P.drift.kernel = kernel;
+  P.nd_max = 16; P.mixed = Lg != 0 || mix_W != nullptr; P.Lg = Lg; P.mix_W = mix_W; P.mix_c = P.mixed ? mix_c : nullptr;
+  return mmp_nd_rollout(P, x0, cost, tape, tape_bytes, with_jacobians);
 }
 
 // the MEAN of the drift in place of its sample paths (the reference's model_uncertainty=False: the drift in a KernelRegressor):
@@ -455,12 +455,13 @@ extern "C" int mm_pathwise_policy_rollout_mean(int S, int M, int dtype, int H, d
                                                int with_jacobians, void* stream, int Lg, const double* mix_W,
                                                const double* mix_c, int kernel) {
   if (kernel < 0 || kernel >= MM_PW_KERNELS || !beta) return MM_E_ARG;
-  const bool mixed = Lg != 0 || mix_W != nullptr;
-  return mmp_nd_rollout(16, mixed, Lg, mix_W, mixed ? mix_c : nullptr, S, M, 1, dtype, H, dt, nx, na, active_dims, nu, nullptr,
-                        nullptr, zs_t, hz, x_scale, nullptr, variance, mean_c, nullptr, policy_packed, policy_bytes, policy_M,
-                        head_scale, head_shift, target, precis, x0, cost, tape, tape_bytes, with_jacobians, stream, kernel, false,
-                        beta);
+  MMP_ROLLOUT_FIELDS(P); MMP_HEAD_FIELDS(P);
+  P.drift.M = M; P.drift.zs_t = zs_t; P.drift.hz = hz; P.drift.x_scale = x_scale; P.drift.variance = variance;
+  P.drift.mean_c = mean_c; P.drift.beta = beta; P.drift.kernel = kernel;
+  P.nd_max = 16; P.mixed = Lg != 0 || mix_W != nullptr; P.Lg = Lg; P.mix_W = mix_W; P.mix_c = P.mixed ? mix_c : nullptr;
+  return mmp_nd_rollout(P, x0, cost, tape, tape_bytes, with_jacobians);
 }
+#undef MMP_STREAM_FIELDS
 
 // 0: a shape the reverse sweep does not take (see the LDS bound at the top of this file)
 static size_t mmp_nd_scratch_bytes(int nd_max, int S, int policy_M, int ne, int nu) {
@@ -480,33 +481,33 @@ extern "C" size_t mm_pathwise_backward_scratch_bytes_wide(int S, int policy_M, i
   return mmp_nd_scratch_bytes(16, S, policy_M, ne, nu);
 }
 
-// the backward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8) and _wide (nd_max = 16), unseeded (g_cost required, g_x = nullptr) and _seeded (either
-// seed may be NULL, not both), are this function; so is _mixed (nd_max = 16, seeded, mixed: Lg and mix_W)
-static int mmp_nd_backward(int nd_max, bool seeded_entry, bool mixed, int Lg, const double* mix_W, int S, int dtype, int H,
-                           double dt, int nx, int na,
-                           const int32_t* active_dims, int nu, const void* policy_packed,
-                           size_t policy_bytes, int policy_M, const double* head_scale,
-                           const double* head_shift, const void* target, const void* precis,
-                           const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
-                           void* g_x0, void* scratch, size_t scratch_bytes, void* stream, bool one_action = false) {
+// the backward entries: one action (nd_max = 8, nu = 1, one_action), _nd (nd_max = 8) and _wide (nd_max = 16), unseeded (g_cost
+// required, g_x = nullptr) and _seeded (seeded_entry: either seed may be NULL, not both), are this function; so is _mixed
+// (nd_max = 16, seeded_entry, mixed: Lg and mix_W)
+static int mmp_nd_backward(const MMPwRollout& P, const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
+                           void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes) {
+  const int S = P.drift.S, dtype = P.drift.dtype, H = P.H, nu = P.nu, policy_M = P.policy_M, Lg = P.Lg;
+  const bool mixed = P.mixed;
+  const double dt = P.dt, *mix_W = P.mix_W;
+  const void *target = P.target, *precis = P.precis;
   MMComposeDims D;
-  int rc = mmp_nd_check(S, 1, 1, dtype, H, nx, na, nu, active_dims, policy_M, nd_max, one_action, D);
+  int rc = mmp_nd_check(P, false, D);
   if (rc) return rc;
-  if (mixed && (Lg < 1 || Lg > nx)) return MM_E_DIM;
-  if (!policy_packed || !head_scale || !head_shift || !target || !precis || !tape ||
-      (seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch || (mixed && !mix_W))
+  if (mixed && (Lg < 1 || Lg > P.nx)) return MM_E_DIM;
+  if (!P.policy_packed || !P.head_scale || !P.head_shift || !target || !precis || !tape ||
+      (P.seeded_entry ? (!g_cost && !g_x) : !g_cost) || !g_policy || !scratch || (mixed && !mix_W))
     return MM_E_ARG;
   const int ne = D.ne, npar = nu * (policy_M * ne + policy_M + ne + 2);
   const size_t lds = mmp_nd_bwd_lds(policy_M, ne, nu);
   if (lds > MMP_ND_LDS_MAX) return MM_E_DIM;
-  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, nx, na, nu, mixed ? Lg : nx, dtype, 1);
+  const MMPwTapeLayout tl = mm_pw_tape_layout_latent(S, H, P.nx, P.na, nu, mixed ? Lg : P.nx, dtype, 1);
   if (tape_bytes < tl.total) return MM_E_WORKSPACE;
-  if (scratch_bytes < mmp_nd_scratch_bytes(nd_max, S, policy_M, ne, nu)) return MM_E_WORKSPACE;
+  if (scratch_bytes < mmp_nd_scratch_bytes(P.nd_max, S, policy_M, ne, nu)) return MM_E_WORKSPACE;
   const MMModelLayout pl = mm_model_layout(nu, policy_M, ne, MM_F64, 1);
-  if (policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
-  const MMHeadND hd = mmp_head_constants(nu, head_scale, head_shift);
-  const char* pp = (const char*)policy_packed; const char* tp = (const char*)tape;
-  hipStream_t s = (hipStream_t)stream;
+  if (P.policy_bytes < pl.Zc64) return MM_E_WORKSPACE;
+  const MMHeadND hd = mmp_head_constants(nu, P.head_scale, P.head_shift);
+  const char* pp = (const char*)P.policy_packed; const char* tp = (const char*)tape;
+  hipStream_t s = (hipStream_t)P.stream;
   const dim3 grid((S + 255) / 256);
   // (the built-in cost alone: the unseeded instantiation, whichever entry was called -- same arithmetic, bit-equal outputs)
   const bool seeded = g_x != nullptr || g_cost == nullptr;
@@ -546,18 +547,18 @@ static int mmp_nd_backward(int nd_max, bool seeded_entry, bool mixed, int Lg, co
                        const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,                   \
                        const double* head_shift, const void* target, const void* precis, const void* tape, size_t tape_bytes,    \
                        const void* g_cost, void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {      \
-    return mmp_nd_backward(nd_max_, false, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,            \
-                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, nullptr,    \
-                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
+    MMP_ROLLOUT_FIELDS(P); MMP_HEAD_FIELDS(P);                                                                                   \
+    P.nd_max = nd_max_;                                                                                                          \
+    return mmp_nd_backward(P, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch, scratch_bytes);                        \
   }                                                                                                                             \
   extern "C" int name_##_seeded(int S, int dtype, int H, double dt, int nx, int na, const int32_t* active_dims, int nu,          \
                                 const void* policy_packed, size_t policy_bytes, int policy_M, const double* head_scale,          \
                                 const double* head_shift, const void* target, const void* precis, const void* tape,              \
                                 size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy, void* g_x0,              \
                                 void* scratch, size_t scratch_bytes, void* stream) {                                            \
-    return mmp_nd_backward(nd_max_, true, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed,             \
-                           policy_bytes, policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x,        \
-                           g_policy, g_x0, scratch, scratch_bytes, stream);                                                     \
+    MMP_ROLLOUT_FIELDS(P); MMP_HEAD_FIELDS(P);                                                                                   \
+    P.nd_max = nd_max_; P.seeded_entry = true;                                                                                   \
+    return mmp_nd_backward(P, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch, scratch_bytes);                            \
   }
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_nd, 8)
 MMP_BACKWARD_ENTRY(mm_pathwise_policy_rollout_backward_wide, 16)
@@ -569,9 +570,9 @@ extern "C" int mm_pathwise_policy_rollout_backward(int S, int dtype, int H, doub
                                                    double head_scale, double head_shift, const void* target, const void* precis,
                                                    const void* tape, size_t tape_bytes, const void* g_cost, void* g_policy,
                                                    void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
-  return mmp_nd_backward(8, false, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, 1, policy_packed, policy_bytes,
-                         policy_M, &head_scale, &head_shift, target, precis, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0,
-                         scratch, scratch_bytes, stream, true);
+  MMP_ROLLOUT_FIELDS(P);
+  P.nu = 1; P.head_scale = &head_scale; P.head_shift = &head_shift; P.one_action = true;       // (nd_max: 8)
+  return mmp_nd_backward(P, tape, tape_bytes, g_cost, nullptr, g_policy, g_x0, scratch, scratch_bytes);
 }
 extern "C" int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int H, double dt, int nx, int na,
                                                           const int32_t* active_dims, const void* policy_packed,
@@ -579,9 +580,9 @@ extern "C" int mm_pathwise_policy_rollout_backward_seeded(int S, int dtype, int 
                                                           const void* target, const void* precis, const void* tape,
                                                           size_t tape_bytes, const void* g_cost, const void* g_x, void* g_policy,
                                                           void* g_x0, void* scratch, size_t scratch_bytes, void* stream) {
-  return mmp_nd_backward(8, true, false, 0, nullptr, S, dtype, H, dt, nx, na, active_dims, 1, policy_packed, policy_bytes,
-                         policy_M, &head_scale, &head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0,
-                         scratch, scratch_bytes, stream, true);
+  MMP_ROLLOUT_FIELDS(P);
+  P.nu = 1; P.head_scale = &head_scale; P.head_shift = &head_shift; P.one_action = true; P.seeded_entry = true;
+  return mmp_nd_backward(P, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch, scratch_bytes);
 }
 
 // the reverse sweep of the _mixed rollout: the _seeded signature (either of g_cost and g_x may be NULL, not both) + the mixing
@@ -592,7 +593,9 @@ extern "C" int mm_pathwise_policy_rollout_backward_mixed(int S, int dtype, int H
                                                          const void* tape, size_t tape_bytes, const void* g_cost, const void* g_x,
                                                          void* g_policy, void* g_x0, void* scratch, size_t scratch_bytes,
                                                          void* stream, int Lg, const double* mix_W) {
-  return mmp_nd_backward(16, true, true, Lg, mix_W, S, dtype, H, dt, nx, na, active_dims, nu, policy_packed, policy_bytes,
-                         policy_M, head_scale, head_shift, target, precis, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch,
-                         scratch_bytes, stream);
+  MMP_ROLLOUT_FIELDS(P); MMP_HEAD_FIELDS(P);
+  P.nd_max = 16; P.seeded_entry = true; P.mixed = true; P.Lg = Lg; P.mix_W = mix_W;
+  return mmp_nd_backward(P, tape, tape_bytes, g_cost, g_x, g_policy, g_x0, scratch, scratch_bytes);
 }
+#undef MMP_HEAD_FIELDS
+#undef MMP_ROLLOUT_FIELDS

@@ -1,21 +1,39 @@
 // Device helpers and the tape layout of the pathwise policy rollout and its reverse sweep (mm_pathwise_policy.hip, 1 .. 4
-// actions).  Encoder, cost, the policy's predictive mean, the fixed-order wave sum.
+// actions).  Encoder, cost, the policy's predictive mean, the fixed-order wave sum; and what its entries hand their drivers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "mm_common.h"
 #include "mm_compose.h"
 
-int mm_pathwise_launch(int S, int L, int M, int K, int d, int dtype, const void* x, const void* omega_t, const void* phase,
-                       const void* zs_t, const void* hz, const double* x_scale, const double* prior_scale, const double* variance,
-                       const double* mean_c, const void* wb, void* f_out, void* jac, hipStream_t s, int kernel = 0);
-// the same outputs from the MEAN of the drift (shared weights beta [L,M] f64 in place of the stream; mm_pathwise_mean.hip, d <= 16)
-int mm_pathwise_mean_launch(int S, int L, int M, int d, int dtype, const void* x, const void* zs_t, const void* hz,
-                            const double* x_scale, const double* variance, const double* mean_c, const double* beta, void* f_out,
-                            void* jac, hipStream_t s, int kernel);
+#include "mm_pathwise_drift.h"
 
 #define MMP_NE 24            // largest encoded dimension (2 na + nb, na <= 8, nx <= 16)
 #define MMP_POLICY_MMAX 256
+
+// What an entry of mm_pathwise_policy.hip knows about its rollout, by name: the forward and the reverse driver take this and
+// their per-call buffers.  The entries differ in which fields they set and in the four at the end of the list.
+struct MMPwRollout {
+  // S, M, K, dtype, kernel and the operands (a reverse sweep: S and dtype alone); L and d are the driver's (the latents a step
+  // keeps, nd drift inputs)
+  MMPwDrift drift;
+  int nx = 0, na = 0, nu = 0;
+  const int32_t* active_dims = nullptr;
+  const void* policy_packed = nullptr;                  // an mm_pack_model pack with L = nu: its f64 blocks are read
+  size_t policy_bytes = 0;
+  int policy_M = 0;
+  const double *head_scale = nullptr, *head_shift = nullptr;    // [nu]
+  const void *target = nullptr, *precis = nullptr;
+  int Lg = 0;                                           // mixed: f = mix_W g + mix_c, mix_W [nx][Lg], mix_c [nx] or NULL
+  const double *mix_W = nullptr, *mix_c = nullptr;
+  int H = 0;
+  double dt = 0.0;
+  void* stream = nullptr;
+  int nd_max = 8;              // 8: the one-action and _nd entries; 16: _wide, _mixed, _kern, _mean
+  bool mixed = false;          // a coregionalised drift (the _mixed entries; _kern and _mean with Lg or mix_W set)
+  bool one_action = false;     // the one-action entries: na > 0 without active_dims is MM_E_DIM, not MM_E_ARG
+  bool seeded_entry = false;   // reverse sweeps: either seed may be NULL, not both (else g_cost is required)
+};
 
 struct MMPwTapeLayout {
   size_t x;      // [H + 1][S][nx] T   states

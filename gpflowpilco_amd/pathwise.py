@@ -126,25 +126,37 @@ class Paths:
     g = self._latent_values(x)
     return g if self.mix_W is None else self._mixed_values(g)
 
-  def _entry(self, name: str):
-    """The ABI entry of these paths' kernel family and its trailing arguments: SquaredExponential paths call the entries they
-    always have, Matern paths the ``_kern`` siblings."""
-    return (name, ()) if self.kernel == 0 else (name + "_kern", (int(self.kernel),))
+  def _operands(self):
+    """((S, L, Mp, Kp, d), the nine drift operands omega_t .. wb): sizes and pointers in the order every entry of the C ABI lists
+    them.  The one place this list is written: the sample entries (``_run``) and ``PolicyRollout`` both take it from here."""
+    return self._dims(), (self.omega.data_ptr(), self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
+                          self.lengthscales.data_ptr(), self.prior_scale.data_ptr(), self.variance.data_ptr(),
+                          _ptr(self.mean_c), self.wb.data_ptr())
 
-  def _latent_values(self, x: torch.Tensor) -> torch.Tensor:
+  def _run(self, stem: str, ins, outs, steps=()):
+    """One call of a sample entry -- ``stem``: mm_pathwise_eval | _eval_jac | _eval_bound | _rollout; SquaredExponential paths call
+    the entries they always have, Matern paths the ``_kern`` siblings with the family appended.  The argument list: sizes, dtype,
+    ``steps`` (the rollout's H, dt), the buffers ``ins`` (x [S, d] first), the drift operands, the buffers ``outs`` (None: NULL),
+    stream."""
+    x = ins[0]
     _require_device(x, self.wb)
-    S, L, Mp, Kp, d = self._dims()
+    sizes, drift = self._operands()
+    S, d = sizes[0], sizes[-1]
     if x.shape != (S, d) or x.dtype != self.dtype:
       raise ValueError(f"expected x [{S},{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
-    x = x.contiguous()
-    out = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    entry, kern = self._entry("mm_pathwise_eval")
-    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                    out.data_ptr(), _stream(x.device), *kern)
+    entry, kern = (stem, ()) if self.kernel == 0 else (stem + "_kern", (int(self.kernel),))
+    ins = [t.contiguous() for t in ins]                      # (kept until the call is made)
+    rc = getattr(_lib.lib(), entry)(*sizes, _dtype_code(self.dtype), *steps, *(t.data_ptr() for t in ins), *drift,
+                                    *(_ptr(t) for t in outs), _stream(x.device), *kern)
     check(rc, entry)
+
+  def _empty(self, x: torch.Tensor, *tail) -> torch.Tensor:
+    """An output [S, L, *tail] beside x."""
+    return torch.empty(self.num_samples, self.omega.shape[0], *tail, dtype=self.dtype, device=x.device)
+
+  def _latent_values(self, x: torch.Tensor) -> torch.Tensor:
+    out = self._empty(x)
+    self._run("mm_pathwise_eval", (x,), (out,))
     return out
 
   def eval_jac(self, x: torch.Tensor):
@@ -156,20 +168,8 @@ class Paths:
     return self._mixed_values(g), torch.einsum('il,sld->sid', self.mix_W, jac.to(DEFAULT_FLOAT)).to(self.dtype)
 
   def _latent_jac(self, x: torch.Tensor):
-    _require_device(x, self.wb)
-    S, L, Mp, Kp, d = self._dims()
-    if x.shape != (S, d) or x.dtype != self.dtype:
-      raise ValueError(f"expected x [{S},{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
-    x = x.contiguous()
-    out = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    jac = torch.empty(S, L, d, dtype=self.dtype, device=x.device)
-    entry, kern = self._entry("mm_pathwise_eval_jac")
-    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                    out.data_ptr(), jac.data_ptr(), _stream(x.device), *kern)
-    check(rc, entry)
+    out, jac = self._empty(x), self._empty(x, self.omega.shape[1])
+    self._run("mm_pathwise_eval_jac", (x,), (out, jac))
     return out, jac
 
   def eval_with_bound(self, x: torch.Tensor):
@@ -184,20 +184,8 @@ class Paths:
     return self._mixed_values(g), (err.to(DEFAULT_FLOAT) @ self.mix_W.abs().T).to(self.dtype)
 
   def _latent_bound(self, x: torch.Tensor):
-    _require_device(x, self.wb)
-    S, L, Mp, Kp, d = self._dims()
-    if x.shape != (S, d) or x.dtype != self.dtype:
-      raise ValueError(f"expected x [{S},{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
-    x = x.contiguous()
-    out = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    ab = torch.empty(S, L, dtype=self.dtype, device=x.device)
-    entry, kern = self._entry("mm_pathwise_eval_bound")
-    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), x.data_ptr(), self.omega.data_ptr(),
-                                    self.phase.data_ptr(), self.zs.data_ptr(), self.hz.data_ptr(),
-                                    self.lengthscales.data_ptr(), self.prior_scale.data_ptr(),
-                                    self.variance.data_ptr(), _ptr(self.mean_c), self.wb.data_ptr(),
-                                    out.data_ptr(), ab.data_ptr(), _stream(x.device), *kern)
-    check(rc, entry)
+    out, ab = self._empty(x), self._empty(x)
+    self._run("mm_pathwise_eval_bound", (x,), (out, ab))
     # unit roundoff u = finfo.eps / 2; v and the basis value each carry ~u, the exponent's own rounding (|arg| up to ~20 at the
     # C5 shape) a few u more: BOUND_ULPS u covers the measured worst case with a factor ~2 in hand (tests/test_pathwise.py)
     return out, ab * (BOUND_ULPS * 0.5 * torch.finfo(self.dtype).eps)
@@ -213,18 +201,10 @@ class Paths:
     if self.mix_W is not None:
       raise ValueError("Paths.rollout: the drift-only rollout does not mix (these paths carry mix_W: f = W g + c); step "
                        "x + dt paths(x) in torch, or use PolicyRollout")
-    _require_device(x0, self.wb)
-    S, L, Mp, Kp, d = self._dims()
     x = x0.contiguous().clone()
     tmp = torch.empty_like(x)
-    traj = torch.empty(num_steps, S, d, dtype=self.dtype, device=x.device) if keep_trajectory else None
-    entry, kern = self._entry("mm_pathwise_rollout")
-    rc = getattr(_lib.lib(), entry)(S, L, Mp, Kp, d, _dtype_code(self.dtype), int(num_steps), float(dt),
-                                    x.data_ptr(), tmp.data_ptr(), self.omega.data_ptr(), self.phase.data_ptr(),
-                                    self.zs.data_ptr(), self.hz.data_ptr(), self.lengthscales.data_ptr(),
-                                    self.prior_scale.data_ptr(), self.variance.data_ptr(), _ptr(self.mean_c),
-                                    self.wb.data_ptr(), _ptr(traj), _stream(x.device), *kern)
-    check(rc, entry)
+    traj = torch.empty(num_steps, *x.shape, dtype=self.dtype, device=x.device) if keep_trajectory else None
+    self._run("mm_pathwise_rollout", (x, tmp), (traj,), steps=(int(num_steps), float(dt)))
     return (x, traj) if keep_trajectory else x
 
 
@@ -392,19 +372,22 @@ class MeanDrift:
     f = g.to(DEFAULT_FLOAT) @ self.mix_W.T
     return (f if self.mix_c is None else f + self.mix_c).to(self.dtype)
 
+  def _operands(self):
+    """((L, Mp, d), the six drift operands zs_t .. beta) in the order of the C ABI: ``Paths._operands`` for a mean-only drift."""
+    return self._dims(), (self.zs.data_ptr(), self.hz.data_ptr(), self.lengthscales.data_ptr(), self.variance.data_ptr(),
+                          _ptr(self.mean_c), self.beta.data_ptr())
+
   def _eval(self, x: torch.Tensor, jac: bool):
     _require_device(x, self.zs)
-    L, Mp, d = self._dims()
+    (L, Mp, d), drift = self._operands()
     if x.ndim != 2 or x.shape[1] != d or x.dtype != self.dtype:
       raise ValueError(f"expected x [S,{d}] of {self.dtype}, got {tuple(x.shape)} {x.dtype}")
     x = x.contiguous()
     S = x.shape[0]
     out = torch.empty(S, L, dtype=self.dtype, device=x.device)
     J = torch.empty(S, L, d, dtype=self.dtype, device=x.device) if jac else None
-    rc = _lib.lib().mm_pathwise_mean_eval(S, L, Mp, d, _dtype_code(self.dtype), x.data_ptr(), self.zs.data_ptr(),
-                                          self.hz.data_ptr(), self.lengthscales.data_ptr(), self.variance.data_ptr(),
-                                          _ptr(self.mean_c), self.beta.data_ptr(), out.data_ptr(), _ptr(J), _stream(x.device),
-                                          int(self.kernel))
+    rc = _lib.lib().mm_pathwise_mean_eval(S, L, Mp, d, _dtype_code(self.dtype), x.data_ptr(), *drift, out.data_ptr(), _ptr(J),
+                                          _stream(x.device), int(self.kernel))
     check(rc, "mm_pathwise_mean_eval")
     return out, J
 
@@ -715,10 +698,29 @@ class PolicyRollout:
     self.precis = (torch.zeros(self.ne, self.ne, dtype=paths.dtype, device=dev) if precis is None else
                    precis.to(dtype=paths.dtype, device=dev).contiguous())
     self._act = (_lib.C.c_int32 * self.na)(*self.active)
-    self._sfx = "wide" if self.wide else "nd"                  # which set of entries with the _nd signatures
-    if self.mixed:                                             # (the scratch query of the mixed sweep is the _wide one)
+    if self.mixed:
       self._mix_W = mix_W.detach().to(dtype=torch.float64, device=dev).contiguous()
       self._mix_c = None if mix_c is None else mix_c.detach().to(dtype=torch.float64, device=dev).contiguous()
+    # which entries this rollout calls and what its argument lists carry besides the buffers, decided here once.  The one-action
+    # entries take no action count and their head constants by value; the others the count and one array per constant.
+    sfx = "wide" if self.wide else "nd"                        # which set of entries with the _nd signatures
+    stem = "mm_pathwise_policy_rollout"
+    self._bounded_scratch_query = f"mm_pathwise_backward_scratch_bytes_{sfx}"      # (the mixed sweep's query is the _wide one)
+    mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
+    if self.nd_entries:
+      self._forward = f"{stem}_" + ("mean" if self.mean else "kern" if self.kernel else "mixed" if self.mixed else sfx)
+      self._tape_query = "mm_pathwise_tape_bytes_" + ("mixed" if self.mixed else "nd")
+      self._scratch_query = self._bounded_scratch_query
+      # (unseeded, seeded): the mixed sweep is one entry with the seeded signature
+      self._sweeps = (f"{stem}_backward_mixed",) * 2 if self.mixed else (f"{stem}_backward_{sfx}", f"{stem}_backward_{sfx}_seeded")
+      self._nu, self._head = (self.nu,), (self._scale_c, self._shift_c)
+      # the _kern and _mean entries always take the mixing (none: 0, NULL, NULL) and the family after it
+      self._forward_tail = (mixing or (0, None, None)) + (self.kernel,) if self.kernel or self.mean else mixing
+    else:
+      self._forward, self._tape_query, self._scratch_query = stem, "mm_pathwise_tape_bytes", "mm_pathwise_backward_scratch_bytes"
+      self._sweeps = (f"{stem}_backward", f"{stem}_backward_seeded")
+      self._nu, self._head, self._forward_tail = (), (self.scale, self.shift), ()
+    self._tape_Lg, self._sweep_tail = mixing[:1], mixing[:2]
 
   def _policy(self, policy):
     pol = self.policy if policy is None else policy
@@ -728,53 +730,31 @@ class PolicyRollout:
 
   def supports_backward(self) -> bool:
     """False where the reverse sweep's per-workgroup LDS (the nu policy blocks + four gradient slabs) exceeds 160 KiB."""
-    query = getattr(_lib.lib(), f"mm_pathwise_backward_scratch_bytes_{self._sfx}")
-    return query(self.S, self.policy.M, self.ne, self.nu) > 0
+    return getattr(_lib.lib(), self._bounded_scratch_query)(self.S, self.policy.M, self.ne, self.nu) > 0
 
   def __call__(self, x0: torch.Tensor, num_steps: int, dt: float = 1.0, with_jacobians: bool = False, policy=None):
     pol = self._policy(policy)
     P = self.paths
-    S, Mp = self.S, P.zs.shape[-1]
+    S = self.S
     _require_device(x0, P.zs)
     if x0.shape != (S, self.nx) or x0.dtype != P.dtype:
       raise ValueError(f"expected x0 [{S},{self.nx}] of {P.dtype}, got {tuple(x0.shape)} {x0.dtype}")
     H, code = int(num_steps), _dtype_code(P.dtype)
     lib = _lib.lib()
-    if self.mixed:
-      n = lib.mm_pathwise_tape_bytes_mixed(S, H, self.nx, self.na, self.nu, self.Lg, code, int(with_jacobians))
-    elif self.nd_entries:
-      n = lib.mm_pathwise_tape_bytes_nd(S, H, self.nx, self.na, self.nu, code, int(with_jacobians))
-    else:
-      n = lib.mm_pathwise_tape_bytes(S, H, self.nx, self.na, code, int(with_jacobians))
+    n = getattr(lib, self._tape_query)(S, H, self.nx, self.na, *self._nu, *self._tape_Lg, code, int(with_jacobians))
     if n == 0:
       raise ValueError("mm_pathwise_tape_bytes rejected the shape")
     tape = torch.empty(n, dtype=torch.uint8, device=x0.device)
     cost = torch.empty(H, S, dtype=P.dtype, device=x0.device)
     x0 = x0.contiguous()
-    # the one-action entry takes no action count and its head constants by value; the others the count and one array each
-    mixing = (self.Lg, self._mix_W.data_ptr(), _ptr(self._mix_c)) if self.mixed else ()
-    if self.nd_entries:
-      entry = "mm_pathwise_policy_rollout_" + ("mean" if self.mean else "kern" if self.kernel else
-                                               "mixed" if self.mixed else self._sfx)
-      if self.kernel or self.mean:
-        mixing = (mixing or (0, None, None)) + (self.kernel,)
-      nu, head = (self.nu,), (self._scale_c, self._shift_c)
-    else:
-      entry, nu, head = "mm_pathwise_policy_rollout", (), (self.scale, self.shift)
-    if self.mean:                                              # shared weights: no K, no prior half, beta in the stream's place
-      sizes = (S, Mp)
-      drift = (P.zs.data_ptr(), P.hz.data_ptr(), P.lengthscales.data_ptr(), P.variance.data_ptr(), _ptr(P.mean_c),
-               P.beta.data_ptr())
-    else:
-      sizes = (S, Mp, P.omega.shape[-1])
-      drift = (P.omega.data_ptr(), P.phase.data_ptr(), P.zs.data_ptr(), P.hz.data_ptr(), P.lengthscales.data_ptr(),
-               P.prior_scale.data_ptr(), P.variance.data_ptr(), _ptr(P.mean_c), P.wb.data_ptr())
-    rc = getattr(lib, entry)(*sizes, code, H, float(dt), self.nx, self.na, self._act, *nu, *drift,
-                             pol.buf.data_ptr(), pol.nbytes, pol.M,
-                             *head, self.target.data_ptr(), self.precis.data_ptr(),
-                             x0.data_ptr(), cost.data_ptr(), tape.data_ptr(), tape.numel(),
-                             int(with_jacobians), _stream(x0.device), *mixing)
-    check(rc, entry)
+    dims, drift = P._operands()
+    # a mean-only drift has shared weights: no K, no prior half, beta in the stream's place
+    sizes = (S, dims[1]) if self.mean else (S, dims[2], dims[3])
+    rc = getattr(lib, self._forward)(*sizes, code, H, float(dt), self.nx, self.na, self._act, *self._nu, *drift,
+                                     pol.buf.data_ptr(), pol.nbytes, pol.M, *self._head,
+                                     self.target.data_ptr(), self.precis.data_ptr(), x0.data_ptr(), cost.data_ptr(),
+                                     tape.data_ptr(), tape.numel(), int(with_jacobians), _stream(x0.device), *self._forward_tail)
+    check(rc, self._forward)
     return cost, tape
 
   def states(self, tape: torch.Tensor, num_steps: int) -> torch.Tensor:
@@ -817,26 +797,17 @@ class PolicyRollout:
     g_x0 = torch.empty(S, self.nx, dtype=torch.float64, device=dev) if want_state_grad else None
     seeded = seeded or self.mixed
     seeds = (_ptr(g_cost), _ptr(g_states)) if seeded else (g_cost.data_ptr(),)
-    mixing = (self.Lg, self._mix_W.data_ptr()) if self.mixed else ()
     lib = _lib.lib()
-    if self.nd_entries:
-      ns = getattr(lib, f"mm_pathwise_backward_scratch_bytes_{self._sfx}")(S, pol.M, self.ne, self.nu)
-      if ns == 0:
-        raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
-                         "slabs exceed 160 KiB of LDS (see supports_backward)")
-      g_pol = torch.empty(self.nu, npar, dtype=torch.float64, device=dev)
-      entry = ("mm_pathwise_policy_rollout_backward_mixed" if self.mixed else
-               f"mm_pathwise_policy_rollout_backward_{self._sfx}" + ("_seeded" if seeded else ""))
-      head = (self.nu, pol.buf.data_ptr(), pol.nbytes, pol.M, self._scale_c, self._shift_c)
-    else:
-      ns = lib.mm_pathwise_backward_scratch_bytes(S, pol.M, self.ne)
-      g_pol = torch.empty(npar, dtype=torch.float64, device=dev)
-      entry = "mm_pathwise_policy_rollout_backward" + ("_seeded" if seeded else "")
-      head = (pol.buf.data_ptr(), pol.nbytes, pol.M, self.scale, self.shift)
+    ns = getattr(lib, self._scratch_query)(S, pol.M, self.ne, *self._nu)
+    if ns == 0:
+      raise ValueError(f"the reverse sweep does not take nu={self.nu}, M={pol.M}, ne={self.ne}: its policy blocks and gradient "
+                       "slabs exceed 160 KiB of LDS (see supports_backward)")
+    g_pol = torch.empty(*self._nu, npar, dtype=torch.float64, device=dev)
     scratch = torch.empty(ns, dtype=torch.uint8, device=dev)
-    rc = getattr(lib, entry)(S, code, H, dt, self.nx, self.na, self._act, *head, self.target.data_ptr(), self.precis.data_ptr(),
-                             tape.data_ptr(), tape.numel(), *seeds, g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(),
-                             scratch.numel(), _stream(dev), *mixing)
+    entry = self._sweeps[bool(seeded)]
+    rc = getattr(lib, entry)(S, code, H, dt, self.nx, self.na, self._act, *self._nu, pol.buf.data_ptr(), pol.nbytes, pol.M,
+                             *self._head, self.target.data_ptr(), self.precis.data_ptr(), tape.data_ptr(), tape.numel(), *seeds,
+                             g_pol.data_ptr(), _ptr(g_x0), scratch.data_ptr(), scratch.numel(), _stream(dev), *self._sweep_tail)
     check(rc, entry)
     return g_pol, g_x0
 
