@@ -24,6 +24,8 @@ def device():
   return torch.device("cuda", 0)
 
 
+# (_pm and _states also make the inputs of tests/test_gpu_offdiag_slot_golden.py, whose fixture is compared to the bit: a change of
+# their seeds, recipes or spread means recording tests/golden/offdiag_slot_parent.npz again)
 def _pm(L, M, d, seed, recipe, device):
   syn = make_svgp(L, M, d, seed=seed, device=str(device), **RECIPE[recipe])
   return syn.to_model(device).packed(F32, True, device)
