@@ -53,6 +53,8 @@ def main():
   ap.add_argument("--length", type=int, default=40)
   ap.add_argument("--inducing", type=int, default=40)
   ap.add_argument("--fit-iters", type=int, default=40)
+  ap.add_argument("--collapsed", action="store_true",
+                  help="fit the hyper-parameters on the collapsed (SGPR) bound and set q(u) to its closed-form optimum")
   ap.add_argument("--policy-steps", type=int, default=10)
   ap.add_argument("--horizon", type=int, default=15)
   args = ap.parse_args()
@@ -72,7 +74,7 @@ def main():
     with torch.no_grad():
       return float(drift.predict_log_density((t(held_X), t(held_Y))).mean())
   before, before_ld = rmse(), log_density()
-  history = fit_svgp(drift, (t(X), t(Y)), max_iter=args.fit_iters)
+  history = fit_svgp(drift, (t(X), t(Y)), max_iter=args.fit_iters, collapsed=args.collapsed)
   print(f"drift fit: {len(X)} transitions, {len(history) - 1} L-BFGS iterations, loss {history[0]:+.2f} -> {history[-1]:+.2f}, "
         f"held-out RMSE {before:.2e} -> {rmse():.2e}, held-out mean log density {before_ld:+.3f} -> {log_density():+.3f}")
   # 3. the policy, on the fitted drift

@@ -181,6 +181,9 @@ SIGNATURES = {
     "mm_gram_se_backward": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
     "mm_predict_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "mm_predict_se": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]),
+    "mm_gram_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "mm_gram_stats_se": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    "mm_gram_stats_se_backward": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
     "mm_rollout_closed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_double, C.c_int, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -528,3 +528,61 @@ class GramSESelfFunction(torch.autograd.Function):
   def backward(ctx, G):
     Z, ls, var = ctx.saved_tensors
     return ops.gram_se_backward(G, None, Z, ls, var)
+
+
+class GramStatsSEFunction(torch.autograd.Function):
+  """The streamed Gram statistics (Phi [L,M,M] = K K^T, Psi [L,M,Q] = K R) of the collapsed bound as a differentiable op
+  (``mm_gram_stats_se`` / ``mm_gram_stats_se_backward``, csrc/mm_gram_stats.hip): gradients with respect to Z, the lengthscales and
+  the variances; X and R are constants.  Only the operands are saved and K [L,M,N] exists on neither pass.  A missing output
+  gradient counts as zeros."""
+
+  @staticmethod
+  def forward(ctx, X, R, Z, ls, var):
+    ctx.save_for_backward(X, R, Z, ls, var)
+    return ops.gram_stats_se(X, R, Z, ls, var)
+
+  @staticmethod
+  def backward(ctx, GPhi, GPsi):
+    X, R, Z, ls, var = ctx.saved_tensors
+    L, M, _ = Z.shape
+    if GPhi is None:
+      GPhi = torch.zeros(L, M, M, dtype=torch.float64, device=Z.device)
+    if GPsi is None:
+      GPsi = torch.zeros(L, M, R.shape[1], dtype=torch.float64, device=Z.device)
+    gZ, gls, gvar = ops.gram_stats_se_backward(GPhi, GPsi, X, R, Z, ls, var)
+    return None, None, gZ, gls, gvar
+
+
+class GramStatsComposedFunction(torch.autograd.Function):
+  """The same (Phi, Psi) as ``GramStatsSEFunction`` from the existing parts, for the shapes at which that is the faster route
+  (``models.STATS_STREAMED_MAX_M``): per chunk of N that keeps [L,M,chunk] below ``chunk_bytes``, ``ops.gram_se`` and a batched
+  GEMM for the statistics; in the adjoint ``ops.gram_se`` again, a batched GEMM for the adjoint of K,
+  (GPhi + GPhi^T) K + GPsi R^T, and ``ops.gram_se_backward``.  Memory is bounded by the chunk, not by N."""
+
+  @staticmethod
+  def forward(ctx, X, R, Z, ls, var, chunk_bytes):
+    ctx.save_for_backward(X, R, Z, ls, var)
+    L, M, _ = Z.shape
+    ctx.chunk = max(1, int(chunk_bytes) // (8 * L * M))
+    Phi = torch.zeros(L, M, M, dtype=torch.float64, device=Z.device)
+    Psi = torch.zeros(L, M, R.shape[1], dtype=torch.float64, device=Z.device)
+    for s in range(0, X.shape[0], ctx.chunk):
+      K = ops.gram_se(X[s:s + ctx.chunk], Z, ls, var)
+      Phi.baddbmm_(K, K.transpose(1, 2))
+      Psi.add_(K @ R[s:s + ctx.chunk])
+    return 0.5 * (Phi + Phi.transpose(1, 2)), Psi
+
+  @staticmethod
+  def backward(ctx, GPhi, GPsi):
+    X, R, Z, ls, var = ctx.saved_tensors
+    L, M, _ = Z.shape
+    Gs = None if GPhi is None else GPhi + GPhi.transpose(1, 2)
+    gZ, gls, gvar = torch.zeros_like(Z), torch.zeros_like(ls), torch.zeros_like(var)
+    for s in range(0, X.shape[0], ctx.chunk):
+      K = ops.gram_se(X[s:s + ctx.chunk], Z, ls, var)
+      GK = torch.zeros_like(K) if GPsi is None else GPsi @ R[s:s + ctx.chunk].T
+      if Gs is not None:
+        GK.baddbmm_(Gs, K)
+      for acc, g in zip((gZ, gls, gvar), ops.gram_se_backward(GK, X[s:s + ctx.chunk], Z, ls, var)):
+        acc.add_(g)
+    return None, None, gZ, gls, gvar, None

@@ -22,7 +22,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from .linalg import cholesky
+from .linalg import CholeskyError, cholesky
 
 DEFAULT_JITTER = 1e-6  # gpflow.config.default_jitter()
 DEFAULT_FLOAT = torch.float64  # gpflow.config.default_float()
@@ -325,6 +325,13 @@ def _stack_kernel_params(kernels, Zs, device):
 
 
 PREDICT_CHUNK_BYTES = 256 * 2 ** 20  # the torch route of predict_f keeps every intermediate below about this size
+# the native route of the collapsed bound takes the streamed statistics kernel (mm_gram_stats_se) up to this many inducing points
+# and the composition of existing parts (chunked mm_gram_se, batched GEMM, mm_gram_se_backward) above it.  Origin: the sweep of
+# tools/bench_svgp_collapsed.py (profiles/svgp_collapsed_bench.json; L 8, d 8, statistics + adjoint, streamed / composed):
+# M 256 is the largest swept size at which the streamed kernel is the faster one at both N -- 0.87 at N 4000, 0.38 at N 65 536;
+# M 320: 1.10 / 0.51, M 384: 1.29 / 0.62, M 512: 1.76 / 1.16 (it re-forms a K tile for every block pair that uses it).  Sizes
+# between the swept ones (steps of 64) are not measured.
+STATS_STREAMED_MAX_M = 256
 
 
 def _native_predict_refusal(model, X, kernels, family: int, d: int, differ: bool) -> Optional[str]:
@@ -355,6 +362,10 @@ def _predict_y_from_f(model, who: str, mean, var, full_output_cov: bool):
 def _gaussian_log_density(Y, mean, var):
   import math
   return -0.5 * (torch.log(2.0 * math.pi * var) + (Y - mean) ** 2 / var)
+
+
+class SingularCollapsedBound(CholeskyError):
+  """``I + Lu^-1 Phi Lu^-T / s2`` of the collapsed bound could not be factorised: its condition grows as N var / s2."""
 
 
 class SVGP:
@@ -658,6 +669,137 @@ class SVGP:
   def training_loss_closure(self, data, native: Optional[bool] = None) -> Callable[[], torch.Tensor]:
     """Zero-argument callable of the training loss: the reference's ``dynamics_loss_closure`` (loops/pilco.py:173-174)."""
     return lambda: self.training_loss(data, native=native)
+
+  # -- collapsed (SGPR) training: the bound at the optimal q(u), from the Gram statistics Phi = Kuf Kuf^T and Psi = Kuf [Y, 1] ------
+  def _native_stats_refusal(self, X, kernels, family: int, d: int, differ: bool, Q: int) -> Optional[str]:
+    """Why the collapsed bound of this model on these data does not take the HIP statistics (None: it does)."""
+    if not X.is_cuda:
+      return f"the data are on {X.device} (the HIP statistics kernel runs on the GPU)"
+    if family != KERNEL_SE:
+      return f"the native statistics are SquaredExponential only, the latents are {type(kernels[0]).__name__} (torch route)"
+    if differ:
+      return "the latent kernels act on differing active_dims (torch route)"
+    if d > 32:
+      return f"input dimension {d} exceeds MM_DMAX = 32"
+    if Q > 33:
+      return f"{Q - 1} outputs exceed the 32 the statistics kernel takes"
+    return None
+
+  def _collapsed_factors(self, data, native: Optional[bool], who: str):
+    """What the collapsed bound and the optimal q(u) share, per latent: Lu, LB = chol(I + AAT), c = LB^-1 Lu^-1 psi / s2, AAT, the
+    residual sums r^T r [L], the kernel variances [L], s2 and N."""
+    X, Y = data
+    if not isinstance(self.likelihood, GaussianLikelihood):
+      raise NotImplementedError(f"{who}: Gaussian likelihood only, got {type(self.likelihood).__name__}")
+    if isinstance(self.kernel, LinearCoregionalization):
+      raise NotImplementedError(f"{who}: a LinearCoregionalization kernel couples the latents through W (the optimal q(u) is "
+                                "joint over the latents and needs cross-latent statistics); elbo / fit_svgp remain for it")
+    if not isinstance(self.mean_function, (Zero, Constant)):
+      raise NotImplementedError(f"{who}: mean function {type(self.mean_function).__name__}")
+    kernels, Zs = unpack_multioutput(self.kernel, self.inducing_variable, self.num_latent_gps)
+    family = kernel_family(kernels)
+    device = X.device
+    Z, ls, var = _stack_kernel_params(kernels, Zs, device)
+    L, M, d = Z.shape
+    union, differ = kernel_input_dims(kernels, X.shape[-1])
+    Xs = (X[..., list(union)] if differ else kernels[0].slice(X)).to(DEFAULT_FLOAT)
+    Y = Y.to(device=device, dtype=DEFAULT_FLOAT)
+    N = Xs.shape[0]
+    if Y.shape != (N, L):
+      raise ValueError(f"{who}: Y {tuple(Y.shape)} against {(N, L)} model outputs")
+    R = torch.cat([Y, torch.ones(N, 1, dtype=DEFAULT_FLOAT, device=device)], dim=1)           # [N, Q], Q = P + 1
+    refusal = self._native_stats_refusal(Xs, kernels, family, d, differ, L + 1)
+    if native and refusal is not None:
+      raise ValueError(f"{who}(native=True): {refusal}")
+    if native is not False and refusal is None:
+      from .autodiff import GramSESelfFunction, GramStatsComposedFunction, GramStatsSEFunction
+      if M <= STATS_STREAMED_MAX_M:
+        Phi, Psi = GramStatsSEFunction.apply(Xs.detach(), R.detach(), Z, ls, var)
+      else:
+        Phi, Psi = GramStatsComposedFunction.apply(Xs.detach(), R.detach(), Z, ls, var, PREDICT_CHUNK_BYTES)
+      Kuu = GramSESelfFunction.apply(Z, ls, var)
+    else:
+      Az = Z / ls[:, None, :]
+      Kuu = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Az), family)
+      Phi = torch.zeros(L, M, M, dtype=DEFAULT_FLOAT, device=device)
+      Psi = torch.zeros(L, M, L + 1, dtype=DEFAULT_FLOAT, device=device)
+      chunk = max(1, PREDICT_CHUNK_BYTES // (8 * L * M))
+      for start in range(0, N, chunk):
+        Ax = Xs[None, start:start + chunk] / ls[:, None, :]
+        Kuf = var[:, None, None] * stationary_profile(_scaled_sqdist(Az, Ax), family)          # [L, M, chunk]
+        Phi = Phi + Kuf @ Kuf.transpose(1, 2)
+        Psi = Psi + Kuf @ R[start:start + chunk]
+    s2 = self.likelihood.variance.to(device=device, dtype=DEFAULT_FLOAT)
+    if isinstance(self.mean_function, Constant):
+      mc = self.mean_function.c.to(device=device, dtype=DEFAULT_FLOAT).expand(L)
+    else:
+      mc = torch.zeros(L, dtype=DEFAULT_FLOAT, device=device)
+    eye = torch.eye(M, dtype=DEFAULT_FLOAT, device=device)
+    Lu = cholesky(Kuu + DEFAULT_JITTER * eye)
+    T = torch.linalg.solve_triangular(Lu, Phi, upper=False)                                    # Lu^-1 Phi
+    AAT = torch.linalg.solve_triangular(Lu, T.transpose(1, 2), upper=False) / s2              # Lu^-1 Phi Lu^-T / s2
+    AAT = 0.5 * (AAT + AAT.transpose(1, 2))
+    try:
+      LB = cholesky(eye + AAT)
+    except CholeskyError as e:                                  # (Kuu + jitter I above raises the plain CholeskyError)
+      raise SingularCollapsedBound(f"{who}: I + AAT is singular to rounding (noise variance {float(s2.detach()):.3e}): {e}") from e
+    idx = torch.arange(L, device=device)
+    psi = Psi[idx, :, idx] - mc[:, None] * Psi[:, :, L]                                        # [L, M]: Kuf_l (y_l - c_l)
+    c = torch.linalg.solve_triangular(LB, torch.linalg.solve_triangular(Lu, psi.unsqueeze(-1), upper=False), upper=False) / s2
+    rr = ((Y - mc) ** 2).sum(0)                                                                # [L]
+    return Lu, LB, c.squeeze(-1), AAT, rr, var, s2, N
+
+  def collapsed_elbo(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """The ELBO at the optimal q(u) (Titsias' collapsed bound, gpflow's ``SGPR.elbo``) on the full batch ``data = (X [N,d], Y [N,P])``:
+    sum over the latents of log N(y_l | c_l, Qff_l + s2 I) - tr(Kff_l - Qff_l) / (2 s2).  Independent latents (P = L outputs, one
+    Gaussian noise s2) with a ``Zero`` or ``Constant`` mean; ``q_mu`` and ``q_sqrt`` are not read.  Differentiable in the kernel
+    variances and lengthscales, Z, ``likelihood.variance`` and the Constant mean.
+
+    The data enter through Phi_l = Kuf_l Kuf_l^T [M,M], Psi_l = Kuf_l [Y, 1] [M,P+1] and sums over Y alone; everything after that
+    is M x M algebra.  ``native=None`` takes Phi and Psi from HIP on a GPU for SquaredExponential latents with equal ``active_dims``,
+    d <= 32 and P <= 32 -- up to ``STATS_STREAMED_MAX_M`` inducing points from the streamed kernel
+    (``autodiff.GramStatsSEFunction``: Kuf is never stored, on either pass), above it from the composition that is faster there
+    (``autodiff.GramStatsComposedFunction``: chunked ``mm_gram_se``, batched GEMMs, ``mm_gram_se_backward``; memory bounded by
+    ``PREDICT_CHUNK_BYTES``) -- and from torch otherwise; ``native=False`` always from torch; ``native=True`` raises ``ValueError`` with the reason where the native route does
+    not apply.  The torch route forms the statistics in chunks of N that keep [L, M, chunk] below ``PREDICT_CHUNK_BYTES`` and lets
+    autograd keep the chunks: it is the CPU / Matern route, not the fast one."""
+    import math
+    Lu, LB, c, AAT, rr, var, s2, N = self._collapsed_factors(data, native, "SVGP.collapsed_elbo")
+    L = c.shape[0]
+    bound = -0.5 * N * L * math.log(2.0 * math.pi) - torch.log(torch.diagonal(LB, dim1=-2, dim2=-1)).sum()
+    bound = bound - 0.5 * N * L * torch.log(s2) - rr.sum() / (2.0 * s2) + 0.5 * (c * c).sum()
+    bound = bound - N * var.sum() / (2.0 * s2) + 0.5 * torch.diagonal(AAT, dim1=-2, dim2=-1).sum()
+    return bound
+
+  def optimal_q(self, data, native: Optional[bool] = None):
+    """-> (q_mu [M,L], q_sqrt [L,M,M]) of the q(u) that maximises ``elbo`` at the present hyper-parameters (Titsias 2009, eq. 10),
+    in the model's own parametrisation: whitened, q_mu_l = LB^-T c and q_sqrt_l = chol((I + AAT)^-1); not whitened, Lu times the
+    mean and chol(Lu (I + AAT)^-1 Lu^T).  Runs under ``torch.no_grad()``; routing as ``collapsed_elbo``."""
+    with torch.no_grad():
+      Lu, LB, c, AAT, rr, var, s2, N = self._collapsed_factors(data, native, "SVGP.optimal_q")
+      M = Lu.shape[-1]
+      mu = torch.linalg.solve_triangular(LB.transpose(1, 2), c.unsqueeze(-1), upper=True)      # [L, M, 1]
+      LBinv = torch.linalg.solve_triangular(LB, torch.eye(M, dtype=DEFAULT_FLOAT, device=Lu.device).expand_as(LB), upper=False)
+      if not self.whiten:
+        mu = Lu @ mu
+        LBinv = LBinv @ Lu.transpose(1, 2)                                                     # cov = (LB^-1 Lu^T)^T (LB^-1 Lu^T)
+      cov = LBinv.transpose(1, 2) @ LBinv
+      q_sqrt = cholesky(0.5 * (cov + cov.transpose(1, 2)))
+      return mu.squeeze(-1).T.contiguous(), q_sqrt
+
+  def set_optimal_q(self, data, native: Optional[bool] = None):
+    """Writes ``optimal_q(data)`` into ``q_mu`` and ``q_sqrt`` in place (their ``_version`` moves: the pack cache repacks)."""
+    q_mu, q_sqrt = self.optimal_q(data, native=native)
+    with torch.no_grad():
+      self.q_mu.copy_(q_mu.to(self.q_mu))
+      self.q_sqrt.copy_(q_sqrt.to(self.q_sqrt))
+
+  def collapsed_training_loss(self, data, native: Optional[bool] = None) -> torch.Tensor:
+    """-(``collapsed_elbo`` + prior(self)): ``training_loss`` with q(u) at its optimum."""
+    objective = self.collapsed_elbo(data, native=native)
+    if self.prior is not None:
+      objective = objective + self.prior(self)
+    return -objective
 
   @classmethod
   def initialize(cls, data, num_inducing: int, likelihood=None, mean_function="default", kernels=None,

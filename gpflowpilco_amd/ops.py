@@ -1023,3 +1023,66 @@ def predict_se(X: torch.Tensor, Z: torch.Tensor, ls: torch.Tensor, var: torch.Te
                             _ptr(mean_c), mean.data_ptr(), _ptr(fvar), ws.data_ptr(), ws.numel(), _stream(Z.device)),
         "mm_predict_se")
   return mean, fvar
+
+
+_GRAM_STATS_WS: Dict[Tuple[int, int, int, int, str], torch.Tensor] = {}      # (L, M, d, Q, device) -> the workspace of mm_gram_stats_se*
+
+
+def _gram_stats_operands(who: str, X, R, Z, ls, var):
+  """Checked, contiguous float64 operands of the streamed Gram statistics, (L, M, N, d, Q) and the cached workspace."""
+  _require_device(X, R, Z, ls, var)
+  if Z.ndim != 3 or ls.shape != (Z.shape[0], Z.shape[2]) or var.shape != (Z.shape[0],):
+    raise ValueError(f"{who}: Z [L,M,d], ls [L,d], var [L] expected, got {tuple(Z.shape)}, {tuple(ls.shape)}, {tuple(var.shape)}")
+  L, M, d = Z.shape
+  if X.requires_grad or (R is not None and R.requires_grad):
+    raise ValueError(f"{who}: the data X and R are constants (the adjoint has no gradient with respect to them)")
+  if X.ndim != 2 or X.shape[1] != d:
+    raise ValueError(f"{who}: X [N,{d}] expected, got {tuple(X.shape)}")
+  N = X.shape[0]
+  if R is not None and (R.ndim != 2 or R.shape[0] != N):
+    raise ValueError(f"{who}: R [{N},Q] expected, got {tuple(R.shape)}")
+  Q = 0 if R is None else R.shape[1]
+  if Q == 0:
+    R = None
+  nbytes = lib().mm_gram_stats_workspace_bytes(L, M, N, d, Q)
+  if nbytes == 0:
+    check(-2, "mm_gram_stats_workspace_bytes")      # the size query's 0 is MM_E_DIM
+  key = (L, M, d, Q, str(Z.device))
+  ws = _GRAM_STATS_WS.get(key)
+  if ws is None or ws.numel() < nbytes:
+    ws = _GRAM_STATS_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=Z.device)
+  ops_ = [None if t is None else t.detach().to(torch.float64).contiguous() for t in (X, R, Z, ls, var)]
+  return ops_, (L, M, N, d, Q), ws
+
+
+def gram_stats_se(X: torch.Tensor, R: Optional[torch.Tensor], Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor):
+  """``mm_gram_stats_se`` (csrc/mm_gram_stats.hip): Phi [L,M,M] = K K^T and Psi [L,M,Q] = K R of the SE-ARD Gram matrix K [L,M,N]
+  between X [N,d] and Z [L,M,d] (``gram_se``'s entries), in float64, K formed tile by tile and never stored: no buffer grows with
+  N.  ``R`` None (or with no column): Phi alone, the second result is None.  Phi is symmetric to the bit.  Deterministic: two calls
+  are bit-equal.  Not differentiable by itself: ``autodiff.GramStatsSEFunction``."""
+  (X, R, Z, ls, var), (L, M, N, d, Q), ws = _gram_stats_operands("gram_stats_se", X, R, Z, ls, var)
+  Phi = torch.empty(L, M, M, dtype=torch.float64, device=Z.device)
+  Psi = None if R is None else torch.empty(L, M, Q, dtype=torch.float64, device=Z.device)
+  check(lib().mm_gram_stats_se(L, M, N, d, Q, X.data_ptr(), _ptr(R), Z.data_ptr(), ls.data_ptr(), var.data_ptr(), Phi.data_ptr(),
+                               _ptr(Psi), ws.data_ptr(), ws.numel(), _stream(Z.device)), "mm_gram_stats_se")
+  return Phi, Psi
+
+
+def gram_stats_se_backward(GPhi: torch.Tensor, GPsi: Optional[torch.Tensor], X: torch.Tensor, R: Optional[torch.Tensor],
+                           Z: torch.Tensor, ls: torch.Tensor, var: torch.Tensor):
+  """``mm_gram_stats_se_backward``: GPhi [L,M,M] (any matrix: GPhi + GPhi^T is used) and GPsi [L,M,Q] -> (gZ [L,M,d], gls [L,d],
+  gvar [L]) of ``gram_stats_se``; the adjoint of K, (GPhi + GPhi^T) K + GPsi R^T, is formed tile by tile and never stored.
+  Deterministic: two calls are bit-equal."""
+  (X, R, Z, ls, var), (L, M, N, d, Q), ws = _gram_stats_operands("gram_stats_se_backward", X, R, Z, ls, var)
+  _require_device(GPhi, GPsi)
+  if GPhi.shape != (L, M, M):
+    raise ValueError(f"gram_stats_se_backward: GPhi [{L},{M},{M}] expected, got {tuple(GPhi.shape)}")
+  if (GPsi is None) != (R is None) or (GPsi is not None and GPsi.shape != (L, M, Q)):
+    raise ValueError(f"gram_stats_se_backward: GPsi [{L},{M},{Q}] with R, or neither, expected")
+  GPhi = GPhi.detach().to(torch.float64).contiguous()
+  GPsi = None if GPsi is None else GPsi.detach().to(torch.float64).contiguous()
+  gZ, gls, gvar = torch.empty_like(Z), torch.empty_like(ls), torch.empty_like(var)
+  check(lib().mm_gram_stats_se_backward(L, M, N, d, Q, GPhi.data_ptr(), _ptr(GPsi), X.data_ptr(), _ptr(R), Z.data_ptr(),
+                                        ls.data_ptr(), var.data_ptr(), gZ.data_ptr(), gls.data_ptr(), gvar.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream(Z.device)), "mm_gram_stats_se_backward")
+  return gZ, gls, gvar

@@ -812,6 +812,25 @@ int mm_predict_se(int L, int M, int N, int d, const double* X, const double* Z, 
                   const double* beta, const double* C, const double* mean_c, double* mean, double* fvar, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- streamed Gram statistics of the collapsed (SGPR) bound and their adjoint (csrc/mm_gram_stats.hip, schedule in
+ * csrc/mm_gram_stats.h; f64, row-major) ----
+ * mm_gram_stats_se: X [N,d], R [N,Q], Z [L,M,d], ls [L,d], var [L] ->
+ *     Phi[l] = K_l K_l^T [M,M] (written in full, symmetric to the bit),   Psi[l] = K_l R [M,Q],   K_l[m][n] as mm_gram_se's.
+ *   Q == 0 with R == NULL and Psi == NULL: Phi alone (MM_E_ARG when the three disagree).
+ * mm_gram_stats_se_backward: GPhi [L,M,M] (a GENERAL matrix: GPhi + GPhi^T is used), GPsi [L,M,Q] and the same operands ->
+ *   gZ [L,M,d], gls [L,d], gvar [L]: mm_gram_se_backward's sums with G = (GPhi + GPhi^T) K + GPsi R^T, formed tile by tile.
+ *   There is no gradient with respect to X or R.
+ * K is never stored: nothing of a size proportional to L M N is allocated, written or read, and mm_gram_stats_workspace_bytes
+ * ignores N (one buffer of that size serves both entries; 0 for a rejected shape).  No atomics: two calls are bit-equal.
+ * Any L, M, N >= 1, 1 <= d <= MM_DMAX, 0 <= Q <= 33, M <= 2^15; MM_E_DIM otherwise; MM_E_WORKSPACE for a workspace below the
+ * query's size. */
+size_t mm_gram_stats_workspace_bytes(int L, int M, int N, int d, int Q);
+int mm_gram_stats_se(int L, int M, int N, int d, int Q, const double* X, const double* R, const double* Z, const double* ls,
+                     const double* var, double* Phi, double* Psi, void* workspace, size_t workspace_bytes, void* stream);
+int mm_gram_stats_se_backward(int L, int M, int N, int d, int Q, const double* GPhi, const double* GPsi, const double* X,
+                              const double* R, const double* Z, const double* ls, const double* var, double* gZ, double* gls,
+                              double* gvar, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
