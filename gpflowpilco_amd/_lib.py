@@ -35,6 +35,8 @@ MM_ISTAGE_NO_BOUND_SKIP = 1 << 27
 # internal A/B bit of the forward's f64 weight moments (csrc/mm_common.h; results are bit-identical): the 64 x 128 GEMM tiling and
 # the one-workgroup-per-item contraction
 MM_ISTAGE_OLD_WMOM = 1 << 28
+# internal A/B bit of the degree-4..6 contraction (csrc/mm_common.h; results are bit-identical): every load where its value is used
+MM_ISTAGE_OLD_SPOLY_LOADS = 1 << 29
 
 ERRORS = {
     -1: "MM_E_ARG: NULL pointer or non-positive size",

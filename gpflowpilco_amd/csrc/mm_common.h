@@ -42,6 +42,11 @@ static inline size_t mm_elem_size(int dtype) { return dtype == MM_F64 ? 8 : 4; }
 // k_spoly even where the one-pass tiling k_wmom_gemm1 and the one-wave-per-item contraction apply -- A/B tests and measurements on
 // one build; every moment the forward reads, and s12, are bit-identical
 #define MM_ISTAGE_OLD_WMOM (1 << 28)
+// degree-4..6 contraction (k_spoly56, k_spoly4: mm_moments6.hip) and the prologue of k_spoly_wave8 (mm_moments.hip): load every value where it is used -- the moments, G, the group
+// flags and the weights in loops of load / wait / use, a step's tables behind the barrier in front of it -- instead of issuing an
+// item's prologue loads together and requesting a step's tables before that barrier -- A/B tests and measurements on one build;
+// the arithmetic and every order of summation are the same: s56, estS and s12 are bit-identical
+#define MM_ISTAGE_OLD_SPOLY_LOADS (1 << 29)
 
 // kernel families of the pathwise entries' `kernel` argument (mm_pathwise_*_kern): 0 SquaredExponential, 1 Matern-3/2, 2 Matern-5/2
 #define MM_PW_KERNELS 3

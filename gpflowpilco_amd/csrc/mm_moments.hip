@@ -540,6 +540,10 @@ __global__ __launch_bounds__(256) void k_spoly(const double* __restrict__ mom, i
 // `total` / `part` accumulator each and the stride of 256 in every dot; the final sum is mm_block_sum256m's -- the shuffle tree
 // per virtual wave, then red[0] + red[1] + red[2] + red[3].  Filling T, the fibre transforms and the dmu contractions are
 // per-element and do not depend on who runs them.
+// PRE: the item's prologue in two round trips to global memory -- the item's words, G, mu and zbar together; then, the column count
+// known, all the lane's moments (<= 3 columns x 2 sides x the k slices) -- where the loops of load / wait / use took one per column
+// round and one each for the words, G and dmu; !PRE (MM_ISTAGE_OLD_SPOLY_LOADS): those loops.  The k slices of a column are summed
+// in the same order.  (The index tables rtab are still read where the loops use them, inside the item's own arithmetic.)
 // ---------------------------------------------------------------------------------------------
 #define MM_SPW_WAVES 4
 __device__ __forceinline__ void mm_wave_sync_m() {
@@ -550,6 +554,7 @@ __device__ __forceinline__ void mm_wave_sync_m() {
 // doubles of one wave's slice: T [8^3], U [8^2] (both padded), ncs row-side and ncs column-side moments, G, dmu
 static inline int mm_spw_slice(int ncs) { return 512 + 16 + 64 + 2 + 2 * ncs + 64 + 8; }
 
+template <bool PRE>
 __global__ __launch_bounds__(64 * MM_SPW_WAVES) void k_spoly_wave8(const double* __restrict__ mom, int KMp, const double* __restrict__ pairmat,
                                                                    const double* __restrict__ zbar, const unsigned int* __restrict__ amax,
                                                                    const unsigned int* __restrict__ amaxc, const float* __restrict__ mu,
@@ -574,19 +579,52 @@ __global__ __launch_bounds__(64 * MM_SPW_WAVES) void k_spoly_wave8(const double*
   double* qh = nh + ncs;
   double* Gs = qh + ncs;
   double* dmu = Gs + DK * DK;
-  const bool coll = allow_collapse && mm_item_collapsed(amaxc[(size_t)b * Po + po]);
-  const int nmax = coll ? DEG : 2;
-  {
+  const double* nm = mom + (((size_t)b * Po + po) * 2 + 0) * MM_MOM_SPLIT * KMp;
+  const double* qm = mom + (((size_t)b * Po + po) * 2 + 1) * MM_MOM_SPLIT * KMp;
+  const double* pm = pairmat + ((size_t)b * P + p) * (d * d + 1);
+  bool coll;
+  if constexpr (PRE) {
+    const int gi = lane >> LB, gj = lane & (DK - 1);
+    const bool gok = gi < d && gj < d, mok = lane < DK && lane < d;
+    const unsigned int wc = amaxc[(size_t)b * Po + po], wa = amax[(size_t)b * Po + po];
+    const double g = pm[gok ? gi * d + gj : 0];
+    const float mu_l = mu[(size_t)b * d + (mok ? lane : 0)];
+    const double zb_l = zbar[a * d + (mok ? lane : 0)];
+    coll = allow_collapse && mm_item_collapsed(wc);
     const int ncol = coll ? off4 : off3;                   // columns of degree <= nmax
-    const double* nm = mom + (((size_t)b * Po + po) * 2 + 0) * MM_MOM_SPLIT * KMp;
-    const double* qm = mom + (((size_t)b * Po + po) * 2 + 1) * MM_MOM_SPLIT * KMp;
+    constexpr int NK = 3;                                  // (d <= 8: off4 <= 165 columns, at most three per lane)
+    double vn[NK][MM_MOM_SPLIT], vq[NK][MM_MOM_SPLIT];
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      const int k = lane + 64 * i, kc = k < ncol ? k : 0;
+#pragma unroll
+      for (int t = 0; t < MM_MOM_SPLIT; ++t) { vn[i][t] = nm[t * KMp + kc]; vq[i][t] = qm[t * KMp + kc]; }
+    }
+    Gs[lane] = gok ? g : 0.0;
+    if (lane < DK) dmu[lane] = (mok && !mm_rows_recentred(wa)) ? (double)mu_l - zb_l : 0.0;
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      const int k = lane + 64 * i;
+      double sn = 0.0, sq = 0.0;                           // fixed summation order of the split-K partials
+#pragma unroll
+      for (int t = 0; t < MM_MOM_SPLIT; ++t) { sn += vn[i][t]; sq += vq[i][t]; }
+      if (k < ncol) { nh[k] = sn; qh[k] = sq; }
+    }
+    for (int k = lane + 64 * NK; k < ncol; k += 64) {      // (no such column at d <= 8)
+      double sn = 0.0, sq = 0.0;
+#pragma unroll
+      for (int t = 0; t < MM_MOM_SPLIT; ++t) { sn += nm[t * KMp + k]; sq += qm[t * KMp + k]; }
+      nh[k] = sn; qh[k] = sq;
+    }
+  } else {
+    coll = allow_collapse && mm_item_collapsed(amaxc[(size_t)b * Po + po]);
+    const int ncol = coll ? off4 : off3;                   // columns of degree <= nmax
     for (int k = lane; k < ncol; k += 64) {                // fixed summation order of the split-K partials
       double sn = 0.0, sq = 0.0;
 #pragma unroll
       for (int t = 0; t < MM_MOM_SPLIT; ++t) { sn += nm[t * KMp + k]; sq += qm[t * KMp + k]; }
       nh[k] = sn; qh[k] = sq;
     }
-    const double* pm = pairmat + ((size_t)b * P + p) * (d * d + 1);
     {
       const int i = lane >> LB, j = lane & (DK - 1);
       Gs[lane] = (i < d && j < d) ? pm[i * d + j] : 0.0;
@@ -594,6 +632,7 @@ __global__ __launch_bounds__(64 * MM_SPW_WAVES) void k_spoly_wave8(const double*
     const bool rcen = mm_rows_recentred(amax[(size_t)b * Po + po]);
     if (lane < DK) dmu[lane] = (lane < d && !rcen) ? (double)mu[(size_t)b * d + lane] - zbar[a * d + lane] : 0.0;
   }
+  const int nmax = coll ? DEG : 2;
   mm_wave_sync_m();
   double Gr[64];
 #pragma unroll
@@ -722,7 +761,7 @@ static int mm_launch_wmom_onepass(const char* packed, const MMModelLayout& ml, c
 }
 
 int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
-                        int B, int L, int d, int allow, int old_spoly56, hipStream_t stream);
+                        int B, int L, int d, int allow, int old_spoly56, int old_loads, hipStream_t stream);
 
 int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
                       int B, int L, int d, const void* mu_f32, int flags, hipStream_t stream) {
@@ -784,7 +823,9 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
     const int ncs = (off4 + 7) & ~7;                        // (deg = 3 here: the columns below off4 are all an item reads)
     const int slice = mm_spw_slice(ncs);
     const int nitem = B * wl.Po;
-    hipLaunchKernelGGL(k_spoly_wave8, dim3((nitem + MM_SPW_WAVES - 1) / MM_SPW_WAVES), dim3(64 * MM_SPW_WAVES),
+    // (MM_ISTAGE_OLD_SPOLY_LOADS, mm_common.h: the prologue's loads where their values are used)
+    const auto kw8 = (flags & MM_ISTAGE_OLD_SPOLY_LOADS) ? k_spoly_wave8<false> : k_spoly_wave8<true>;
+    hipLaunchKernelGGL(kw8, dim3((nitem + MM_SPW_WAVES - 1) / MM_SPW_WAVES), dim3(64 * MM_SPW_WAVES),
                        (size_t)MM_SPW_WAVES * slice * sizeof(double), stream, (const double*)mom, ml.KMp,
                        (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zbar), (const unsigned int*)(ws + wl.amax),
                        (const unsigned int*)(ws + wl.amaxc), (const float*)mu_f32, L, d, wl.P, B, allow, off1, off2, off3, off4,
@@ -804,7 +845,8 @@ int mm_launch_moments(const char* packed, const MMModelLayout& ml, char* ws, con
     return es == hipSuccess ? 0 : (int)es;
   }
   // orders 5 and 6 of the collapsed items (f32 moments on the bf16 matrix pipe: mm_moments6.hip) -> s56, estS
-  return mm_launch_moments56(packed, ml, ws, wl, B, L, d, some ? 1 : 0, (flags & MM_ISTAGE_OLD_SPOLY56) ? 1 : 0, stream);
+  return mm_launch_moments56(packed, ml, ws, wl, B, L, d, some ? 1 : 0, (flags & MM_ISTAGE_OLD_SPOLY56) ? 1 : 0,
+                             (flags & MM_ISTAGE_OLD_SPOLY_LOADS) ? 1 : 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -269,10 +269,58 @@ __global__ __launch_bounds__(256, 2) void k_wmom56_gemm(const unsigned short* __
 #ifndef MM6_NC
 #define MM6_NC 2
 #endif
-template <int K, bool TRANSG, int MODE, int NC = MM6_NC, int NW = MM6_WAVES>
+// A step's tables for the wave's FIRST chunk group -- the gather offsets ins[J'][8] and, MODE 1, multJ[J'] -- as they come from
+// the packed model.  PRE steps take them from the caller, who requests them (mm6_request / mm6_request8) after the previous step's
+// unit loop and BEFORE the barrier that ends it: the round trip to global memory runs while the wave waits for the others, and its
+// s_waitcnt falls behind the barrier.  The 4 NC (+ NC) registers live across that barrier only, never across a unit loop.  A lane
+// past the end of J' (and a wave without a unit) requests the last entry: every address is inside the table.
+typedef unsigned int mm6_u4 __attribute__((ext_vector_type(4), aligned(8)));   // ins[J'][0..7]: eight shorts
+template <int NC> struct mm6_pre { mm6_u4 w[NC]; float mj[NC]; };
+
+// behind the barrier: the registers are USED here, in the barrier's own block -- the compiler otherwise sinks the request into the
+// first conditional block that reads it, behind the barrier again
+template <int MODE, int NC>
+__device__ __forceinline__ void mm6_pre_arrived(mm6_pre<NC>& pre) {
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    asm volatile("" : "+v"(pre.w[q]));
+    if constexpr (MODE == 1) asm volatile("" : "+v"(pre.mj[q]));
+  }
+}
+
+template <int NC>
+__device__ __forceinline__ void mm6_pre_offsets(const mm6_pre<NC>& pre, int (&off)[NC][8], float (&mj)[NC]) {
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      off[q][2 * j] = (int)(short)(pre.w[q][j] & 0xffffu);
+      off[q][2 * j + 1] = (int)pre.w[q][j] >> 16;
+    }
+    mj[q] = pre.mj[q];
+  }
+}
+
+// the request of mm6_step<K, ., MODE, NC, .>: chunk group of the wave's first unit u = wave
+template <int K, int MODE, int NC>
+__device__ __forceinline__ void mm6_request(mm6_pre<NC>& pre, int nI, int nJp, const short* __restrict__ ins,
+                                            const float* __restrict__ multJ, int wave, int lane) {
+  int c = K == 0 ? wave : (int)(((float)wave + 0.5f) * (1.0f / (float)nI));
+  c = __builtin_amdgcn_readfirstlane(c);
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const int Jp = (c * NC + q) * 64 + lane;
+    const int Jc = Jp < nJp ? Jp : nJp - 1;
+    pre.w[q] = *reinterpret_cast<const mm6_u4*>(ins + (size_t)Jc * 8);
+    pre.mj[q] = 0.0f;
+    if constexpr (MODE == 1) pre.mj[q] = multJ[Jc];
+  }
+}
+
+template <int K, bool TRANSG, int MODE, int NC = MM6_NC, int NW = MM6_WAVES, bool PRE = false>
 __device__ __forceinline__ void mm6_step(const float* __restrict__ Tin, int nJin, int nI, float* __restrict__ Tout, int nJp,
                                          const short* __restrict__ ins, int d, const float (&G)[64], const float* __restrict__ multJ,
-                                         int xs, float& acc, int wave, int lane) {
+                                         int xs, float& acc, int wave, int lane, const mm6_pre<NC>& pre) {
   const int chunks = (nJp + 64 * NC - 1) / (64 * NC);
   // the outputs i = I0 .. 7 of one (I, J'): eight-term dot products of the gathered v with the matrix the caller loaded into G as
   // G[j * 8 + i] = (coefficient of v_j in output i) -- output index fastest, so that the packed FMA over an output pair (i, i + 1)
@@ -333,6 +381,18 @@ __device__ __forceinline__ void mm6_step(const float* __restrict__ Tin, int nJin
   float mj[NC];
 #pragma unroll
   for (int q = 0; q < NC; ++q) { Jc[q] = 0; jv[q] = false; mj[q] = 0.0f; }
+  if constexpr (PRE) {
+    // the chunk group of the first unit u = wave: its tables were requested by the caller (mm6_request)
+    cprev = K == 0 ? wave : (int)(((float)wave + 0.5f) * rnI);
+    cprev = __builtin_amdgcn_readfirstlane(cprev);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      const int Jp = (cprev * NC + q) * 64 + lane;
+      jv[q] = Jp < nJp;
+      Jc[q] = jv[q] ? Jp : nJp - 1;
+    }
+    mm6_pre_offsets<NC>(pre, off, mj);
+  }
   for (int u = wave; u < nunit; u += NW) {
     int c = K == 0 ? u : (int)(((float)u + 0.5f) * rnI);   // u / nI (exact: u < 2^20)
     c = __builtin_amdgcn_readfirstlane(c);
@@ -384,9 +444,37 @@ constexpr int mm6_cbinom(int n, int k) {
 }
 constexpr int mm6_sym8(int k) { return mm6_cbinom(8 + k - 1, k); }   // sym(k) at d = 8: 1, 8, 36, 120, 330, 792, 1716
 
-template <int K, int MODE, int NJIN, int NJP, int XS, int NC, int NW>
+// chunk group of the wave's first unit in mm6_step8<K, MODE, ., NJP, ., NC, NW> (its four unit-to-wave maps below)
+template <int K, int MODE, int NJP, int NC, int NW>
+__device__ __forceinline__ int mm6_first_c8(int wave) {
+  constexpr int NI = mm6_sym8(K);
+  constexpr int CH = (NJP + 64 * NC - 1) / (64 * NC);
+  if constexpr (CH == 1) return 0;
+  else if constexpr (NI == 1) return wave;
+  else if constexpr (MODE != 2 && NW % CH == 0) return wave % CH;
+  else return wave / NI;
+}
+
+// the request of mm6_step8<K, MODE, ., NJP, ., NC, NW> (mm6_pre)
+template <int K, int MODE, int NJP, int NC, int NW>
+__device__ __forceinline__ void mm6_request8(mm6_pre<NC>& pre, const short* __restrict__ ins, const float* __restrict__ multJ,
+                                             int wave, int lane) {
+  asm volatile("" : "+v"(lane));                         // (the addresses are formed here, per request: see mm6_step8)
+  const int c = mm6_first_c8<K, MODE, NJP, NC, NW>(wave);
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const int Jp = (c * NC + q) * 64 + lane;
+    const int Jc = Jp < NJP ? Jp : NJP - 1;
+    pre.w[q] = *reinterpret_cast<const mm6_u4*>(ins + (size_t)Jc * 8);
+    pre.mj[q] = 0.0f;
+    if constexpr (MODE == 1) pre.mj[q] = multJ[Jc];
+  }
+}
+
+template <int K, int MODE, int NJIN, int NJP, int XS, int NC, int NW, bool PRE = false>
 __device__ __forceinline__ void mm6_step8(const float* __restrict__ Tin_, float* __restrict__ Tout_, const short* __restrict__ ins,
-                                          const float (&G)[64], const float* __restrict__ multJ, float& acc, int wave, int lane) {
+                                          const float (&G)[64], const float* __restrict__ multJ, float& acc, int wave, int lane,
+                                          const mm6_pre<NC>& pre) {
   // (the lane's table addresses are formed here, per step: hoisted out of the item loop for every step at once -- they depend on
   // the lane alone -- they were spilled to scratch)
   asm volatile("" : "+v"(lane));
@@ -419,6 +507,26 @@ __device__ __forceinline__ void mm6_step8(const float* __restrict__ Tin_, float*
       off[q][0] = ia.x; off[q][1] = ia.y; off[q][2] = ia.z; off[q][3] = ia.w;
       off[q][4] = ib.x; off[q][5] = ib.y; off[q][6] = ib.z; off[q][7] = ib.w;
       if constexpr (MODE == 1) mj[q] = multJ[Jc[q]];
+    }
+  };
+  // PRE: the wave's first chunk group c = mm6_first_c8(wave) from the tables the caller requested
+  auto take_c = [&](int c) __attribute__((always_inline)) {
+    if constexpr (PRE) {
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        const int Jp = (c * NC + q) * 64 + lane;
+        jv[q] = Jp < NJP;
+        Jc[q] = jv[q] ? Jp : NJP - 1;
+      }
+      mm6_pre_offsets<NC>(pre, off, mj);
+      // (unpacked HERE, once: the compiler otherwise keeps the packed words and unpacks them again in every unit)
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(off[q][j]));
+      }
+    } else {
+      load_c(c);
     }
   };
   // one unit whose outputs start in the pair (I0, I0 + 1): t = I0 (first) or I0 + 1
@@ -516,25 +624,26 @@ __device__ __forceinline__ void mm6_step8(const float* __restrict__ Tin_, float*
   // (chunk 0 of a group is never wholly past the end: jv[0] is a lane mask)
   if constexpr (CH == 1) {
     if (wave < NI) {
-      load_c(0);
+      take_c(0);
       for (int I = wave; I < NI; I += NW)
         if (jv[0]) unit(I);
     }
   } else if constexpr (NI == 1) {
     for (int c = wave; c < CH; c += NW) {
-      load_c(c);
+      if (PRE && c == wave) take_c(c); else load_c(c);   // (CH <= NW wherever this runs: one group per wave)
       if (jv[0]) unit(0);
     }
   } else if constexpr (MODE != 2 && NW % CH == 0) {
     // wave -> (chunk group wave % CH, I = wave / CH, + NW / CH, ..)
     const int c = wave % CH;
-    load_c(c);
+    take_c(c);
     for (int I = wave / CH; I < NI; I += NW / CH)
       if (jv[0]) unit(I);
   } else {
     // units (c, I), I fastest, round robin as in mm6_step (the fused dot keeps its order of summation whatever NC is): the offsets
     // are reloaded when c changes
     int cprev = -1;
+    if constexpr (PRE) { cprev = wave / NI; take_c(cprev); }
     for (int u = wave; u < CH * NI; u += NW) {
       const int c = u / NI, I = u - c * NI;
       if (c != cprev) { cprev = c; load_c(c); }
@@ -544,15 +653,55 @@ __device__ __forceinline__ void mm6_step8(const float* __restrict__ Tin_, float*
 }
 
 // one contraction step of the kernels below: from sym(KIN) to sym(KIN - 1) values of J'; D8: the d = 8 form
-template <bool D8, int K, bool TRANSG, int MODE, int NC, int NW, int KIN, int XS8>
+// PRE: the tables of the wave's first chunk group come from the caller (mm6_req of the same <D8, K, MODE, NC, NW, KIN>)
+template <bool D8, int K, bool TRANSG, int MODE, int NC, int NW, int KIN, int XS8, bool PRE = false>
 __device__ __forceinline__ void mm6_do(const float* __restrict__ Tin, float* __restrict__ Tout, const int* sy, const short* __restrict__ tabi,
                                        const MMTab56& tb, int d, const float (&G)[64], const float* __restrict__ multJ, int xs,
-                                       float& acc, int wave, int lane) {
+                                       float& acc, int wave, int lane, const mm6_pre<NC>& pre = mm6_pre<NC>{}) {
   if constexpr (D8)
-    mm6_step8<K, MODE, mm6_sym8(KIN), mm6_sym8(KIN - 1), XS8, NC, NW>(Tin, Tout, tabi + tb.ins[KIN - 1], G, multJ, acc, wave, lane);
+    mm6_step8<K, MODE, mm6_sym8(KIN), mm6_sym8(KIN - 1), XS8, NC, NW, PRE>(Tin, Tout, tabi + tb.ins[KIN - 1], G, multJ, acc, wave, lane, pre);
   else
-    mm6_step<K, TRANSG, MODE, NC, NW>(Tin, sy[KIN], sy[K], Tout, sy[KIN - 1], tabi + tb.ins[KIN - 1], d, G, multJ, xs, acc, wave, lane);
+    mm6_step<K, TRANSG, MODE, NC, NW, PRE>(Tin, sy[KIN], sy[K], Tout, sy[KIN - 1], tabi + tb.ins[KIN - 1], d, G, multJ, xs, acc, wave, lane, pre);
 }
+
+template <bool D8, int K, int MODE, int NC, int NW, int KIN>
+__device__ __forceinline__ void mm6_req(mm6_pre<NC>& pre, const int* sy, const short* __restrict__ tabi, const MMTab56& tb,
+                                        const float* __restrict__ multJ, int wave, int lane) {
+  if constexpr (D8) mm6_request8<K, MODE, mm6_sym8(KIN - 1), NC, NW>(pre, tabi + tb.ins[KIN - 1], multJ, wave, lane);
+  else mm6_request<K, MODE, NC>(pre, sy[K], sy[KIN - 1], tabi + tb.ins[KIN - 1], multJ, wave, lane);
+}
+
+// The prologue loads of an item (PRE kernels): every thread issues ALL its loads -- the moments, the element of G, the group
+// flags and the weights -- and waits once; as loops of load / wait / use they were 8 + 1 + 2 ceil(Mp / threads) round trips to
+// global memory one after another, at one workgroup per CU with nothing else to run.
+template <int W> struct mm6_vecw { typedef float type __attribute__((ext_vector_type(W))); };
+constexpr int mm6_vec_width(int n) { return n <= 4 ? 4 : (n <= 8 ? 8 : 16); }
+
+// sum of whR[m]^2 over the rows of the collapsed groups, of whC[m]^2 over all rows: a thread's m = tid, tid + T, .. in that order
+// (as the loop it replaces: estS is bit-equal), U of them per round trip.  whR is read whatever the flag says (k_pairvec_reg
+// writes every m < Mp) and 0.0 is SELECTED where the loop branched.
+template <int T, int U>
+struct mm6_s2_batch {
+  unsigned char f[U];
+  double x[U], y[U];
+  __device__ __forceinline__ void issue(const unsigned char* __restrict__ gf, const double* __restrict__ hr, const double* __restrict__ hc,
+                                        int m0, int Mp) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int m = m0 + u * T, mc = m < Mp ? m : 0;
+      f[u] = gf[mc >> 6]; x[u] = hr[mc]; y[u] = hc[mc];
+    }
+  }
+  __device__ __forceinline__ void add(int m0, int Mp, double& s2r, double& s2c) const {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool in = m0 + u * T < Mp;
+      const double xx = f[u] ? x[u] : 0.0;
+      const double r = fma(xx, xx, s2r), c = fma(y[u], y[u], s2c);
+      s2r = in ? r : s2r; s2c = in ? c : s2c;
+    }
+  }
+};
 
 // Work lists by collapse degree (MMWorkspaceLayout::ilist): the contractions run over the items that need them, the degree-6/5 ones
 // in workgroups of MM6_THREADS threads with 160 KB of LDS (one per CU), the degree-4 ones -- every item of the pilco recipe --
@@ -599,8 +748,10 @@ __device__ __forceinline__ float mm6_estS(float bound2, bool need5, bool need6, 
   return (float)fmin((double)MM_C6_SYS2 * (amp * amp) * r2 * c2, 3.0e38);
 }
 
-// grid: persistent over the degree-6 / degree-5 items of ilist (any size; one workgroup per CU fits).  D8: d == 8, the steps are mm6_step8
-template <bool D8>
+// grid: persistent over the degree-6 / degree-5 items of ilist (any size; one workgroup per CU fits).  D8: d == 8, the steps are mm6_step8.
+// PRE: the item's prologue issues all its loads and waits once, and every phase's first step takes its tables from a request made
+// before the barrier in front of it (mm6_pre); !PRE (MM_ISTAGE_OLD_SPOLY_LOADS): load where the value is used.  Same arithmetic.
+template <bool D8, bool PRE>
 __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict__ mom56, int N56p, const double* __restrict__ pairmat,
                                                  const double* __restrict__ zmax2, const unsigned int* __restrict__ amaxc,
                                                  const unsigned char* __restrict__ gflag,
@@ -636,38 +787,93 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
   float* A = X + sy[3] * xs;
   float* Bf = A + sy[2] * sy[4];
   float* red = sm6 + ((2 * n56 + sy[3] * xs + sy[2] * sy[4] + sy[1] * sy[5] + 1) & ~1);   // [MM6_WAVES][3] doubles (8-byte aligned)
-  for (int idx = tid; idx < 2 * n56; idx += MM6_THREADS) {
-    const int side = idx >= n56, c = idx - side * n56;
+  const short* tabi = (const short*)tab;
+  const float* mult2 = (const float*)(tab + (size_t)tb.n_i16 * 2) + tb.mult2;
+  const float* mult3 = (const float*)(tab + (size_t)tb.n_i16 * 2) + tb.mult3;
+  // the nq entry idx -> (side, column of mom56; whether the item reads it: degree 4, or what its bound leaves in)
+  auto nq_col = [&](int idx, int& side, int& col) __attribute__((always_inline)) {
+    side = idx >= n56;
+    const int c = idx - side * n56;
     const int dg = c < sy[4] ? 4 : (c < sy[4] + sy[5] ? 5 : 6);
-    const int col = dg == 4 ? c : (dg == 5 ? off5 + (c - sy[4]) : off6 + (c - sy[4] - sy[5]));
-    float v = 0.0f;
-    if (dg == 4 || (dg == 5 ? need5 : need6)) v = mom56[(item * 2 + side) * N56p + col];
-    nq[idx] = v;
-  }
+    col = dg == 4 ? c : (dg == 5 ? off5 + (c - sy[4]) : off6 + (c - sy[4] - sy[5]));
+    return dg == 4 || (dg == 5 ? need5 : need6);
+  };
   // G in VECTOR registers (through LDS): as 64 scalar registers beside the loop's own scalars it spilled to VGPR lanes
   // (780 v_readlane / v_writelane in the kernel, 47 per work unit)
   float* Gl = sm6 + ((2 * n56 + sy[3] * xs + sy[2] * sy[4] + sy[1] * sy[5] + 6 * MM6_WAVES + 2 + 3) & ~3);   // [128], 16-byte aligned
   float* Bf4 = Gl + 128;                                 // n = 4: T_1 [sym1][sym3]
   float* X4 = Bf4 + sy[1] * sy[3];                       //        X [sym2][sym2 + 1]
-  if (tid < 64) {
-    const int i = tid >> 3, j = tid & 7;
-    const double* pm = pairmat + ((size_t)b * P + (L + po)) * (d * d + 1);
-    const float g = (i < d && j < d) ? (float)pm[i * d + j] : 0.0f;
-    Gl[tid] = g;                                         // row-major: the Y side's (G^T applied: output j' takes G[m][j'])
-    Gl[64 + j * 8 + i] = g;                              // transposed: the X side's (output i takes G[i][j])
-  }
+  const double* pm = pairmat + ((size_t)b * P + (L + po)) * (d * d + 1);
+  const double* hr = whR + item * Mp;
+  const double* hc = whC + item * Mp;
+  const unsigned char* gf = gflag + item * (size_t)(Mp / MM_GROUP_ROWS);
   // what the skipped tiles leave out, in the units of the sweep's error estimate (mm_common.h: MM_C6_SYS2)
   double s2r = 0.0, s2c = 0.0;
-  {
-    const double* hr = whR + item * Mp;
-    const double* hc = whC + item * Mp;
-    const unsigned char* gf = gflag + item * (size_t)(Mp / MM_GROUP_ROWS);
+  mm6_pre<NC> p0 = {};                                      // the tables of the next phase's first step (mm6_pre)
+  mm6_pre<1> p1 = {};
+  if constexpr (PRE) {
+    // every load of the prologue is issued before the first wait: the weights and flags, G, the moments, the first step's tables
+    // (the thread's indices are formed here, per item: hoisted out of the item loop they live across every unit loop)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    constexpr int S2U = 4;
+    mm6_s2_batch<MM6_THREADS, S2U> sb;
+    sb.issue(gf, hr, hc, tid, Mp);
+    const int gi = tid >> 3, gj = tid & 7;
+    const bool gok = tid < 64 && gi < d && gj < d;
+    const double gd = pm[gok ? gi * d + gj : 0];
+    // (d <= 8: the count at d = 8 bounds every d)
+    constexpr int NQL = (2 * (mm6_sym8(4) + mm6_sym8(5) + mm6_sym8(6)) + MM6_THREADS - 1) / MM6_THREADS;
+    static_assert(NQL <= 16, "the moments of one thread as one register tuple");
+    typename mm6_vecw<mm6_vec_width(NQL)>::type r = 0.0f;
+    const float* mrow = mom56 + item * 2 * N56p;
+#pragma unroll
+    for (int q = 0; q < NQL; ++q) {
+      const int idx = tid + q * MM6_THREADS;
+      int side, col;
+      const bool ld = nq_col(idx, side, col) && idx < 2 * n56;
+      r[q] = mrow[ld ? side * N56p + col : 0];             // (a column the item leaves out: the first one instead, and 0.0 below)
+    }
+    if (need6) mm6_req<D8, 0, 0, NC, NW, 6>(p0, sy, tabi, tb, nullptr, wave, lane);
+    else mm6_req<D8, 0, 0, NC, NW, 5>(p0, sy, tabi, tb, nullptr, wave, lane);
+    asm volatile("" : "+v"(r));                            // ONE wait for the moments: every element is needed here
+#pragma unroll
+    for (int q = 0; q < NQL; ++q) {
+      const int idx = tid + q * MM6_THREADS;
+      int side, col;
+      const bool ld = nq_col(idx, side, col);
+      if (idx < 2 * n56) nq[idx] = ld ? r[q] : 0.0f;
+    }
+    if (tid < 64) {
+      const float g = gok ? (float)gd : 0.0f;
+      Gl[tid] = g;                                         // row-major: the Y side's (G^T applied: output j' takes G[m][j'])
+      Gl[64 + gj * 8 + gi] = g;                            // transposed: the X side's (output i takes G[i][j])
+    }
+    sb.add(tid, Mp, s2r, s2c);
+    for (int m0 = tid + S2U * MM6_THREADS; m0 < Mp; m0 += S2U * MM6_THREADS) {
+      sb.issue(gf, hr, hc, m0, Mp);
+      sb.add(m0, Mp, s2r, s2c);
+    }
+  } else {
+    for (int idx = tid; idx < 2 * n56; idx += MM6_THREADS) {
+      int side, col;
+      float v = 0.0f;
+      if (nq_col(idx, side, col)) v = mom56[(item * 2 + side) * N56p + col];
+      nq[idx] = v;
+    }
+    if (tid < 64) {
+      const int i = tid >> 3, j = tid & 7;
+      const float g = (i < d && j < d) ? (float)pm[i * d + j] : 0.0f;
+      Gl[tid] = g;                                         // row-major: the Y side's (G^T applied: output j' takes G[m][j'])
+      Gl[64 + j * 8 + i] = g;                              // transposed: the X side's (output i takes G[i][j])
+    }
     for (int m = tid; m < Mp; m += MM6_THREADS) {
       const double x = gf[m >> 6] ? hr[m] : 0.0, y = hc[m];     // (the rows of the collapsed groups)
       s2r = fma(x, x, s2r); s2c = fma(y, y, s2c);
     }
   }
   __syncthreads();
+  if constexpr (PRE) mm6_pre_arrived<0>(p0);
   float G[64];
   auto load_G = [&](int transposed) __attribute__((always_inline)) {
 #pragma unroll
@@ -676,33 +882,45 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
       G[4 * q] = g4.x; G[4 * q + 1] = g4.y; G[4 * q + 2] = g4.z; G[4 * q + 3] = g4.w;
     }
   };
-  const short* tabi = (const short*)tab;
-  const float* mult2 = (const float*)(tab + (size_t)tb.n_i16 * 2) + tb.mult2;
-  const float* mult3 = (const float*)(tab + (size_t)tb.n_i16 * 2) + tb.mult3;
   float acc5 = 0.0f, acc6 = 0.0f, dummy = 0.0f;
   // ---- n = 6: X = three indices of Q_6 (column side of nq) through G; Y = three indices of N_6 through G^T, fused dot
+  // (PRE: before every barrier the request of the step behind it -- the same <K, MODE, NC, KIN> as that step)
   if (need6) {
     const float* Q6 = nq + n56 + sy[4] + sy[5];
     const float* N6 = nq + sy[4] + sy[5];
     load_G(1);
-    mm6_do<D8, 0, false, 0, NC, NW, 6, 0>(Q6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, false, 0, NC, NW, 6, 0, PRE>(Q6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 1, 0, NC, NW, 5>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
-    mm6_do<D8, 1, false, 0, NC, NW, 5, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
+    mm6_do<D8, 1, false, 0, NC, NW, 5, 0, PRE>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 2, 1, NC, NW, 4>(p0, sy, tabi, tb, mult3, wave, lane);
     __syncthreads();
-    mm6_do<D8, 2, false, 1, NC, NW, 4, 121>(A, X, sy, tabi, tb, d, G, mult3, xs, dummy, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<1>(p0);
+    mm6_do<D8, 2, false, 1, NC, NW, 4, 121, PRE>(A, X, sy, tabi, tb, d, G, mult3, xs, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 0, 0, NC, NW, 6>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
     load_G(0);
-    mm6_do<D8, 0, true, 0, NC, NW, 6, 0>(N6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, true, 0, NC, NW, 6, 0, PRE>(N6, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 1, 0, NC, NW, 5>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
-    mm6_do<D8, 1, true, 0, NC, NW, 5, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
+    mm6_do<D8, 1, true, 0, NC, NW, 5, 0, PRE>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 2, 2, NC, NW, 4>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
-    mm6_do<D8, 2, true, 2, NC, NW, 4, 121>(A, X, sy, tabi, tb, d, G, nullptr, xs, acc6, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<2>(p0);
+    mm6_do<D8, 2, true, 2, NC, NW, 4, 121, PRE>(A, X, sy, tabi, tb, d, G, nullptr, xs, acc6, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 0, 0, NC, NW, 5>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
   }
   // ---- n = 5 (X [sym3][sym2] = three indices of Q_5 through G; Y = two indices of N_5 through G^T, fused dot) and n = 4 (every
   // collapsed item: X4 [sym2][sym2] = two indices of Q_4; Y = two indices of N_4) in the SAME barrier phases: the n = 4 steps are
   // 1 / 8 / 1 / 8 work units on buffers of their own (Bf4, X4: 9 KB) -- as a pass of its own they cost four nearly empty rounds
-  // per item (0.15 ms at C3); merged, a few waves take one more unit per phase
+  // per item (0.15 ms at C3); merged, a few waves take one more unit per phase.  (PRE: the requests serve the n = 5 steps, the
+  // first of their phases -- every item of this kernel has them; the n = 4 steps behind them load their own tables: held over the
+  // n = 5 step's unit loop the registers would count against it)
   float acc4 = 0.0f;
   {
     const float* Q5 = nq + n56 + sy[4];
@@ -711,21 +929,29 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
     const float* N4 = nq;
     const int xs4 = sy[2] + 1;
     load_G(1);
-    if (need5) mm6_do<D8, 0, false, 0, NC, NW, 5, 0>(Q5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if (need5) mm6_do<D8, 0, false, 0, NC, NW, 5, 0, PRE>(Q5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
     mm6_do<D8, 0, false, 0, NC, NW, 4, 0>(Q4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if constexpr (PRE) { if (need5) mm6_req<D8, 1, 0, NC, NW, 4>(p0, sy, tabi, tb, nullptr, wave, lane); }
     __syncthreads();
-    if (need5) mm6_do<D8, 1, false, 0, NC, NW, 4, 0>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
+    if (need5) mm6_do<D8, 1, false, 0, NC, NW, 4, 0, PRE>(Bf, A, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
     mm6_do<D8, 1, false, 1, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, mult2, xs4, dummy, wave, lane);   // (J' = sym2 <= 36: one chunk)
+    if constexpr (PRE) { if (need5) mm6_req<D8, 2, 1, 1, NW, 3>(p1, sy, tabi, tb, mult2, wave, lane); }
     __syncthreads();
+    if constexpr (PRE) mm6_pre_arrived<1>(p1);
     if (need5) {
-      mm6_do<D8, 2, false, 1, 1, NW, 3, 121>(A, X, sy, tabi, tb, d, G, mult2, xs, dummy, wave, lane);
+      mm6_do<D8, 2, false, 1, 1, NW, 3, 121, PRE>(A, X, sy, tabi, tb, d, G, mult2, xs, dummy, wave, lane, p1);
+      if constexpr (PRE) mm6_req<D8, 0, 0, NC, NW, 5>(p0, sy, tabi, tb, nullptr, wave, lane);
       __syncthreads();
+      if constexpr (PRE) mm6_pre_arrived<0>(p0);
     }
     load_G(0);
-    if (need5) mm6_do<D8, 0, true, 0, NC, NW, 5, 0>(N5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if (need5) mm6_do<D8, 0, true, 0, NC, NW, 5, 0, PRE>(N5, Bf, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
     mm6_do<D8, 0, true, 0, NC, NW, 4, 0>(N4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    if constexpr (PRE) { if (need5) mm6_req<D8, 1, 2, NC, NW, 4>(p0, sy, tabi, tb, nullptr, wave, lane); }
     __syncthreads();
-    if (need5) mm6_do<D8, 1, true, 2, NC, NW, 4, 121>(Bf, X, sy, tabi, tb, d, G, nullptr, xs, acc5, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<2>(p0);
+    if (need5) mm6_do<D8, 1, true, 2, NC, NW, 4, 121, PRE>(Bf, X, sy, tabi, tb, d, G, nullptr, xs, acc5, wave, lane, p0);
     mm6_do<D8, 1, true, 2, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, nullptr, xs4, acc4, wave, lane);
   }
   double tot = (double)MM_C6_C1 * (double)acc4 + (double)MM_C6_C2 * (double)acc5 + (double)MM_C6_C3 * (double)acc6;
@@ -750,7 +976,8 @@ __global__ __launch_bounds__(MM6_THREADS) void k_spoly56(const float* __restrict
 // k_spoly4: the degree-4 items (bound X <= 1/40: orders 5 and 6 are below p6's own error) -- s56 = C1 <N_4, G^{(x)4} Q_4>, the n = 4
 // steps of k_spoly56 alone: 256 threads, 13 KB of LDS, persistent over the back part of ilist
 // ---------------------------------------------------------------------------------------------
-template <bool D8>
+// PRE: as k_spoly56 -- one wait for the prologue loads, every step's tables requested before the barrier in front of it
+template <bool D8, bool PRE>
 __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56, int N56p, const double* __restrict__ pairmat,
                                                 const double* __restrict__ zmax2, const unsigned int* __restrict__ amaxc,
                                                 const unsigned char* __restrict__ gflag,
@@ -786,28 +1013,67 @@ __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56,
     int a, a2;
     mm6_decode_pair_o(po, L, a, a2);
     const float bound2 = mm_collapse_bound2(amaxc[item], zmax2[a2]);
-    for (int idx = tid; idx < 2 * sy[4]; idx += 256) {
-      const int side = idx >= sy[4], c = idx - side * sy[4];
-      nq[idx] = mom56[(item * 2 + side) * N56p + c];       // (the degree-4 block: the first columns of mom56)
-    }
-    if (tid < 64) {
-      const int i = tid >> 3, j = tid & 7;
-      const double* pm = pairmat + ((size_t)b * P + (L + po)) * (d * d + 1);
-      const float g = (i < d && j < d) ? (float)pm[i * d + j] : 0.0f;
-      Gl[tid] = g;                                         // row-major: the Y side's
-      Gl[64 + j * 8 + i] = g;                              // transposed: the X side's
-    }
+    const double* pm = pairmat + ((size_t)b * P + (L + po)) * (d * d + 1);
+    const double* hr = whR + item * Mp;
+    const double* hc = whC + item * Mp;
+    const unsigned char* gf = gflag + item * (size_t)(Mp / MM_GROUP_ROWS);
     double s2r = 0.0, s2c = 0.0;
-    {
-      const double* hr = whR + item * Mp;
-      const double* hc = whC + item * Mp;
-      const unsigned char* gf = gflag + item * (size_t)(Mp / MM_GROUP_ROWS);
+    mm6_pre<NC0> p0 = {};                                     // the next step's tables (mm6_pre)
+    mm6_pre<1> p1 = {};
+    if constexpr (PRE) {
+      int tid = threadIdx.x;                               // (formed per item: see k_spoly56)
+      asm volatile("" : "+v"(tid));
+      constexpr int S2U = 4;
+      mm6_s2_batch<256, S2U> sb;
+      sb.issue(gf, hr, hc, tid, Mp);
+      const int gi = tid >> 3, gj = tid & 7;
+      const bool gok = tid < 64 && gi < d && gj < d;
+      const double gd = pm[gok ? gi * d + gj : 0];
+      constexpr int NQL = (2 * mm6_sym8(4) + 255) / 256;   // (d <= 8)
+      static_assert(NQL <= 16, "the moments of one thread as one register tuple");
+      typename mm6_vecw<mm6_vec_width(NQL)>::type r = 0.0f;
+      const float* mrow = mom56 + item * 2 * N56p;
+#pragma unroll
+      for (int q = 0; q < NQL; ++q) {
+        const int idx = tid + q * 256;
+        const int side = idx >= sy[4], c = idx - side * sy[4];
+        r[q] = mrow[idx < 2 * sy[4] ? side * N56p + c : 0];
+      }
+      mm6_req<D8, 0, 0, NC0, NW, 4>(p0, sy, tabi, tb, nullptr, wave, lane);
+      asm volatile("" : "+v"(r));                          // ONE wait for the moments
+#pragma unroll
+      for (int q = 0; q < NQL; ++q) {
+        const int idx = tid + q * 256;
+        if (idx < 2 * sy[4]) nq[idx] = r[q];
+      }
+      if (tid < 64) {
+        const float g = gok ? (float)gd : 0.0f;
+        Gl[tid] = g;                                       // row-major: the Y side's
+        Gl[64 + gj * 8 + gi] = g;                          // transposed: the X side's
+      }
+      sb.add(tid, Mp, s2r, s2c);
+      for (int m0 = tid + S2U * 256; m0 < Mp; m0 += S2U * 256) {
+        sb.issue(gf, hr, hc, m0, Mp);
+        sb.add(m0, Mp, s2r, s2c);
+      }
+    } else {
+      for (int idx = tid; idx < 2 * sy[4]; idx += 256) {
+        const int side = idx >= sy[4], c = idx - side * sy[4];
+        nq[idx] = mom56[(item * 2 + side) * N56p + c];     // (the degree-4 block: the first columns of mom56)
+      }
+      if (tid < 64) {
+        const int i = tid >> 3, j = tid & 7;
+        const float g = (i < d && j < d) ? (float)pm[i * d + j] : 0.0f;
+        Gl[tid] = g;                                       // row-major: the Y side's
+        Gl[64 + j * 8 + i] = g;                            // transposed: the X side's
+      }
       for (int m = tid; m < Mp; m += 256) {
         const double x = gf[m >> 6] ? hr[m] : 0.0, y = hc[m];
         s2r = fma(x, x, s2r); s2c = fma(y, y, s2c);
       }
     }
     __syncthreads();
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
     float G[64];
     auto load_G = [&](int transposed) __attribute__((always_inline)) {
 #pragma unroll
@@ -820,14 +1086,20 @@ __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56,
     const float* Q4 = nq + sy[4];
     const float* N4 = nq;
     load_G(1);
-    mm6_do<D8, 0, false, 0, NC0, NW, 4, 0>(Q4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, false, 0, NC0, NW, 4, 0, PRE>(Q4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 1, 1, 1, NW, 3>(p1, sy, tabi, tb, mult2, wave, lane);
     __syncthreads();
-    mm6_do<D8, 1, false, 1, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, mult2, xs4, dummy, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<1>(p1);
+    mm6_do<D8, 1, false, 1, 1, NW, 3, 37, PRE>(Bf4, X4, sy, tabi, tb, d, G, mult2, xs4, dummy, wave, lane, p1);
+    if constexpr (PRE) mm6_req<D8, 0, 0, NC0, NW, 4>(p0, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
+    if constexpr (PRE) mm6_pre_arrived<0>(p0);
     load_G(0);
-    mm6_do<D8, 0, true, 0, NC0, NW, 4, 0>(N4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane);
+    mm6_do<D8, 0, true, 0, NC0, NW, 4, 0, PRE>(N4, Bf4, sy, tabi, tb, d, G, nullptr, 0, dummy, wave, lane, p0);
+    if constexpr (PRE) mm6_req<D8, 1, 2, 1, NW, 3>(p1, sy, tabi, tb, nullptr, wave, lane);
     __syncthreads();
-    mm6_do<D8, 1, true, 2, 1, NW, 3, 37>(Bf4, X4, sy, tabi, tb, d, G, nullptr, xs4, acc4, wave, lane);
+    if constexpr (PRE) mm6_pre_arrived<2>(p1);
+    mm6_do<D8, 1, true, 2, 1, NW, 3, 37, PRE>(Bf4, X4, sy, tabi, tb, d, G, nullptr, xs4, acc4, wave, lane, p1);
     double tot = (double)MM_C6_C1 * (double)acc4;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -848,7 +1120,7 @@ __global__ __launch_bounds__(256) void k_spoly4(const float* __restrict__ mom56,
 // Degree-5/6 moments + contraction for the collapsed items of the last q stage (after k_wmom_perm on the same stream).
 // allow == 0 (forced worst tier): nothing is collapsed; s56 / estS are zeroed.
 int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, const MMWorkspaceLayout& wl,
-                        int B, int L, int d, int allow, int old_spoly56, hipStream_t stream) {
+                        int B, int L, int d, int allow, int old_spoly56, int old_loads, hipStream_t stream) {
   const int N56p = mm_moment56_cols(d);
   if (N56p <= 0 || wl.Po <= 0) return 0;
   if (allow) {
@@ -902,8 +1174,10 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
   const unsigned long long bit2 = (dev >= 0 && dev < 64) ? (1ull << dev) : 0ull;
   int ncu = bit2 ? ncu_cached[dev].load() : 0;
   if (!bit2 || !(attr2_done.load() & bit2)) {
-    hipError_t ea = hipFuncSetAttribute((const void*)k_spoly56<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_spoly56<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t ea = hipSuccess;
+    for (const void* fn : {(const void*)k_spoly56<false, false>, (const void*)k_spoly56<true, false>, (const void*)k_spoly56<false, true>,
+                           (const void*)k_spoly56<true, true>})
+      if (ea == hipSuccess) ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (ea != hipSuccess) return (int)ea;
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev < 64 ? dev : 0) != hipSuccess || v <= 0) v = 256;
@@ -915,7 +1189,11 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
   const int g56 = nitem < ncu ? nitem : ncu, g4 = nitem < 8 * ncu ? nitem : 8 * ncu;
   // d = 8: the steps with compile-time sizes (mm6_step8), unless the caller asks for the generic ones (MM_ISTAGE_OLD_SPOLY56)
   const bool d8 = d == 8 && !old_spoly56;
-  hipLaunchKernelGGL((d8 ? k_spoly56<true> : k_spoly56<false>), dim3(g56), dim3(MM6_THREADS), shm, stream, (const float*)(ws + wl.mom56), N56p,
+  // the loads of an item issued ahead of their use (PRE), unless the caller asks for loads at their use (MM_ISTAGE_OLD_SPOLY_LOADS)
+  const bool pre = !old_loads;
+  const auto k56 = d8 ? (pre ? k_spoly56<true, true> : k_spoly56<true, false>) : (pre ? k_spoly56<false, true> : k_spoly56<false, false>);
+  const auto k4 = d8 ? (pre ? k_spoly4<true, true> : k_spoly4<true, false>) : (pre ? k_spoly4<false, true> : k_spoly4<false, false>);
+  hipLaunchKernelGGL(k56, dim3(g56), dim3(MM6_THREADS), shm, stream, (const float*)(ws + wl.mom56), N56p,
                      (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zmax2), (const unsigned int*)(ws + wl.amaxc),
                      (const unsigned char*)(ws + wl.gflag), (const double*)(ws + wl.whR), (const double*)(ws + wl.whC),
                      packed + ml.tab56, mm_tab56(d), L, d, wl.P, wl.Mp, (const int*)ilist, (double*)(ws + wl.s56), (float*)(ws + wl.estS));
@@ -924,7 +1202,7 @@ int mm_launch_moments56(const char* packed, const MMModelLayout& ml, char* ws, c
     if (e5 != hipSuccess) return (int)e5;
   }
   const size_t shm4 = (size_t)(((2 * sy[4] + sy[1] * sy[3] + sy[2] * (sy[2] + 1) + 3) & ~3) + 128 + 2 * 3 * 4 + 8) * sizeof(float);
-  hipLaunchKernelGGL((d8 ? k_spoly4<true> : k_spoly4<false>), dim3(g4), dim3(256), shm4, stream, (const float*)(ws + wl.mom56), N56p,
+  hipLaunchKernelGGL(k4, dim3(g4), dim3(256), shm4, stream, (const float*)(ws + wl.mom56), N56p,
                      (const double*)(ws + wl.pairmat), (const double*)(packed + ml.zmax2), (const unsigned int*)(ws + wl.amaxc),
                      (const unsigned char*)(ws + wl.gflag), (const double*)(ws + wl.whR), (const double*)(ws + wl.whC),
                      packed + ml.tab56, mm_tab56(d), L, d, wl.P, wl.Mp, nitem, (const int*)ilist, (double*)(ws + wl.s56),

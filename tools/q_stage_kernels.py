@@ -16,7 +16,8 @@ ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--recipe", default="baseline", choices=["baseline", "pilco"])
 ap.add_argument("--reduce", action="store_true", help="also run the two sweeps (stage calls)")
 ap.add_argument("--extra-flags", type=int, default=0,
-                help="internal bits OR-ed into every call, e.g. 33554432 = MM_ISTAGE_OLD_DIAG_MAP (csrc/mm_common.h)")
+                help="internal bits OR-ed into every call, e.g. 33554432 = MM_ISTAGE_OLD_DIAG_MAP, 536870912 = MM_ISTAGE_OLD_SPOLY_LOADS "
+                     "(csrc/mm_common.h)")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 L = d = 8; M = 2000
